@@ -14,6 +14,13 @@ sub-quantisers model-parallel and encodes its own rows (lance_amd/dist.py: creat
 build plus the all-gather of the 20 bytes per row that gives every rank a replica.  `value` = the replicas serving their own
 query batches ("weak" scaling, no data-path collective); `multi_gpu.list_sharded_qps_strong_scaling` = the same batch
 answered jointly by IVF lists sharded over the ranks (all_to_all by list owner, one all-gather + device merge per batch).
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) builds the index, measures recall@10, warms up, times the N steps and prints
+the line (`value`, `ms_per_step` = milliseconds per timed step, `build_sec`, `recall_at_10`).  `--full` adds everything else the
+line used to carry: latencies and the recall grid, per-kernel timing and rooflines, PMC traffic, host-buffer runs, the child runs
+(f32 refine source, other metrics), the CPU baseline and, with N ranks, the replicated build and the strong-scaling run.
+`--dump-outputs DIR` writes what the last timed step returned (ids, distances) as .npy files; the inputs are seeded, so two
+builds of the project can be compared output for output.
 """
 import argparse
 import json
@@ -81,6 +88,35 @@ def collect_pmc_traffic(kernel_substr, child_args, timeout_s=300):
             "`bench.py " + " ".join(child_args) + "`; bytes = 1024 x counter, FETCH_SIZE x 2 (gfx950 correction, MI355X_MICROARCH.md HBM section)")
 
 
+def print_line(result):
+    # RCCL's banner sits in the C stdio buffer until exit: push it out first so that the JSON line is the LAST line
+    import ctypes
+    try:
+        ctypes.CDLL(None).fflush(None)
+    except Exception:
+        pass
+    sys.stdout.flush()
+    print(json.dumps(result), flush=True)
+
+
+def dump_outputs(out_dir, ids, dists, max_bytes=64 << 20):
+    """--dump-outputs: what the timed path returned to its caller in the last step -- the (nq, k) row ids (int64, written as
+    float64: exact below 2^53) and distances (float32) -- as out_dir/ids.npy and out_dir/distances.npy.  A batch larger than
+    max_bytes is cut to a fixed, seeded sample of its queries, whose indices go to out_dir/query_rows.npy."""
+    import numpy as np
+    ids = ids.cpu().numpy().astype(np.float64)
+    dists = dists.cpu().numpy().astype(np.float32)
+    per_query = ids.shape[1] * (ids.itemsize + dists.itemsize)
+    os.makedirs(out_dir, exist_ok=True)
+    if ids.shape[0] * per_query > max_bytes:
+        keep = max_bytes // (per_query + 8)
+        rows = np.sort(np.random.default_rng(0).choice(ids.shape[0], keep, replace=False))
+        ids, dists = ids[rows], dists[rows]
+        np.save(os.path.join(out_dir, "query_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "ids.npy"), ids)
+    np.save(os.path.join(out_dir, "distances.npy"), dists)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -102,6 +138,12 @@ def main():
     ap.add_argument("--no-grid", action="store_true", help="skip the small-batch latencies and the SURVEY 8(d) recall grid (a few seconds)")
     ap.add_argument("--nlist", type=int, default=None, help="override the configuration's number of IVF lists (tests: a count the ranks do not divide)")
     ap.add_argument("--no-extras", action="store_true", help="skip the child run on the f32 refine source and the PCIe-inclusive build (round 6 additions to the line)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: latencies and recall grid, per-kernel timing and rooflines, PMC traffic, "
+                         "host-buffer runs, the f32-refine and other-metric child runs, the CPU baseline, and (N ranks) the replicated "
+                         "build and the list-sharded strong-scaling run.  A plain run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned (ids as float64, distances as float32) to DIR/*.npy")
     # ranks started by this script's own launcher take their arguments from the environment: torchrun's argument parser refuses
     # `--n` after the script name (an abbreviation of several of ITS options: gpurun r05a)
     args = ap.parse_args(json.loads(os.environ["LANCE_BENCH_ARGV"])) if "LANCE_BENCH_ARGV" in os.environ else ap.parse_args()
@@ -111,6 +153,8 @@ def main():
     # against the world size instead of being ignored.
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         import socket
         with socket.socket() as sk:
@@ -218,7 +262,7 @@ def main():
         build_sec = min(build_secs)
         # informational (never `build_sec`): the same build when the boundary hands over a HOST buffer -- the column crosses PCIe first
         build_sec_pcie = None
-        if not args.no_extras and os.environ.get("LANCE_BENCH_CHILD") != "1":
+        if args.full and not args.no_extras and os.environ.get("LANCE_BENCH_CHILD") != "1":
             hx = x.cpu().pin_memory()
             xd = torch.empty_like(x)
             bt = []
@@ -255,7 +299,7 @@ def main():
 
         build_once("sharded")            # warm-up
         secs = {}
-        for mode in ("replicated", "sharded"):
+        for mode in (("replicated", "sharded") if args.full else ("sharded",)):
             best = float("inf")
             for _ in range(2):
                 idx, bld, bs = build_once(mode)
@@ -268,7 +312,7 @@ def main():
         torch.cuda.synchronize()
         mg = {"rccl_ranks": world, "transport": "rccl" if backend == "nccl" else f"{backend} through host memory" + (", all ranks on one GPU" if one_gpu else ""),
               "rows_per_rank": hi - lo, "build_sec_ivf_sharded_allreduce": secs["sharded"],
-              "build_sec_ivf_replicated": secs["replicated"], "raw_vectors_allgather_sec": time.perf_counter() - t0,
+              "build_sec_ivf_replicated": secs.get("replicated"), "raw_vectors_allgather_sec": time.perf_counter() - t0,
               "build_stages_ms_sharded": {k_: round(v * 1e3, 3) for k_, v in bld.stats.seconds.items()},
               # what "sharded" IVF training means at this nlist, and what it can be checked against
               "ivf_training_sharded_is": ("hierarchical k-means (nlist > 256, kmeans.rs:1027) with its splits spread over the ranks: bit-identical to the "
@@ -276,28 +320,29 @@ def main():
                                           "row-sharded Lloyd loop, one all-reduce per iteration: the sums arrive in rank order, not row order -- equal to the "
                                           "single-GPU trainer to f32 round-off only (no oracle equality; one rank: identical)"),
               "ivf_hierarchical_rounds": getattr(bld.stats, "ivf_hierarchical", None)}
-        # strong-scaling line: the IVF lists sharded over the ranks (list p -> rank p % N, rows moved by all_to_all), every
-        # rank answers the SAME query batches with its lists, one all-gather + device (dist, rowid) merge per batch
-        shard, l2g = ld.list_shard_index(bld, x_local)
-        common = [((sift_like(args.nq, d, seed=9000 + i, device=dev, n_clusters=4096) / 256.0).to(torch.float16) if half else
-                   sift_like(args.nq, d, seed=9000 + i, device=dev)) for i in range(2)]
+        if args.full:
+            # strong-scaling line: the IVF lists sharded over the ranks (list p -> rank p % N, rows moved by all_to_all), every
+            # rank answers the SAME query batches with its lists, one all-gather + device (dist, rowid) merge per batch
+            shard, l2g = ld.list_shard_index(bld, x_local)
+            common = [((sift_like(args.nq, d, seed=9000 + i, device=dev, n_clusters=4096) / 256.0).to(torch.float16) if half else
+                       sift_like(args.nq, d, seed=9000 + i, device=dev)) for i in range(2)]
 
-        def lstep(i):
-            return ld.search_list_sharded(lambda qq, kk, npb, rf: shard.search(qq, kk, npb, rf), l2g, common[i % 2], args.k, args.nprobes,
-                                          args.refine, engine=eng, local_candidates=lambda qq, ke, npb: shard.search_candidates(qq, ke, npb))
+            def lstep(i):
+                return ld.search_list_sharded(lambda qq, kk, npb, rf: shard.search(qq, kk, npb, rf), l2g, common[i % 2], args.k, args.nprobes,
+                                              args.refine, engine=eng, local_candidates=lambda qq, ke, npb: shard.search_candidates(qq, ke, npb))
 
-        li, _ = lstep(0)
-        ri, _ = idx.search_device(common[0], args.k, args.nprobes, args.refine)
-        mg["list_sharded_equals_replica"] = bool(torch.equal(li, ri))
-        torch.cuda.synchronize()
-        dist.barrier()
-        t0 = time.perf_counter()
-        for i in range(args.steps):
-            lstep(i)
-        torch.cuda.synchronize()
-        dist.barrier()
-        mg["list_sharded_qps_strong_scaling"] = args.nq * args.steps / (time.perf_counter() - t0)
-        shard.close()
+            li, _ = lstep(0)
+            ri, _ = idx.search_device(common[0], args.k, args.nprobes, args.refine)
+            mg["list_sharded_equals_replica"] = bool(torch.equal(li, ri))
+            torch.cuda.synchronize()
+            dist.barrier()
+            t0 = time.perf_counter()
+            for i in range(args.steps):
+                lstep(i)
+            torch.cuda.synchronize()
+            dist.barrier()
+            mg["list_sharded_qps_strong_scaling"] = args.nq * args.steps / (time.perf_counter() - t0)
+            shard.close()
 
     # ---- recall@10 on a 1000-query sample against exact flat top-10 (GPU flat kernel,
     # itself parity-tested against the oracle) ----------------------------------------------
@@ -310,7 +355,7 @@ def main():
     # recall@k over nprobes x refine_factor).  Latency = wall time of one synchronous call (host launch + device + the flags read-back),
     # median of 50 after 5 warm calls, queries resident on the device; grid = recall@10 of the 1000-query sample + ms per 1000-query batch.
     latency, recall_grid = None, None
-    if not args.no_grid and os.environ.get("LANCE_BENCH_PMC_CHILD") != "1" and rank == 0:
+    if args.full and not args.no_grid and os.environ.get("LANCE_BENCH_PMC_CHILD") != "1" and rank == 0:
         latency = {}
         for nq_l in (1, 16, 256):
             ql = qbatches[1][:nq_l].contiguous()
@@ -349,7 +394,7 @@ def main():
     offs = torch.from_numpy(idx._ix.part_offsets().astype(np.int64)).to(dev)
     sizes = offs[1:] - offs[:-1]
     scan_bytes, scan_bytes_c1 = [], []
-    for qb in qbatches:
+    for qb in (qbatches if args.full else []):
         probes, _ = eng.find_partitions(qb, idx._ix.centroids, args.nprobes)
         per = sizes[probes.long()]
         scan_bytes.append(int(per.sum().item()) * m)
@@ -401,6 +446,61 @@ def main():
     elapsed = time.perf_counter() - t0
     if os.environ.get("LANCE_BENCH_PMC_CHILD") == "1":      # a counter pass of collect_pmc_traffic: the launches are all it is for
         return
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *outs[(args.steps - 1) % nstreams])
+    if world > 1:
+        from lance_amd import dist as ld
+        tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
+        ld._all_reduce(tt, op=dist.ReduceOp.MAX)
+        elapsed = tt.item()
+        if "list_sharded_qps_strong_scaling" in mg:
+            tl = torch.tensor([mg["list_sharded_qps_strong_scaling"]], dtype=torch.float64, device=dev)
+            ld._all_reduce(tl, op=dist.ReduceOp.MIN)
+            mg["list_sharded_qps_strong_scaling"] = tl.item()
+    ms_per_step = elapsed / args.steps * 1e3
+    qps = world * args.nq * args.steps / elapsed
+    c4 = args.config == "c4"
+    result = {
+        "metric": ("QPS @ recall@10 (SIFT-1M IVF_PQ nlist=256 M=16) + index-build sec" if args.config == "c2" else
+                   "QPS @ recall@10 (synthetic f16 x128, IVF_PQ nlist=4096 M=16; BASELINE config 4 shape) + index-build sec" if c4 else
+                   "QPS @ recall@10 (synthetic int8 x128, IVF_PQ nlist=65536 M=32, hierarchical k-means; BASELINE config 5 shape) + index-build sec"),
+        "value": qps,
+        "unit": "queries/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32" if args.config == "c2" else "f16 rows, f32 arithmetic" if c4 else "int8 rows, f32 arithmetic",
+        "data": "synthetic",
+        "config": {"workload": ("SIFT-1M-like 1Mx128 f32, IVF_PQ nlist=256 M=16 nbits=8, build+search on MI355X" if args.config == "c2" else
+                                f"C4 shape: {args.n} x 128 f16 rows, IVF_PQ nlist=4096 M=16 nbits=8, build+search on MI355X" if c4 else
+                                f"C5 shape: {args.n} x 128 int8 rows, IVF_PQ nlist=65536 M=32 nbits=8 (hierarchical k-means), build+search on MI355X"),
+                   "n": args.n, "d": d, "nlist": nlist, "m": m, "queries_per_step_per_gpu": args.nq, "k": args.k,
+                   "nprobes": args.nprobes, "refine_factor": args.refine,
+                   "parallelism": (f"build: rows sharded over {world} ranks, RCCL all-reduce per Lloyd iteration; search: replica x{world} "
+                                   f"(weak) + list-sharded (strong)") if multi else "single"},
+        "recall_at_10": recall,
+        "streams": nstreams,
+        "graph_priming_calls": graph_priming,
+        "build_sec": build_sec,
+        "build_sec_pcie_inclusive": build_sec_pcie,
+        # N > 1: the two numbers that say something about scaling (the replica `value` is linear by construction): the SAME
+        # query batches answered jointly by list shards (strong scaling, --full), and the row-sharded build with one all-reduce per
+        # Lloyd iteration.  null at N = 1.  No multi-GPU hardware record exists for them before the driver's SCALE run.
+        "strong_scaling_list_sharded_qps": mg.get("list_sharded_qps_strong_scaling") if mg else None,
+        "build_sec_rows_sharded_allreduce": mg.get("build_sec_ivf_sharded_allreduce") if mg else None,
+        "multi_gpu": mg or None,
+        "build_stages_ms": {k_: round(v * 1e3, 3) for k_, v in (idx.stats.seconds.items() if idx.stats else [])},
+    }
+    if not args.full:      # a plain run: the headline line and nothing else
+        if rank == 0:
+            print_line(result)
+        if world > 1 or force_dist:
+            dist.destroy_process_group()
+        return
     # kernel-level timing pass (same batches, one stream, events on that stream)
     eng.timing(True)
     for i in range(args.steps):
@@ -411,15 +511,6 @@ def main():
     kt = {kname: eng.timing_query(kname) for kname in ("dist_matrix", "select_probes", "pm_group", "ivfpq_scan", "ivfpq_scan_c0",
                                                        "q_residual", "ivfpq_scan_c1", "ivfpq_merge", "ivfpq_exact", "refine")}
     mscan = eng.timing_query("ivfpq_mscan")[1] > 0      # the main pass ran as the matrix-core filter scan (search_ms.hip)
-    if world > 1:
-        from lance_amd import dist as ld
-        tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
-        ld._all_reduce(tt, op=dist.ReduceOp.MAX)
-        elapsed = tt.item()
-        if "list_sharded_qps_strong_scaling" in mg:
-            tl = torch.tensor([mg["list_sharded_qps_strong_scaling"]], dtype=torch.float64, device=dev)
-            ld._all_reduce(tl, op=dist.ReduceOp.MIN)
-            mg["list_sharded_qps_strong_scaling"] = tl.item()
 
     if rank != 0:
         if world > 1:
@@ -450,8 +541,6 @@ def main():
             host_step(i)
         pcie_qps = args.nq * args.steps / (time.perf_counter() - t1)
 
-    ms_per_step = elapsed / args.steps * 1e3
-    qps = world * args.nq * args.steps / elapsed
     quantised = kt["ivfpq_scan_c1"][1] > 0 and not os.environ.get("LANCE_HIP_NO_QSCAN") and not os.environ.get("LANCE_HIP_PM_NOBOUND")
     if kt["ivfpq_scan_c1"][1] > 0:      # partition-major path: dominant launch = the main pass
         scan_ms, scan_launches = kt["ivfpq_scan_c1"]
@@ -552,44 +641,10 @@ def main():
             "build_stages_ms": {k_: round(v * 1e3, 3) for k_, v in (idx.stats.seconds.items() if idx.stats else [])},
         }
     guide_lds_peak = LDS_B64_CONFLICT_FREE_PER_CLK_CU * 256 * 2.4e9      # lane-gathers/s: ds_read_b64, 256 B/clk/CU, 256 CUs, 2.4 GHz
-    c4 = args.config == "c4"
-    result = {
-        "metric": ("QPS @ recall@10 (SIFT-1M IVF_PQ nlist=256 M=16) + index-build sec" if args.config == "c2" else
-                   "QPS @ recall@10 (synthetic f16 x128, IVF_PQ nlist=4096 M=16; BASELINE config 4 shape) + index-build sec" if c4 else
-                   "QPS @ recall@10 (synthetic int8 x128, IVF_PQ nlist=65536 M=32, hierarchical k-means; BASELINE config 5 shape) + index-build sec"),
-        "value": qps,
-        "unit": "queries/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32" if args.config == "c2" else "f16 rows, f32 arithmetic" if c4 else "int8 rows, f32 arithmetic",
-        "data": "synthetic",
-        "config": {"workload": ("SIFT-1M-like 1Mx128 f32, IVF_PQ nlist=256 M=16 nbits=8, build+search on MI355X" if args.config == "c2" else
-                                f"C4 shape: {args.n} x 128 f16 rows, IVF_PQ nlist=4096 M=16 nbits=8, build+search on MI355X" if c4 else
-                                f"C5 shape: {args.n} x 128 int8 rows, IVF_PQ nlist=65536 M=32 nbits=8 (hierarchical k-means), build+search on MI355X"),
-                   "n": args.n, "d": d, "nlist": nlist, "m": m, "queries_per_step_per_gpu": args.nq, "k": args.k,
-                   "nprobes": args.nprobes, "refine_factor": args.refine,
-                   "parallelism": (f"build: rows sharded over {world} ranks, RCCL all-reduce per Lloyd iteration; search: replica x{world} "
-                                   f"(weak) + list-sharded (strong)") if multi else "single"},
-        "recall_at_10": recall,
+    result.update({
         "exact_replays_last_step": exact_replays,
-        "streams": nstreams,
-        "graph_priming_calls": graph_priming,
         "host_buffers_qps_pcie_inclusive": pcie_qps,
-        "build_sec": build_sec,
-        "build_sec_pcie_inclusive": build_sec_pcie,
         "qps_f32_refine_source": None,
-        # N > 1: the two numbers that say something about scaling (the replica `value` is linear by construction): the SAME
-        # query batches answered jointly by list shards (strong scaling), and the row-sharded build with one all-reduce per
-        # Lloyd iteration.  null at N = 1.  No multi-GPU hardware record exists for them before the driver's SCALE run.
-        "strong_scaling_list_sharded_qps": mg.get("list_sharded_qps_strong_scaling") if mg else None,
-        "build_sec_rows_sharded_allreduce": mg.get("build_sec_ivf_sharded_allreduce") if mg else None,
-        "multi_gpu": mg or None,
-        "build_stages_ms": {k_: round(v * 1e3, 3) for k_, v in (idx.stats.seconds.items() if idx.stats else [])},
         "kernel_ms_per_step": {k_: round(v[0] / max(v[1], 1), 4) for k_, v in kt.items()},
         # frac = achieved / peak with peak from MI355X_MICROARCH.md (LDS table: conflict-free ds_read_b64, 2 cycles per wave-instruction
         # = 32 lanes/clk/CU, x 256 CUs x 2.4 GHz); the same rate against the random-gather microbenchmark of this run is kept as
@@ -599,7 +654,7 @@ def main():
         "latency": latency,
         "recall_grid": recall_grid,
         "roofline": None,
-    }
+    })
     common = {"traffic": traffic, "traffic_unit": "HBM bytes per launch", "traffic_source": traffic_src, "traffic_detail": traffic_detail,
               "traffic_recorded": traffic_recorded, "traffic_vs_algorithmic_code_bytes": (traffic / avg_bytes) if (traffic and avg_bytes) else None,
               "avg_launch_ms": avg_scan_ms, "survey_8d_code_bytes_per_launch": avg_bytes, "survey_8d_byte_rate_GBps": hbm_equiv,
@@ -704,7 +759,7 @@ def main():
         import subprocess
         env = dict(os.environ, LANCE_HIP_NO_RAW_COMPACT="1", LANCE_BENCH_CHILD="1")
         cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(args.steps), "--warmup", str(args.warmup), "--streams", str(args.streams),
-               "--no-pmc", "--no-cpu-baseline", "--no-grid", "--no-extras", "--config", args.config, "--n", str(args.n), "--nq", str(args.nq),
+               "--full", "--no-pmc", "--no-cpu-baseline", "--no-grid", "--no-extras", "--config", args.config, "--n", str(args.n), "--nq", str(args.nq),
                "--nprobes", str(args.nprobes), "--refine", str(args.refine), "--k", str(args.k)]
         try:
             cp = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
@@ -786,14 +841,7 @@ def main():
         result["cpu_baseline"] = None
     if world > 1 or force_dist:
         dist.destroy_process_group()
-    # RCCL's banner sits in the C stdio buffer until exit: push it out first so that the JSON line is the LAST line
-    import ctypes
-    try:
-        ctypes.CDLL(None).fflush(None)
-    except Exception:
-        pass
-    sys.stdout.flush()
-    print(json.dumps(result), flush=True)
+    print_line(result)
 
 
 if __name__ == "__main__":

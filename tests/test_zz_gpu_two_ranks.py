@@ -124,7 +124,7 @@ def test_bench_two_ranks_on_one_gpu_end_to_end():
     env = dict(os.environ, LANCE_BENCH_ONE_GPU="1", LANCE_BENCH_BACKEND="gloo", MASTER_PORT=str(_free_port()))
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--n", "200000",
-                        "--nq", "3000", "--no-pmc", "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+                        "--nq", "3000", "--full", "--no-pmc", "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     line = [l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1]
     j = json.loads(line)
@@ -145,7 +145,7 @@ def test_bench_eight_ranks_on_one_gpu_uneven_blocks_and_lists():
     env = dict(os.environ, LANCE_BENCH_ONE_GPU="1", LANCE_BENCH_BACKEND="gloo", MASTER_PORT=str(_free_port()))
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--n", "200003", "--nlist", "250",
-                        "--nq", "2000", "--no-pmc", "--no-cpu-baseline", "--no-grid"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
+                        "--nq", "2000", "--full", "--no-pmc", "--no-cpu-baseline", "--no-grid"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     line = [l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1]
     j = json.loads(line)
