@@ -286,7 +286,13 @@ __device__ __forceinline__ float cosine_exact_rt(const float *__restrict__ x, fl
 // metric value as the reference scans see it: L2 -> squared L2; DOT -> 1 - dot.
 template <int METRIC>
 __device__ __forceinline__ float finish_metric(float raw) {
-  if constexpr (METRIC == METRIC_DOT) return 1.0f - raw;
+  if constexpr (METRIC == METRIC_DOT) {
+    // A NaN dot product (a NaN element in the row) stays the NaN it is: the reference's `1.0 - dot` is a CPU subtraction, which hands a NaN
+    // operand on with its sign, and f32::total_cmp then sorts the positive NaN LAST.  The subtraction here came back with the sign bit SET
+    // (the operand is negated on its way into the adder), so under dot such rows were returned FIRST (tests/test_zz_gpu_flat_real.py).
+    const float v = 1.0f - raw;
+    return raw != raw ? raw : v;
+  }
   return raw;
 }
 

@@ -148,3 +148,22 @@ def test_dryrun_ivfflat_ties(fake, oracle):
     import test_zz_gpu_zz_ivfflat_ties as T
     T.test_ivf_flat_more_ties_than_the_pool_holds(oracle)
     T.test_ivf_flat_f16_cosine_norm_overflow_gives_nan_like_the_reference(oracle)
+
+
+# ---- flat KNN on real-valued data (tests/test_zz_gpu_flat_real.py): shapes, dtypes and the tests' own expectations, on reduced parameter sets
+@pytest.mark.parametrize("metric,d", [("l2", 20), ("dot", 136), ("l2", 2049)])
+def test_dryrun_flat_real_single_pass(fake, oracle, metric, d):
+    import test_zz_gpu_flat_real as R
+    R.test_single_pass_real_f32(fake, oracle, metric, d, ns=(4224, 4097), ks=(1, 128))
+
+
+@pytest.mark.parametrize("metric", ["l2", "dot"])
+def test_dryrun_flat_real_special_values(fake, oracle, metric):
+    import test_zz_gpu_flat_real as R
+    R.test_special_values_inside_the_answer(fake, oracle, metric)
+
+
+@pytest.mark.parametrize("metric,d", [("l2", 32), ("dot", 20)])
+def test_dryrun_flat_real_batch_path(fake, oracle, metric, d):
+    import test_zz_gpu_flat_real as R
+    R.test_batch_path_real_f32(fake, oracle, metric, d, nqs=(3,), ks=(10, 129))
