@@ -351,6 +351,22 @@ int lance_hip_flat_topk(lance_hip_ctx *ctx, int dtype, int metric, const void *x
                         uint64_t n, uint32_t d, const void *q, uint32_t nq, uint32_t k, uint64_t *ids,
                         float *dists);
 
+/* ---- flat KNN over a MULTIVECTOR column (Arrow List<FixedSizeList<T, d>>: one bag of vectors per row) ------------------
+ * values  [offsets[n_rows]][d]: the flattened child array, LANCE_HIP_F32 or LANCE_HIP_F16 (int8 / uint8 columns: LANCE_HIP_EINVAL);
+ * offsets [n_rows + 1], device, 64-bit, non-decreasing; row r holds the vectors offsets[r] .. offsets[r + 1] - 1;
+ * q       [nqv][d] in the column's element type, 1 <= nqv <= LANCE_HIP_MULTIVEC_MAX_QUERY_VECTORS.
+ * distance(row) = 1 - sum_i max_j (1 - dist(q_i, v_j)): the max by f32::total_cmp, the sum sequential in query-vector order,
+ * dist = l2 | 1 - dot | cosine.  A zero-length row is an error (LANCE_HIP_EINVAL; the reference unwraps a None there), reported
+ * after the scan: the outputs are then undefined.  Any d >= 1; k <= 1024; slots beyond n_rows: id UINT64_MAX, distance +inf.   */
+#define LANCE_HIP_MULTIVEC_MAX_QUERY_VECTORS 256
+/* multivec_distance (lance-linalg distance.rs:107-206): dists[n_rows] */
+int lance_hip_multivec_distance(lance_hip_ctx *ctx, int dtype, int metric, const void *values, const uint64_t *offsets,
+                                uint64_t n_rows, uint32_t d, const void *q, uint32_t nqv, float *dists);
+/* flat KNN over a multivector column (flat.rs:129-133 + SortExec(dist, rowid).fetch(k)); row_ids NULL -> row index */
+int lance_hip_flat_multivec_topk(lance_hip_ctx *ctx, int dtype, int metric, const void *values, const uint64_t *offsets,
+                                 const uint64_t *row_ids, uint64_t n_rows, uint32_t d, const void *q, uint32_t nqv,
+                                 uint32_t k, uint64_t *ids, float *dists);
+
 /* ---- N4: IVF_FLAT (FlatIndex sub-index over raw vectors: flat/index.rs:82-177, flat/storage.rs:345-402) ------ */
 /* Builds the per-partition FlatFloatStorage on the device: x[n][d] (dtype elements, widened exactly to f32) is
  * gathered into partition order (stable, rows with part id LANCE_HIP_NONE dropped).  L2, Dot and Cosine (f32 and f16 columns;

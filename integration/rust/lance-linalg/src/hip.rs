@@ -99,6 +99,13 @@ extern "C" {
         nprobes: u32, allow_by_rowid: *const u8, n_allow: u64, ids: *mut u64, dists: *mut f32) -> i32;
     pub fn lance_hip_flat_topk(ctx: *mut LanceHipCtx, dtype: i32, metric: i32, x: *const c_void, row_ids: *const u64,
         n: u64, d: u32, q: *const c_void, nq: u32, k: u32, ids: *mut u64, dists: *mut f32) -> i32;
+    /// multivec_distance (distance.rs:107-206) of one multivector query to every row of a List<FixedSizeList> column: `values` is the
+    /// list's child array, `offsets` [n_rows + 1] its offsets as u64 (device).  A row without a vector is LANCE_HIP_EINVAL.
+    pub fn lance_hip_multivec_distance(ctx: *mut LanceHipCtx, dtype: i32, metric: i32, values: *const c_void, offsets: *const u64,
+        n_rows: u64, d: u32, q: *const c_void, nqv: u32, dists: *mut f32) -> i32;
+    /// the same followed by SortExec(dist, rowid).fetch(k) (flat.rs:129-133); row_ids NULL -> row index
+    pub fn lance_hip_flat_multivec_topk(ctx: *mut LanceHipCtx, dtype: i32, metric: i32, values: *const c_void, offsets: *const u64,
+        row_ids: *const u64, n_rows: u64, d: u32, q: *const c_void, nqv: u32, k: u32, ids: *mut u64, dists: *mut f32) -> i32;
 }
 
 /// Maps a return code to the error type the reference path already produces (`Error::Index`), with the library's message.

@@ -10,7 +10,8 @@ from . import _lib
 from ._lib import LanceHipError
 
 __all__ = ["_lib", "LanceHipError", "Engine", "DeviceIndex", "KMeans", "IvfPqParams", "IvfPqIndex", "create_index",
-           "flat_knn", "train_ivf_centroids", "train_pq_codebook", "default_engine", "load_index", "validate_vector_index", "IndicesBuilder", "IvfModel", "PqModel"]
+           "flat_knn", "multivector_distance", "multivector_flat_knn", "train_ivf_centroids", "train_pq_codebook", "default_engine", "load_index",
+           "validate_vector_index", "IndicesBuilder", "IvfModel", "PqModel"]
 
 
 def __getattr__(name):
@@ -18,7 +19,8 @@ def __getattr__(name):
     if name in ("Engine", "DeviceIndex"):
         from . import engine
         return getattr(engine, name)
-    if name in ("KMeans", "IvfPqParams", "IvfPqIndex", "create_index", "flat_knn", "train_ivf_centroids",
+    if name in ("KMeans", "IvfPqParams", "IvfPqIndex", "create_index", "flat_knn", "multivector_distance", "multivector_flat_knn",
+                "train_ivf_centroids",
                 "train_pq_codebook", "default_engine", "load_index", "validate_vector_index"):
         from . import vector
         return getattr(vector, name)

@@ -131,3 +131,35 @@ def codebook_from_batch(batch, num_sub_vectors):
     sd = col.type.list_size
     flat = np.asarray(col.values.to_numpy(zero_copy_only=False))
     return flat.reshape(num_sub_vectors, -1, sd)
+
+
+def multivector_from_arrow(col):
+    """A multivector column -- pyarrow ListArray / LargeListArray / ChunkedArray of FixedSizeList<float16 | float32, d> -- as
+    (values ndarray [total vectors][d], offsets int64 [n_rows + 1]), the inputs of multivector_flat_knn.  A sliced array's
+    offsets are honoured (the values are those of its rows only, the offsets start at 0); a column with a null row, a null
+    vector or a null element is refused."""
+    chunks = col.chunks if isinstance(col, pa.ChunkedArray) else [col]
+    t = col.type
+    if not (pa.types.is_list(t) or pa.types.is_large_list(t)) or not pa.types.is_fixed_size_list(t.value_type):
+        raise ValueError(f"a multivector column is List<FixedSizeList<float16 | float32, d>>, got {t}")
+    et = t.value_type.value_type
+    if not (pa.types.is_float16(et) or pa.types.is_float32(et)):
+        raise ValueError(f"unsupported multivector element type {et}: float16 or float32")
+    d = t.value_type.list_size
+    np_t = np.float16 if pa.types.is_float16(et) else np.float32
+    vals, offs, base = [], [np.zeros(1, np.int64)], 0
+    for a in chunks:
+        if a.null_count:
+            raise ValueError("the multivector column holds null rows: not supported")
+        o = np.asarray(a.offsets.to_numpy(zero_copy_only=False), dtype=np.int64)
+        fsl = a.flatten()                    # the vectors of this (possibly sliced) chunk's rows
+        if fsl.null_count:
+            raise ValueError("the multivector column holds null vectors: not supported")
+        flat = fsl.flatten()
+        if flat.null_count:
+            raise ValueError("the multivector column holds null elements: not supported")
+        vals.append(np.asarray(flat.to_numpy(zero_copy_only=False), dtype=np_t).reshape(-1, d))
+        offs.append(o[1:] - o[0] + base)
+        base += int(o[-1] - o[0])
+    values = np.concatenate(vals) if vals else np.zeros((0, d), np_t)
+    return np.ascontiguousarray(values), np.concatenate(offs)

@@ -140,7 +140,10 @@ __device__ __forceinline__ f4 load4(const int8_t *p) {
 // Runtime-d version (both operands through pointers); same order.  Used by the
 // generic-dimension fallbacks and by small host-order helpers.  TB = float or __half
 // (f16 elements are widened one by one, l2.rs:128-159).
-template <int METRIC, typename TB = float, int LANES = 16>
+// SWAP (L2): the difference is taken as b - a.  Its square is the same bit for bit; what differs is a NaN element of b, which the
+// GPU's subtract returns with the sign flipped when it is the subtrahend and unchanged when it is the minuend (the reference's CPU
+// hands a NaN operand on unchanged from either side).  multivec.hip, where the sign of a NaN decides a maximum, sets it.
+template <int METRIC, typename TB = float, int LANES = 16, bool SWAP = false>
 __device__ __forceinline__ float dist_exact_rt(const float *__restrict__ a, const TB *__restrict__ bp, int d) {
   struct BView { const TB *p; __device__ __forceinline__ float operator[](int i) const { return ld_elem(p, i); } };
   const BView b{bp};
@@ -152,7 +155,7 @@ __device__ __forceinline__ float dist_exact_rt(const float *__restrict__ a, cons
       if constexpr (METRIC == METRIC_DOT) {
         acc = acc + a[i] * b[i];
       } else {
-        float diff = a[i] - b[i];
+        float diff = SWAP ? b[i] - a[i] : a[i] - b[i];
         acc = acc + diff * diff;
       }
     }
@@ -167,7 +170,7 @@ __device__ __forceinline__ float dist_exact_rt(const float *__restrict__ a, cons
       if constexpr (METRIC == METRIC_DOT) {
         sums[i] += a[c + i] * b[c + i];
       } else {
-        float diff = a[c + i] - b[c + i];
+        float diff = SWAP ? b[c + i] - a[c + i] : a[c + i] - b[c + i];
         sums[i] += diff * diff;
       }
     }
@@ -281,6 +284,67 @@ __device__ __forceinline__ float cosine_exact_rt(const float *__restrict__ x, fl
   const float y_norm = reduce8_tree(u16) + reduce8_tree(yn8) + nrest * nrest;
   const float xy = reduce8_tree(t16) + reduce8_tree(xy8) + dist_exact_rt<METRIC_DOT, TB>(x + aligned, yp + aligned, d - aligned);
   return 1.0f - xy / x_norm / sqrtf(y_norm);
+}
+
+// cosine_exact_rt split for kernels that hold x in registers and visit every y with MANY x (multivec.hip): the y-only half
+// (sqrtf(y_norm), once per y) and the x-dependent half, for the compile-time dimensions 8, 16 (cosine_once) and the multiples of 16.
+// Operation for operation the sequence of cosine_exact_rt -- the empty 8-group and the zero-length tails included -- so the value is
+// bit-identical to it.  The 16 accumulators are taken four at a time (dist_exact's lane groups: one LDS latency per group, a bounded
+// number of registers); each accumulator still sees its chunks in order.
+template <int D, bool SQUARE>
+__device__ __forceinline__ void cosine_acc16(const RegVec<D> *x, const float *__restrict__ y, float (&out)[16]) {
+  constexpr int NJ = D / 16;
+#pragma unroll
+  for (int ig = 0; ig < 4; ++ig) {
+    f4 bv[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) bv[j] = *reinterpret_cast<const f4 *>(y + 16 * j + 4 * ig);
+    f4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      f4 av;
+      if constexpr (SQUARE) av = bv[j]; else av = x->q[4 * j + ig];
+      acc = __builtin_elementwise_fma(av, bv[j], acc);      // four correctly rounded fused multiply-adds (two v_pk_fma_f32)
+    }
+    out[4 * ig] = acc.x; out[4 * ig + 1] = acc.y; out[4 * ig + 2] = acc.z; out[4 * ig + 3] = acc.w;
+  }
+}
+
+template <int D>
+__device__ __forceinline__ float cosine_exact_ysqrt(const float *__restrict__ y) {
+  static_assert(D == 8 || D % 16 == 0, "8, or whole groups of 16");
+  if constexpr (D == 8 || D == 16) {  // cosine_once
+    float u[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) u[i] = D == 16 ? y[i] * y[i] + y[i + 8] * y[i + 8] : y[i] * y[i];
+    return sqrtf(reduce8_tree(u));
+  } else {
+    float yn16[16], yn8[8], u16[8];
+    cosine_acc16<D, true>(nullptr, y, yn16);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { yn8[i] = 0.0f; u16[i] = yn16[i] + yn16[i + 8]; }
+    const float nrest = norm_l2_rt<float>(y + D, 0);
+    return sqrtf(reduce8_tree(u16) + reduce8_tree(yn8) + nrest * nrest);
+  }
+}
+
+// y_sqrt = cosine_exact_ysqrt<D>(y)
+template <int D>
+__device__ __forceinline__ float cosine_exact_fixed(const RegVec<D> &x, float x_norm, const float *__restrict__ y, float y_sqrt) {
+  static_assert(D == 8 || D % 16 == 0, "8, or whole groups of 16");
+  if constexpr (D == 8 || D == 16) {  // cosine_once
+    float t[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) t[i] = D == 16 ? x.get(i) * y[i] + x.get(i + 8) * y[i + 8] : x.get(i) * y[i];
+    return 1.0f - reduce8_tree(t) / x_norm / y_sqrt;
+  } else {
+    float xy16[16], xy8[8], t16[8];
+    cosine_acc16<D, false>(&x, y, xy16);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { xy8[i] = 0.0f; t16[i] = xy16[i] + xy16[i + 8]; }
+    const float xy = reduce8_tree(t16) + reduce8_tree(xy8) + dist_exact_rt<METRIC_DOT, float>(y + D, y + D, 0);
+    return 1.0f - xy / x_norm / y_sqrt;
+  }
 }
 
 // metric value as the reference scans see it: L2 -> squared L2; DOT -> 1 - dot.

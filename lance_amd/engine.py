@@ -69,6 +69,52 @@ def _model(a, ref):
     return t.to(torch.float32 if ref.dtype == torch.int8 else ref.dtype).to(_dev()).contiguous()
 
 
+def _dtype_name(a):
+    return str(a.dtype).replace("torch.", "") if isinstance(a, torch.Tensor) else np.asarray(a).dtype.name
+
+
+def check_multivector(values, offsets, q, metric, k=None):
+    """Host-side validation of a multivector column (values [N][d], offsets [n_rows + 1]) and a multivector query q [nqv][d]; every
+    problem is a ValueError raised before any device call.  -> (metric name, offsets as a contiguous int64 numpy array)"""
+    m = str(metric).lower()
+    if m == "euclidean":
+        m = "l2"
+    if m == "hamming":
+        raise ValueError("metric hamming is not supported for multivector columns (uint8 / hamming columns are not in this library)")
+    if m not in ("l2", "cosine", "dot"):
+        raise ValueError(f"metric {metric} is not supported for multivector columns: l2, dot or cosine")
+    name = _dtype_name(values)
+    if name not in ("float32", "float16"):
+        raise ValueError(f"unsupported multivector element type {name}: the column must be float32 or float16 "
+                         "(int8 / uint8 columns have no arm in the reference's float path)")
+    if len(values.shape) != 2 or int(values.shape[1]) < 1:
+        raise ValueError(f"values must be the flattened [total vectors][d] child array, got shape {tuple(values.shape)}")
+    d = int(values.shape[1])
+    if len(q.shape) != 2 or int(q.shape[1]) != d:
+        raise ValueError(f"q must be [nqv][d] with d = {d}, the dimension of the column, got shape {tuple(q.shape)}")
+    nqv = int(q.shape[0])
+    if nqv < 1:
+        raise ValueError("q holds no vector: a multivector query has at least one")
+    if nqv > _lib.MULTIVEC_MAX_QUERY_VECTORS:
+        raise ValueError(f"q holds {nqv} vectors, above the limit of {_lib.MULTIVEC_MAX_QUERY_VECTORS} query vectors per call")
+    off = offsets.detach().cpu().numpy() if isinstance(offsets, torch.Tensor) else np.asarray(offsets)
+    if off.ndim != 1 or off.size < 1 or off.dtype.kind not in "iu":
+        raise ValueError("offsets must be a 1-D integer array of n_rows + 1 entries")
+    off = np.ascontiguousarray(off.astype(np.int64))
+    if off[0] != 0:
+        raise ValueError(f"offsets must start at 0, got {int(off[0])}")
+    step = np.diff(off)
+    if (step < 0).any():
+        raise ValueError(f"offsets decrease at row {int(np.argmax(step < 0))}")
+    if off[-1] != int(values.shape[0]):
+        raise ValueError(f"offsets must end at len(values) = {int(values.shape[0])}, got {int(off[-1])}")
+    if (step == 0).any():
+        raise ValueError(f"row {int(np.argmax(step == 0))} is empty: every row of a multivector column must hold at least one vector")
+    if k is not None and not 1 <= int(k) <= 1024:
+        raise ValueError(f"k={k} not supported (1..1024)")
+    return m, off
+
+
 _DT = {"float32": (torch.float32, 0), "float16": (torch.float16, 1), "int8": (torch.int8, 2)}
 
 
@@ -370,6 +416,38 @@ class Engine:
         torch.cuda.synchronize()
         check(self.lib.lance_hip_flat_topk(self.h, dt, METRICS[metric], _ptr(x), _ptr(rid), n, d, _ptr(q), nq, k,
                                            _ptr(ids), _ptr(dists)))
+        return ids, dists
+
+    def multivec_distance(self, values, offsets, q, metric="cosine"):
+        """multivec_distance (lance-linalg distance.rs:107-206) of the multivector query q [nqv][d] to every row of a multivector
+        column: values [total vectors][d] (float32 / float16), offsets [n_rows + 1] -> [n_rows] float32"""
+        m, off = check_multivector(values, offsets, q, metric)
+        v, dt = _vec(values)
+        qd = _like(q, v)
+        od = to_device(off, torch.int64)
+        n = off.size - 1
+        dists = torch.empty(n, dtype=torch.float32, device=v.device)
+        torch.cuda.synchronize()
+        check(self.lib.lance_hip_multivec_distance(self.h, dt, METRICS[m], _ptr(v), _ptr(od), n, v.shape[1], _ptr(qd), qd.shape[0],
+                                                   _ptr(dists)))
+        return dists
+
+    def multivec_topk(self, values, offsets, q, k, metric="cosine", row_ids=None):
+        """exhaustive KNN of one multivector query over a multivector column -> (ids [k] int64, distances [k]) sorted by
+        (distance, row id); slots beyond the number of rows hold id -1 and distance +inf, as flat_topk's do"""
+        m, off = check_multivector(values, offsets, q, metric, k)
+        n = off.size - 1
+        if row_ids is not None and int(row_ids.shape[0]) != n:
+            raise ValueError(f"row_ids must hold one id per row ({n}), got {int(row_ids.shape[0])}")
+        v, dt = _vec(values)
+        qd = _like(q, v)
+        od = to_device(off, torch.int64)
+        rid = None if row_ids is None else to_device(row_ids, torch.int64)
+        ids = torch.empty(k, dtype=torch.int64, device=v.device)
+        dists = torch.empty(k, dtype=torch.float32, device=v.device)
+        torch.cuda.synchronize()
+        check(self.lib.lance_hip_flat_multivec_topk(self.h, dt, METRICS[m], _ptr(v), _ptr(od), _ptr(rid), n, v.shape[1], _ptr(qd),
+                                                    qd.shape[0], k, _ptr(ids), _ptr(dists)))
         return ids, dists
 
     def search_stats(self):

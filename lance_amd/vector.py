@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from ._lib import METRICS, NONE
-from .engine import DeviceFlatIndex, DeviceIndex, Engine, to_device
+from .engine import DeviceFlatIndex, DeviceIndex, Engine, check_multivector, to_device
 
 _engine = None
 
@@ -577,3 +577,40 @@ def flat_knn(x, q, k=10, metric="l2", engine=None, prefilter=None):
         return eng.flat_topk(xt[keep].contiguous(), q, k, _normalize_metric_type(metric), row_ids=keep)
     ids, dists = eng.flat_topk(x, q, k, _normalize_metric_type(metric))
     return ids, dists
+
+
+def multivector_distance(values, offsets, q, metric="cosine", engine=None):
+    """Distances of ONE multivector query q [nqv][d] to every row of a multivector column (Arrow List<FixedSizeList<T, d>>:
+    values [total vectors][d] float32 / float16, offsets [n_rows + 1]; arrow_io.multivector_from_arrow gives both) -> [n_rows].
+    distance = 1 - sum_i max_j (1 - dist(q_i, v_j)), multivec_distance (lance-linalg distance.rs:107-206)."""
+    check_multivector(values, offsets, q, metric)
+    return (engine or default_engine()).multivec_distance(values, offsets, q, metric)
+
+
+def multivector_flat_knn(values, offsets, q, k=10, metric="cosine", engine=None, prefilter=None, row_ids=None):
+    """Exhaustive KNN of one multivector query over a multivector column: (row ids [k], distances [k]) sorted by (distance, row id)
+    (the flat scan of a List column, lance-index flat.rs:129-133).  prefilter: boolean array over rows, as in flat_knn -- the scan
+    covers the selected rows, the ids stay those of the full table (row_ids, or the row index)."""
+    _, off = check_multivector(values, offsets, q, metric, k)
+    n = off.size - 1
+    mask = None
+    if prefilter is not None:
+        mask = prefilter.detach().cpu().numpy() if isinstance(prefilter, torch.Tensor) else np.asarray(prefilter)
+        if mask.dtype != np.bool_ or mask.shape != (n,):
+            raise ValueError(f"prefilter must be a boolean array over the {n} rows, got {mask.dtype} {mask.shape}")
+    if row_ids is not None and int(row_ids.shape[0]) != n:
+        raise ValueError(f"row_ids must hold one id per row ({n}), got {int(row_ids.shape[0])}")
+    eng = engine or default_engine()
+    if mask is None:
+        return eng.multivec_topk(values, offsets, q, k, metric, row_ids=row_ids)
+    # the selected rows' vectors, gathered on the device (plumbing): the scan sees a column of its own
+    vt = values.to(to_device(off).device) if isinstance(values, torch.Tensor) else to_device(values)
+    od = to_device(off)
+    keep = torch.nonzero(to_device(mask)).reshape(-1)
+    lens = (od[1:] - od[:-1])[keep]
+    sub_off = torch.zeros(keep.numel() + 1, dtype=torch.int64, device=od.device)
+    sub_off[1:] = torch.cumsum(lens, 0)
+    total = int(sub_off[-1])
+    src = torch.repeat_interleave(od[:-1][keep] - sub_off[:-1], lens) + torch.arange(total, device=od.device)
+    rid = keep if row_ids is None else to_device(row_ids, torch.int64)[keep]
+    return eng.multivec_topk(vt[src].contiguous(), sub_off.cpu().numpy(), q, k, metric, row_ids=rid)
