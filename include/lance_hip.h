@@ -389,6 +389,41 @@ int lance_hip_ivfflat_search(lance_hip_ctx *ctx, const lance_hip_index *idx, con
 int lance_hip_ivfflat_search_filtered(lance_hip_ctx *ctx, const lance_hip_index *idx, const void *q, uint32_t nq, uint32_t k,
                                       uint32_t nprobes, const uint8_t *allow_by_rowid, uint64_t n_allow, uint64_t *ids, float *dists);
 
+/* ---- N5: 8-bit scalar quantisation and IVF_SQ (lance-index/src/vector/sq.rs, sq/storage.rs, sq/builder.rs) ------------ */
+/* Columns are LANCE_HIP_F32 or LANCE_HIP_F16 (an int8 column is refused: the reference's SQ builder takes float arrays only; f64
+ * columns are not in this library).  1 <= d <= LANCE_HIP_SQ_MAX_DIM; only num_bits = 8 exists (sq.rs `// TODO: support SQ4`).
+ * bounds_host is the quantiser's Range<f64> as double[2] = {start, end} in HOST memory.                              */
+#define LANCE_HIP_SQ_MAX_DIM 16384
+/* ScalarQuantizer::update_bounds (sq.rs:67-89): folds the `count` elements of x into bounds_host, start.min(v) .. end.max(v)
+ * after widening to f64; NaN elements are skipped (f64::min / max).  A fresh quantiser starts at {DBL_MAX, -DBL_MAX}
+ * (sq.rs:43-55); folding a second array into the result is the same fold (retrain).  The sign of a zero bound is unspecified. */
+int lance_hip_sq_bounds(lance_hip_ctx *ctx, int dtype, const void *x, uint64_t count, double *bounds_host);
+/* scale_to_u8 (sq.rs:263-277): codes[n][d] = ((f64(v) - start) * 255.0 / (end - start)) as u8 -- truncated toward zero,
+ * saturated to 0..255, NaN -> 0; start == end: every code is 0.                                                      */
+int lance_hip_sq_encode(lance_hip_ctx *ctx, int dtype, const void *x, uint64_t n, uint32_t d, const double *bounds_host,
+                        uint8_t *codes);
+/* SQDistCalculator::distance_all (sq/storage.rs:398-468) for nq raw queries q[nq][d] (dtype elements, encoded with the same
+ * bounds) against codes[n][d]: dists[nq][n] = (dist0 * r * r) / 65025 in f32, r = (end - start) as f32, dist0 = the u32 sum of
+ * squared code differences as f32 (L2 and Cosine: l2_distance_uint_scalar, l2.rs:44-49) or 1 - the u32 sum of code products
+ * as f32 (Dot: dot.rs:152-161).  The query is taken as given (a cosine caller normalises it first).  Finite bounds; nq <= 65535. */
+int lance_hip_sq_distance(lance_hip_ctx *ctx, int dtype, int metric, const uint8_t *codes, uint64_t n, uint32_t d,
+                          const void *q, uint32_t nq, const double *bounds_host, float *dists);
+/* Per-partition ScalarQuantizationStorage on the device (sq/builder.rs, sq/storage.rs): codes[n][d] are gathered into partition
+ * order (stable; rows with part id LANCE_HIP_NONE dropped); row_ids NULL -> row index.  dtype is the element type of centroids
+ * and queries.  Cosine: the caller encoded NORMALISED rows and assigned them in L2, as for lance_hip_ivfflat_create.  The handle
+ * is destroyed with lance_hip_index_destroy; every IVF_PQ / IVF_FLAT entry point and lance_hip_index_save refuse it.            */
+int lance_hip_ivfsq_create(lance_hip_ctx *ctx, int dtype, int metric, uint32_t d, const void *centroids, uint32_t nlist,
+                           const uint8_t *codes, const uint32_t *part_ids, const uint64_t *row_ids, uint64_t n,
+                           const double *bounds_host, lance_hip_index **out);
+/* find_partitions + FlatIndex::search over every probed partition's SQ storage (flat/index.rs:82-177: a max-heap of k on the
+ * scaled f32 distance, rows in storage order) + SortExec(dist, rowid).fetch(k); k <= 128.  Queries whose answer depends on the
+ * heap's handling of ties are replayed through it (counted by lance_hip_search_stats).                                      */
+int lance_hip_ivfsq_search(lance_hip_ctx *ctx, const lance_hip_index *idx, const void *q, uint32_t nq, uint32_t k,
+                           uint32_t nprobes, uint64_t *ids, float *dists);
+/* The same under a row-id prefilter (flat/index.rs:129-165), tested inside the scan and the replay kernel. */
+int lance_hip_ivfsq_search_filtered(lance_hip_ctx *ctx, const lance_hip_index *idx, const void *q, uint32_t nq, uint32_t k,
+                                    uint32_t nprobes, const uint8_t *allow_by_rowid, uint64_t n_allow, uint64_t *ids, float *dists);
+
 /* ---- a22 / 8(f) N3: index files (lance/src/index/vector/builder.rs:938-1079 merge_partitions) ---------------------- */
 /* The `index.idx` + `auxiliary.idx` pair of an IVF_PQ / IVF_FLAT index directory, Lance file format 2.0 (the
  * FileWriter default, lance-file/src/writer.rs:553-561).  Host-side: nothing here needs a GPU except load/save, and every

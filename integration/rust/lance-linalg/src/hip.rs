@@ -97,6 +97,20 @@ extern "C" {
         ids: *mut u64, dists: *mut f32) -> i32;
     pub fn lance_hip_ivfflat_search_filtered(ctx: *mut LanceHipCtx, idx: *const LanceHipIndex, q: *const c_void, nq: u32, k: u32,
         nprobes: u32, allow_by_rowid: *const u8, n_allow: u64, ids: *mut u64, dists: *mut f32) -> i32;
+    // 8-bit scalar quantisation (sq.rs:43-89, 263-287) and the IVF_SQ sub-index (FlatIndex over ScalarQuantizationStorage,
+    // sq/storage.rs:398-468); bounds_host = Range<f64> as [start, end] in host memory
+    pub fn lance_hip_sq_bounds(ctx: *mut LanceHipCtx, dtype: i32, x: *const c_void, count: u64, bounds_host: *mut f64) -> i32;
+    pub fn lance_hip_sq_encode(ctx: *mut LanceHipCtx, dtype: i32, x: *const c_void, n: u64, d: u32, bounds_host: *const f64,
+        codes: *mut u8) -> i32;
+    pub fn lance_hip_sq_distance(ctx: *mut LanceHipCtx, dtype: i32, metric: i32, codes: *const u8, n: u64, d: u32, q: *const c_void,
+        nq: u32, bounds_host: *const f64, dists: *mut f32) -> i32;
+    pub fn lance_hip_ivfsq_create(ctx: *mut LanceHipCtx, dtype: i32, metric: i32, d: u32, centroids: *const c_void, nlist: u32,
+        codes: *const u8, part_ids: *const u32, row_ids: *const u64, n: u64, bounds_host: *const f64,
+        out: *mut *mut LanceHipIndex) -> i32;
+    pub fn lance_hip_ivfsq_search(ctx: *mut LanceHipCtx, idx: *const LanceHipIndex, q: *const c_void, nq: u32, k: u32, nprobes: u32,
+        ids: *mut u64, dists: *mut f32) -> i32;
+    pub fn lance_hip_ivfsq_search_filtered(ctx: *mut LanceHipCtx, idx: *const LanceHipIndex, q: *const c_void, nq: u32, k: u32,
+        nprobes: u32, allow_by_rowid: *const u8, n_allow: u64, ids: *mut u64, dists: *mut f32) -> i32;
     pub fn lance_hip_flat_topk(ctx: *mut LanceHipCtx, dtype: i32, metric: i32, x: *const c_void, row_ids: *const u64,
         n: u64, d: u32, q: *const c_void, nq: u32, k: u32, ids: *mut u64, dists: *mut f32) -> i32;
     /// multivec_distance (distance.rs:107-206) of one multivector query to every row of a List<FixedSizeList> column: `values` is the

@@ -71,6 +71,15 @@ struct lance_hip_index {
   uint8_t *raw_u8 = nullptr;
   uint64_t raw_gen = 0;           // bumped by every lance_hip_index_set_raw: captured search graphs are keyed on it (they hold raw / raw_u8 pointers)
   int raw_compact_state = 0;      // 0: not tried yet; 1: raw_u8 holds the column; -1: the column is not representable (or no memory for the copy)
+  // IVF_SQ (sq.hip; sq.rs, sq/storage.rs): `codes` holds the u8 codes [n][sq_ld] (rows zero-padded to sq_ld = d rounded up to 16, so
+  // a lane reads whole 16-byte words) followed, in the same allocation, by the per-row sums of squared codes sq_xx [n].
+  // An SQ handle keeps m = 0, vectors = NULL and the generic nlist = 0 (its own count is sq_nlist): lance_hip_ivfflat_search refuses
+  // a handle without vectors and every IVF_PQ search clamps nprobes to nlist and refuses 0 probes -- both before they read anything
+  // else, so neither can misread an SQ handle.  lance_hip_index_save refuses by the flag.
+  bool sq = false;
+  double sq_lo = 0.0, sq_hi = 0.0;   // the quantiser's bounds (ScalarQuantizer::bounds)
+  uint32_t sq_nlist = 0, sq_ld = 0;
+  const uint32_t *sq_xx = nullptr;   // alias into `codes`
   uint32_t max_part = 0;
   uint32_t code_bytes() const { return nbits == 4 ? m / 2 : m; }   // bytes of PQ code per row
   ~lance_hip_index();

@@ -117,6 +117,16 @@ def check_multivector(values, offsets, q, metric, k=None):
 
 _DT = {"float32": (torch.float32, 0), "float16": (torch.float16, 1), "int8": (torch.int8, 2)}
 
+SQ_FRESH_BOUNDS = (float(np.finfo(np.float64).max), float(np.finfo(np.float64).min))     # ScalarQuantizer::new (sq.rs:43-55)
+
+
+def _sq_column(a):
+    """a column or query batch for the scalar quantiser -> (cuda tensor, dtype code); float32 and float16 only"""
+    name = _dtype_name(a)
+    if name not in ("float32", "float16"):
+        raise ValueError(f"SQ builder: unsupported data type: {name} (float16 and float32 columns are supported)")
+    return _vec(a)
+
 
 def _on_engine_device(fn):
     """Every tensor a method allocates or moves must live on the GPU the context was created on (two Engines in one process
@@ -450,6 +460,41 @@ class Engine:
                                                     qd.shape[0], k, _ptr(ids), _ptr(dists)))
         return ids, dists
 
+    # ---- 8-bit scalar quantisation (lance-index/src/vector/sq.rs) -------------------------
+    def sq_bounds(self, x, bounds=None):
+        """ScalarQuantizer::update_bounds: folds the elements of x (float32 / float16) into `bounds` = (start, end) -- None: a fresh
+        quantiser's (f64::MAX, f64::MIN) -- skipping NaN.  -> (start, end) as Python floats"""
+        x, dt = _sq_column(x)
+        b = (C.c_double * 2)(*(SQ_FRESH_BOUNDS if bounds is None else (float(bounds[0]), float(bounds[1]))))
+        torch.cuda.synchronize()
+        check(self.lib.lance_hip_sq_bounds(self.h, dt, _ptr(x), x.numel(), b))
+        return float(b[0]), float(b[1])
+
+    def sq_encode(self, x, bounds):
+        """scale_to_u8: x [n][d] -> uint8 codes [n][d] under bounds = (start, end)"""
+        x, dt = _sq_column(x)
+        if x.dim() != 2:
+            raise ValueError(f"x must be [n][d], got shape {tuple(x.shape)}")
+        n, d = x.shape
+        codes = torch.empty((n, d), dtype=torch.uint8, device=x.device)
+        b = (C.c_double * 2)(float(bounds[0]), float(bounds[1]))
+        torch.cuda.synchronize()
+        check(self.lib.lance_hip_sq_encode(self.h, dt, _ptr(x), n, d, b, _ptr(codes)))
+        return codes
+
+    def sq_distance(self, codes, q, bounds, metric="l2"):
+        """SQDistCalculator::distance_all for every query: codes [n][d] uint8, raw queries q [nq][d] (float32 / float16, encoded
+        with the same bounds) -> [nq][n] float32"""
+        q, dt = _sq_column(q)
+        codes = to_device(codes, torch.uint8)
+        n, d = codes.shape
+        q = q.reshape(-1, d)
+        dists = torch.empty((q.shape[0], n), dtype=torch.float32, device=codes.device)
+        b = (C.c_double * 2)(float(bounds[0]), float(bounds[1]))
+        torch.cuda.synchronize()
+        check(self.lib.lance_hip_sq_distance(self.h, dt, METRICS[metric], _ptr(codes), n, d, _ptr(q), q.shape[0], b, _ptr(dists)))
+        return dists
+
     def search_stats(self):
         """queries of the last search replayed by the exact (heap-emulating) kernel"""
         n = C.c_uint32(0)
@@ -564,6 +609,68 @@ class DeviceFlatIndex:
             return ids, dists
         torch.cuda.synchronize()
         check(self.engine.lib.lance_hip_ivfflat_search(self.engine.h, self.h, _ptr(q), nq, k, nprobes, _ptr(ids), _ptr(dists)))
+        return ids, dists
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.engine.lib.lance_hip_index_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+
+class DeviceSqIndex:
+    """Handle of a device-resident IVF_SQ index (FlatIndex sub-index over the 8-bit scalar-quantised codes of each partition)."""
+
+    def __init__(self, engine, handle, metric, centroids, data_dtype, bounds):
+        self.engine = engine
+        self.h = handle
+        self.metric = metric
+        self.centroids = centroids
+        self.data_dtype = data_dtype
+        self.bounds = bounds
+
+    @classmethod
+    def create(cls, engine, metric, centroids, codes, part_ids, bounds, row_ids=None):
+        """centroids: float32 / float16 (the element type of the column and of the queries); codes [n][d] uint8 (Engine.sq_encode of
+        the rows -- the NORMALISED rows for cosine); part_ids [n] (NONE = dropped)"""
+        cent, dt = _sq_column(centroids)
+        codes = to_device(codes, torch.uint8)
+        part = to_device(part_ids, torch.int32)
+        rid = None if row_ids is None else to_device(row_ids, torch.int64)
+        n, d = codes.shape
+        b = (C.c_double * 2)(float(bounds[0]), float(bounds[1]))
+        h = C.c_void_p()
+        torch.cuda.synchronize()
+        check(engine.lib.lance_hip_ivfsq_create(engine.h, dt, METRICS[metric], d, _ptr(cent), cent.shape[0], _ptr(codes), _ptr(part),
+                                                _ptr(rid), n, b, C.byref(h)))
+        return cls(engine, h, metric, cent, cent.dtype, (float(bounds[0]), float(bounds[1])))
+
+    def save(self, index_dir, loss=None):
+        raise NotImplementedError("IVF_SQ index files are not supported (IVF_PQ and IVF_FLAT are)")
+
+    def search(self, q, k, nprobes, allow=None):
+        """allow: boolean array indexed by row id (a prefilter), tested inside the scan kernels (lance_hip_ivfsq_search_filtered)"""
+        d = self.centroids.shape[1]
+        t = q if isinstance(q, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(q))
+        q = t.to(self.data_dtype).to(_dev()).contiguous().reshape(-1, d)
+        nq = q.shape[0]
+        ids = torch.empty((nq, k), dtype=torch.int64, device=q.device)
+        dists = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+        if allow is not None:
+            a = allow if isinstance(allow, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(allow, dtype=bool))
+            a = a.to(torch.uint8).to(_dev()).contiguous()
+            torch.cuda.synchronize()
+            check(self.engine.lib.lance_hip_ivfsq_search_filtered(self.engine.h, self.h, _ptr(q), nq, k, nprobes, _ptr(a), a.numel(),
+                                                                  _ptr(ids), _ptr(dists)))
+            return ids, dists
+        torch.cuda.synchronize()
+        check(self.engine.lib.lance_hip_ivfsq_search(self.engine.h, self.h, _ptr(q), nq, k, nprobes, _ptr(ids), _ptr(dists)))
         return ids, dists
 
     def close(self):
@@ -814,4 +921,5 @@ class DeviceIndex:
 
 
 _wrap_methods(DeviceFlatIndex, skip=("close",))
+_wrap_methods(DeviceSqIndex, skip=("close", "save"))
 _wrap_methods(DeviceIndex, skip=("close",))

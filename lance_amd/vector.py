@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from ._lib import METRICS, NONE
-from .engine import DeviceFlatIndex, DeviceIndex, Engine, check_multivector, to_device
+from .engine import DeviceFlatIndex, DeviceIndex, DeviceSqIndex, Engine, _dtype_name, check_multivector, to_device
 
 _engine = None
 
@@ -326,6 +326,73 @@ class IvfFlatIndex:
         self._ix.save(index_dir, None if self.stats is None else self.stats.ivf_loss)
 
 
+class IvfSqIndex:
+    """IVF_SQ: IVF partitions over 8-bit scalar-quantised codes (lance-index/src/vector/sq.rs, sq/storage.rs): IVF_FLAT's search
+    over a quarter of its bytes, distances computed between codes."""
+
+    def __init__(self, ix, params, stats, part_ids, codes=None):
+        self._ix = ix
+        self.params = params
+        self.stats = stats
+        self.part_ids = part_ids
+        self._codes = codes
+
+    @property
+    def centroids(self):
+        return self._ix.centroids.cpu().numpy()
+
+    @property
+    def bounds(self):
+        """the quantiser's Range<f64> as (start, end)"""
+        return self._ix.bounds
+
+    def search_device(self, q, k, nprobes):
+        return self._ix.search(q, k, nprobes)
+
+    def nearest(self, q, k=10, nprobes=1, prefilter=None, refine_factor=None, distance_range=None):
+        """prefilter: boolean array over row ids; the mask is tested inside the scan kernels (no copy of the index)"""
+        if refine_factor is not None:
+            raise NotImplementedError("IVF_SQ: refine_factor (re-ranking on the raw vectors) is not supported by this engine")
+        if distance_range is not None:
+            raise NotImplementedError("IVF_SQ: distance_range is not supported by this engine")
+        ids, dists = self._ix.search(q, k, nprobes) if prefilter is None else self._ix.search(q, k, nprobes, allow=prefilter)
+        return ids.cpu().numpy().view(np.uint64), dists.cpu().numpy()
+
+    def prefiltered(self, allow):
+        """A compacted copy of the index restricted to the selected rows (for callers that reuse one filter for many batches;
+        `nearest(prefilter=)` does not need it).  The selected rows keep their codes and their storage order, so the copy answers
+        exactly as the prefilter branch of FlatIndex::search does (flat/index.rs:129-165)."""
+        if self.part_ids is None or self._codes is None:
+            raise NotImplementedError("prefilter needs the index's codes and partition ids (an index built by create_index with keep_raw)")
+        part = self.part_ids
+        allow_t = to_device(np.ascontiguousarray(allow, dtype=bool)) if not isinstance(allow, torch.Tensor) else allow.to(part.device)
+        ids = torch.arange(part.numel(), device=part.device)
+        inside = ids < allow_t.numel()
+        sel = torch.zeros_like(inside)
+        sel[inside] = allow_t[ids[inside]]
+        masked = torch.where(sel, part, torch.full_like(part, -1))
+        sub = DeviceSqIndex.create(self._ix.engine, self._ix.metric, self._ix.centroids, self._codes, masked, self._ix.bounds)
+        return IvfSqIndex(sub, self.params, self.stats, masked, self._codes)
+
+    def save(self, index_dir):
+        raise NotImplementedError("IVF_SQ index files are not supported (IVF_PQ and IVF_FLAT are)")
+
+
+def train_sq_bounds(x, params: IvfPqParams, engine=None):
+    """load_or_build_quantizer for the scalar quantiser (rust/lance/src/index/vector/builder.rs:399-466, sq.rs:152-180): sample
+    sample_rate * 2^num_bits rows, normalise (cosine), drop non-finite rows, fold the rest into fresh bounds.  There is no residual
+    step (ScalarQuantizer::use_residual is false).  -> (start, end)"""
+    eng = engine or default_engine()
+    metric = _normalize_metric_type(params.metric)
+    x = to_device(x)
+    idx = pq_sample_indices(x.shape[0], params)
+    sample = x if idx is None else x[torch.from_numpy(idx).to(x.device)]
+    if metric == "cosine":
+        sample = eng.normalize(sample)
+    sample = sample[torch.isfinite(sample).all(dim=1)]
+    return eng.sq_bounds(sample)
+
+
 def load_index(index_dir, dtype=None, raw=None, engine=None):
     """Opens an index directory (`index.idx` + `auxiliary.idx`, written by the reference or by `save`) straight into
     HBM -> IvfPqIndex | IvfFlatIndex.  dtype: element type of the indexed column when it differs from the stored model
@@ -435,8 +502,14 @@ def create_index(x, index_type="IVF_PQ", metric="l2", num_partitions=256, num_su
         raise ValueError(f"Metric {metric} not supported.")
     metric_n = _normalize_metric_type(metric)
     itype = str(index_type).upper()
-    if itype not in ("IVF_PQ", "IVF_FLAT"):
-        raise NotImplementedError(f"index_type {index_type}: IVF_PQ and IVF_FLAT are on this engine's hot path")
+    if itype not in ("IVF_PQ", "IVF_FLAT", "IVF_SQ"):
+        raise NotImplementedError(f"index_type {index_type}: IVF_PQ, IVF_FLAT and IVF_SQ are on this engine's hot path")
+    if itype == "IVF_SQ":
+        # ScalarQuantizer (lance-index/src/vector/sq.rs): 8 bits only (`// TODO: support SQ4`), float columns only
+        if num_bits != 8:
+            raise ValueError(f"ScalarQuantization: num_bits {num_bits} not supported (only 8 is)")
+        if _dtype_name(x) not in ("float32", "float16"):
+            raise NotImplementedError(f"SQ builder: unsupported data type: {_dtype_name(x)} (float16 and float32 columns are supported)")
     if isinstance(num_partitions, float):
         import warnings
         warnings.warn("num_partitions is float, converting to int")
@@ -516,6 +589,21 @@ def create_index(x, index_type="IVF_PQ", metric="l2", num_partitions=256, num_su
         out = IvfFlatIndex(fx, params, stats, part)
         out._x = xs if keep_raw else None     # the stored rows (borrowed): needed to re-partition under a prefilter
         return out
+    if itype == "IVF_SQ":
+        # the transform chain of IVF_FLAT (normalise for cosine, assign in L2 / under dot) followed by SQTransformer; the
+        # quantiser trains on its own sample of the column (train_sq_bounds)
+        bounds = timed("train_sq", lambda: train_sq_bounds(x, params, eng))
+
+        def transform():
+            xs = eng.normalize(x) if params.metric == "cosine" else x
+            part, _ = eng.assign(xs, cent, "l2" if params.metric == "cosine" else params.metric)
+            # KeepFiniteVectors runs ahead of the partition transform (ivf.rs new_ivf_transformer_with_quantizer): a row with a
+            # NaN or an infinity has no partition under any metric
+            part = torch.where(torch.isfinite(xs).all(dim=1), part, torch.full_like(part, -1))
+            return part, eng.sq_encode(xs, bounds)
+        part, codes = timed("transform", transform)
+        sx = timed("build_partitions", lambda: DeviceSqIndex.create(eng, params.metric, cent.to(x.dtype), codes, part, bounds))
+        return IvfSqIndex(sx, params, stats, part, codes if keep_raw else None)
     if num_bits not in (4, 8):
         raise ValueError(f"ProductQuantization: num_bits {num_bits} not supported")
     if pq_codebook is not None:

@@ -1,0 +1,97 @@
+// Runs the device code of lance_amd/csrc/sq.hip on the CPU (simt_emu.h) under AddressSanitizer + UBSan: every buffer has exactly the
+// size the library gives it, so a read past a row or a write past a list is an error here.  sq_device_code.inc is cut out of the
+// sources by tests/test_sq_kernels_cpu.py, which also writes the problem file and compares the outputs with tests/sq_spec.py.
+#include "simt_emu.h"
+
+namespace lh {
+#include "sq_device_code.inc"
+}
+using namespace lh;
+
+template <typename T>
+static std::vector<T> rd(FILE *f, size_t n) {
+  std::vector<T> v(n);
+  if (n && fread(v.data(), sizeof(T), n, f) != n) { puts("short read"); exit(2); }
+  return v;
+}
+template <typename T>
+static void wr(FILE *f, const T *p, size_t n) { if (n && fwrite(p, sizeof(T), n, f) != n) { puts("short write"); exit(2); } }
+static uint8_t *aligned_copy(const uint8_t *src, size_t bytes) {      // 16-byte aligned, NOT padded beyond a multiple of 16
+  uint8_t *p = static_cast<uint8_t *>(aligned_alloc(16, std::max<size_t>(16, (bytes + 15) & ~(size_t)15)));
+  if (src) memcpy(p, src, bytes); else memset(p, 0, bytes);
+  return p;
+}
+
+// in: u32 n, d, nlist, nq, nprobes, k, dot, has_allow | f64 lo, hi | f32 x[n][d] | f32 q[nq][d] (the rows / keys AS STORED: normalised
+// for cosine) | u32 part[n] (the stable grouping is the caller's: perm follows) | u32 n_kept, perm[n_kept], offs[nlist + 1] |
+// u64 row_ids[n] | u32 probes[nq][nprobes] | u32 allow_bits[n_kept / 32 + 4] (if has_allow)
+int main(int argc, char **argv) {
+  if (argc < 3) return 2;
+  FILE *f = fopen(argv[1], "rb");
+  if (!f) return 2;
+  const auto h = rd<uint32_t>(f, 8);
+  const uint32_t n = h[0], d = h[1], nlist = h[2], nq = h[3], nprobes = h[4], k = h[5], dot = h[6], has_allow = h[7];
+  const auto b = rd<double>(f, 2);
+  const auto x = rd<float>(f, (size_t)n * d);
+  const auto q = rd<float>(f, (size_t)nq * d);
+  const auto nk = rd<uint32_t>(f, 1);
+  const uint32_t n_kept = nk[0];
+  const auto perm = rd<uint32_t>(f, n_kept);
+  const auto offs = rd<uint32_t>(f, nlist + 1);
+  const auto row_ids = rd<uint64_t>(f, n);
+  const auto probes = rd<uint32_t>(f, (size_t)nq * nprobes);
+  const auto allow = rd<uint32_t>(f, has_allow ? n_kept / 32 + 4 : 0);
+  fclose(f);
+  const double lo = b[0], hi = b[1];
+  const uint32_t ld = (d + 15u) & ~15u;
+  const float r = (float)(hi - lo), r2 = r * r;
+
+  // bounds of the column, folded on the host as lance_hip_sq_bounds does
+  std::vector<double> partials(2 * 3);
+  simt_launch(3, 1, 256, [&] { sq_bounds_kernel<float>(x.data(), (int64_t)n * d, partials.data()); });
+  double fold[2] = {1.7976931348623157e308, -1.7976931348623157e308};
+  for (int i = 0; i < 3; ++i) { fold[0] = std::min(fold[0], partials[2 * i]); fold[1] = std::max(fold[1], partials[2 * i + 1]); }
+  // encode rows (tight) and keys (padded)
+  std::vector<uint8_t> codes((size_t)n * d, 77);
+  simt_launch(3, 1, 256, [&] { sq_encode_kernel<float>(x.data(), (int64_t)n * d, (int)d, (int64_t)d, lo, hi - lo, lo == hi, codes.data()); });
+  uint8_t *qc = aligned_copy(nullptr, (size_t)nq * ld);
+  simt_launch(2, 1, 256, [&] { sq_encode_kernel<float>(q.data(), (int64_t)nq * d, (int)d, (int64_t)ld, lo, hi - lo, lo == hi, qc); });
+  std::vector<uint32_t> qq(nq);
+  simt_launch((nq + 255) / 256, 1, 256, [&] { sq_norms_kernel(qc, (int64_t)nq, (int)ld, qq.data()); });
+  // distance_all, both row readers
+  std::vector<float> dist_words((size_t)nq * n), dist_wide((size_t)nq * n, -1.0f);
+  simt_launch((n + 255) / 256, nq, 256, [&] { sq_distance_kernel<false>(codes.data(), (int64_t)n, (int)d, qc, (int)ld, (int)dot, r2, dist_words.data()); });
+  uint8_t *codes_al = aligned_copy(codes.data(), codes.size());
+  if (d % 16 == 0)
+    simt_launch((n + 255) / 256, nq, 256, [&] { sq_distance_kernel<true>(codes_al, (int64_t)n, (int)d, qc, (int)ld, (int)dot, r2, dist_wide.data()); });
+  // the index: gather + norms
+  uint8_t *stored = aligned_copy(nullptr, (size_t)n_kept * ld);
+  std::vector<uint64_t> rid(n_kept);
+  std::vector<uint32_t> xx(n_kept);
+  if (n_kept) {
+    simt_launch(((size_t)n_kept * ld + 255) / 256, 1, 256, [&] { sq_gather_kernel(codes.data(), row_ids.data(), perm.data(), (int64_t)n_kept, (int)d, (int)ld, stored, rid.data()); });
+    simt_launch((n_kept + 255) / 256, 1, 256, [&] { sq_norms_kernel(stored, (int64_t)n_kept, (int)ld, xx.data()); });
+  }
+  // search: scan, merge, replay
+  const size_t pairs = (size_t)nq * nprobes;
+  std::vector<uint32_t> pkey(pairs * k), ppos(pairs * k), pcnt(pairs), pamb(pairs), flags(nq + 1, 0);
+  std::vector<uint64_t> ids((size_t)nq * k);
+  std::vector<float> dists((size_t)nq * k);
+  SqArgs a;
+  a.codes = stored; a.xx = xx.data(); a.row_ids = rid.data(); a.part_offsets = offs.data(); a.probes = probes.data(); a.qcodes = qc; a.qq = qq.data();
+  a.ld = (int)ld; a.nprobes = (int)nprobes; a.k = (int)k; a.dot = (int)dot; a.r2 = r2; a.allow = has_allow ? allow.data() : nullptr;
+  a.pkey = pkey.data(); a.ppos = ppos.data(); a.pcnt = pcnt.data(); a.pamb = pamb.data(); a.flags = flags.data(); a.n_replay = flags.data() + nq;
+  simt_launch(nq * nprobes, 1, 256, [&] { sq_scan_kernel(a); });
+  simt_launch(nq, 1, 256, [&] { sq_merge_kernel(a, ids.data(), dists.data()); });
+  const std::vector<uint64_t> fast_ids = ids;
+  simt_launch(nq, 1, 64, [&] { sq_exact_kernel(a, ids.data(), dists.data()); });
+
+  FILE *o = fopen(argv[2], "wb");
+  if (!o) return 2;
+  wr(o, fold, 2); wr(o, codes.data(), codes.size()); wr(o, dist_words.data(), dist_words.size()); wr(o, dist_wide.data(), dist_wide.size());
+  wr(o, ids.data(), ids.size()); wr(o, dists.data(), dists.size()); wr(o, flags.data(), flags.size()); wr(o, fast_ids.data(), fast_ids.size());
+  fclose(o);
+  free(qc); free(codes_al); free(stored);
+  puts("ok");
+  return 0;
+}

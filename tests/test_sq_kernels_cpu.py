@@ -1,0 +1,154 @@
+"""The DEVICE code of lance_amd/csrc/sq.hip run on the CPU, lane by lane (tests/c/simt_emu: a thread per lane, a barrier for
+__syncthreads), under AddressSanitizer + UBSan, against tests/sq_spec.py bit for bit: bounds, codes, distances through both row
+readers, and the search -- per-pair selection, merge, the replay decision and the heap replay.  The kernels' text is cut out of the
+sources at test time, so what runs here is what the GPU compiles, minus the packed dot instruction (its portable definition in
+sq.hip stands in).  This checks the logic and the memory safety of the kernels without a device; the arithmetic of the device's own
+instructions is what tests/test_zz_gpu_sq.py checks."""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import sq_spec as S
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "lance_amd", "csrc")
+EMU = os.path.join(ROOT, "tests", "c", "simt_emu")
+f32 = np.float32
+
+
+def function_text(src, name):
+    """the definition of the __device__ function `name` (with its template line, if any), found by name and brace matching"""
+    m = re.search(r"^(template <[^\n]*>\n)?__device__ [^\n;{]*\b" + re.escape(name) + r"\(", src, flags=re.M)
+    assert m, name
+    depth, i = 0, src.index("{", m.end())
+    while True:
+        depth += {"{": 1, "}": -1}.get(src[i], 0)
+        i += 1
+        if depth == 0:
+            return src[m.start():i] + "\n"
+
+
+def device_code():
+    read = lambda name: open(os.path.join(CSRC, name)).read()
+    exact, common, sq = read("exact.cuh"), read("search_common.cuh"), read("sq.hip")
+    parts = [function_text(exact, n) for n in ("order_key", "key_to_float")]
+    parts += [function_text(common, n) for n in ("row_allowed", "bitonic_sort_kr", "heap_sift_up", "heap_push", "heap_pop")]
+    body = sq[sq.index("constexpr uint32_t SQ_MAX_DIM"):sq.index("// ---- host side")]
+    body = body.replace("LANCE_HIP_SQ_MAX_DIM", "16384").replace("extern __shared__ __attribute__((aligned(16))) char smem[];", "")
+    assert "__global__" in body and "smem" in body
+    return "".join(parts) + body
+
+
+@pytest.fixture(scope="module")
+def emulator(tmp_path_factory):
+    work = tmp_path_factory.mktemp("sq_emu")
+    (work / "sq_device_code.inc").write_text(device_code())
+    exe = str(work / "sq_kernels")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-pthread",
+           "-I", str(work), "-I", EMU, os.path.join(EMU, "sq_kernels_main.cpp"), "-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    if r.returncode != 0 and "sanitize" in r.stderr:
+        pytest.skip("g++ without sanitizer runtimes")
+    assert r.returncode == 0, r.stderr[-3000:]
+    return exe, work
+
+
+def run_case(emulator, oracle, x, q, cent, metric, k, nprobes, bounds, row_ids, prefilter=None):
+    exe, work = emulator
+    xs, part = S.prepare_rows(oracle, x, cent, metric)
+    qs = oracle.normalize(q) if metric == "cosine" else q
+    xs32, qs32 = np.ascontiguousarray(xs, f32), np.ascontiguousarray(qs, f32)
+    n, d = xs32.shape
+    nq, nlist = qs32.shape[0], cent.shape[0]
+    nprobes = min(nprobes, nlist)
+    offs, perm = oracle.partition_layout(part, nlist)
+    probes, _ = oracle.find_partitions(qs, cent, nprobes, "l2" if metric == "cosine" else metric)
+    bits = np.zeros(len(perm) // 32 + 4, np.uint32)
+    if prefilter is not None:
+        stored = row_ids[perm]
+        ok = stored < prefilter.size
+        ok[ok] = prefilter[stored[ok]]
+        for i in np.nonzero(ok)[0]:
+            bits[i >> 5] |= np.uint32(1 << (i & 31))
+    inp, outp = str(work / "in.bin"), str(work / "out.bin")
+    with open(inp, "wb") as fh:
+        np.array([n, d, nlist, nq, nprobes, k, int(metric == "dot"), int(prefilter is not None)], np.uint32).tofile(fh)
+        np.array(bounds, np.float64).tofile(fh)
+        xs32.tofile(fh); qs32.tofile(fh)
+        np.array([len(perm)], np.uint32).tofile(fh); perm.astype(np.uint32).tofile(fh); offs.astype(np.uint32).tofile(fh)
+        row_ids.astype(np.uint64).tofile(fh); probes.astype(np.uint32).tofile(fh)
+        if prefilter is not None:
+            bits.tofile(fh)
+    r = subprocess.run([exe, inp, outp], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout[-1000:] + r.stderr[-4000:]
+    raw = np.fromfile(outp, np.uint8)
+    pos = 0
+
+    def take(count, dt):
+        nonlocal pos
+        a = raw[pos:pos + count * np.dtype(dt).itemsize].view(dt)
+        pos += count * np.dtype(dt).itemsize
+        return a
+    fold = take(2, np.float64)
+    codes = take(n * d, np.uint8).reshape(n, d)
+    dist_words, dist_wide = take(nq * n, f32).reshape(nq, n), take(nq * n, f32).reshape(nq, n)
+    ids, dists = take(nq * k, np.uint64).reshape(nq, k), take(nq * k, f32).reshape(nq, k)
+    flags = take(nq + 1, np.uint32)
+    fast_ids = take(nq * k, np.uint64).reshape(nq, k)
+    assert pos == raw.size
+    # bounds, codes, distances
+    assert tuple(fold) == S.bounds(xs32)
+    want_codes = S.encode(xs32, *bounds)
+    assert (codes == want_codes).all()
+    want_d = S.distances(want_codes, qs32, metric, *bounds)
+    assert (dist_words.view(np.uint32) == want_d.view(np.uint32)).all()
+    assert d % 16 != 0 or (dist_wide.view(np.uint32) == want_d.view(np.uint32)).all()
+    # the search: the final answer, and the fast path's answer for every query it did not hand to the replay
+    oi, od = S.search(oracle, want_codes, part, cent, q, k, nprobes, metric, *bounds, row_ids=row_ids, prefilter=prefilter)
+    assert (ids == oi).all() and (dists.view(np.uint32) == od.view(np.uint32)).all()
+    kept = flags[:nq] == 0
+    assert (fast_ids[kept] == oi[kept]).all()
+    assert flags[nq] == (~kept).sum()
+    return int(flags[nq])
+
+
+def test_device_code_is_found():
+    code = device_code()
+    for name in ("sq_bounds_kernel", "sq_encode_kernel", "sq_distance_kernel", "sq_scan_kernel", "sq_merge_kernel", "sq_exact_kernel",
+                 "sq_gather_kernel", "sq_norms_kernel", "heap_pop", "bitonic_sort_kr", "order_key"):
+        assert name in code, name
+    assert "hipLaunchKernelGGL" not in code and "LH_REQUIRE" not in code, "host code must stay out"
+
+
+def test_ties_are_replayed(emulator, oracle):
+    x, q, rid = S.tie_fixture(n=900, nq=4)
+    cent = S.centroids_with_gaps(x, 4, seed=3)
+    b = S.bounds(x)
+    assert run_case(emulator, oracle, x, q, cent, "l2", 10, 3, b, rid) > 0
+    assert run_case(emulator, oracle, x, q, cent, "l2", 128, 4, b, rid, prefilter=np.arange(int(rid.max()) + 1) % 3 != 0) > 0
+
+
+@pytest.mark.parametrize("metric,kind,d,k,nprobes", [("l2", "f32", 20, 10, 3), ("dot", "f16", 32, 128, 8), ("cosine", "f32", 16, 1, 1)])
+def test_gaussian_rows(emulator, oracle, metric, kind, d, k, nprobes):
+    x, q = S.gaussian(700, d, 3, seed=5, kind=kind)
+    x[650, 2] = np.nan                                    # a row without a partition
+    rid = S.permuted_ids(700, 2)
+    cent = S.centroids_with_gaps(oracle.normalize(x[:600]) if metric == "cosine" else x[:600], 8, seed=1)
+    xs, _ = S.prepare_rows(oracle, x, cent, metric)
+    b = S.bounds(np.asarray(xs, f32)[100:164])            # a sample's bounds: later rows saturate
+    assert run_case(emulator, oracle, x, q, cent, metric, k, nprobes, b, rid) < 3
+    half = np.zeros(int(rid.max()) + 1, bool)
+    half[rid[::2]] = True
+    run_case(emulator, oracle, x, q, cent, metric, k, 8, b, rid, prefilter=half)
+    run_case(emulator, oracle, x, q, cent, metric, k, 8, b, rid, prefilter=np.zeros(5, bool))
+
+
+def test_constant_column(emulator, oracle):
+    x = np.full((300, 5), 1.25, f32)
+    cent = np.ascontiguousarray(np.stack([x[0], x[0] + 1, x[0] - 1]))
+    rid = S.permuted_ids(300, 4)
+    assert run_case(emulator, oracle, x, x[:2], cent, "l2", 10, 3, (0.0, 2.0), rid) == 2
+    assert run_case(emulator, oracle, x, x[:2], cent, "l2", 128, 1, (1.25, 1.25), rid) == 2      # start == end
