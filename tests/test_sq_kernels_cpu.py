@@ -146,6 +146,25 @@ def test_gaussian_rows(emulator, oracle, metric, kind, d, k, nprobes):
     run_case(emulator, oracle, x, q, cent, metric, k, 8, b, rid, prefilter=np.zeros(5, bool))
 
 
+def test_row_addresses(emulator, oracle):
+    """Row ids as a table of several fragments has them (tests/rowid_fixtures.py: fragment << 32 | offset, up to fragment 2^31 - 1, low
+    words that repeat across fragments and order the other way round): the merge and the heap replay compare and carry all 64 bits,
+    and a prefilter mask far shorter than every id selects nothing."""
+    import rowid_fixtures as R
+    x, q, _ = S.tie_fixture(n=450, nq=2)               # (half the rows and queries of the cases above: each run starts a thread per lane)
+    rid = R.row_addresses(450, 21)
+    cent = S.centroids_with_gaps(x, 4, seed=3)
+    b = S.bounds(x)
+    assert run_case(emulator, oracle, x, q, cent, "l2", 10, 3, b, rid) > 0
+    run_case(emulator, oracle, x, q, cent, "l2", 10, 3, b, rid, prefilter=np.ones(1000, bool))
+    x, q = S.gaussian(350, 20, 2, seed=5)
+    rid = R.row_addresses(350, 22)
+    cent = S.centroids_with_gaps(x[:300], 8, seed=1)
+    b = S.bounds(x[100:164])
+    assert run_case(emulator, oracle, x, q, cent, "l2", 10, 3, b, rid) < 2
+    run_case(emulator, oracle, x, q, cent, "l2", 128, 8, b, rid, prefilter=np.ones(1000, bool))
+
+
 def test_constant_column(emulator, oracle):
     x = np.full((300, 5), 1.25, f32)
     cent = np.ascontiguousarray(np.stack([x[0], x[0] + 1, x[0] - 1]))
