@@ -180,8 +180,10 @@ int lance_hip_kmeans_shard_end(lance_hip_ctx *ctx, const void *state, double *lo
  * context's stream; the host reads the state every 8 iterations.  `centroids` holds the initial centroids (identical on every
  * rank: e.g. rank 0's kmeans_random_init rows, broadcast by the host) and receives the trained ones (identical on every rank).
  * comm == NULL: single process, no collective.  balance_factor is the unscaled parameter (divided by n_total as train_kmeans does).
- * Sums arrive in rank order rather than row order: against the single-GPU trainer the centroids agree to f32 round-off for more
- * than one rank and bit for bit for one.  An RCCL the process already maps answers; otherwise librccl.so.1 is loaded on first use.
+ * Each rank adds its rows in row order and the partials arrive in rank order: against the single-GPU trainer the centroids are bit for
+ * bit the same on one rank and wherever the sums are exact (integer-valued rows), and differ by f32 summation order otherwise; among
+ * clusters that tie for largest the update takes the smallest id (the reference: the one whose last member comes first), which shows
+ * only when such a tie happens while the adjusted balance factor binds.  An RCCL the process already maps answers; otherwise librccl.so.1 is loaded on first use.
  * Whatever can fail on one rank only (its row count, scratch, the f32 copy of an f16 / int8 shard, its first E-step) is exchanged as one
  * status word before the first all-reduce of the loop: every rank returns.                                                          */
 typedef struct lance_hip_comm lance_hip_comm;

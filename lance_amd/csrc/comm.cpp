@@ -192,7 +192,7 @@ int lance_hip_kmeans_train_sharded_x(lance_hip_ctx *ctx, lance_hip_comm *comm, i
     if (!state || !bias || !buf || !losses || !radius) pre = LANCE_HIP_ENOMEM;
   }
   // f16 / int8 shards: widened once, here (exact; the flat sharded loop accumulates in f32 -- the M-step of an f16 column on ONE GPU
-  // rounds like half::f16, one more reason the two agree to round-off only)
+  // rounds like half::f16: for an f16 column the two models differ by that rounding)
   if (pre == LANCE_HIP_OK) pre = lh::as_f32(ctx, dtype, x_local, (size_t)n_local * d, "shard.x", &xf);
   if (pre == LANCE_HIP_OK) pre = lance_hip_kmeans_shard_begin(ctx, k, bf_scaled, seed, state, bias);
   double loss = 0.0;

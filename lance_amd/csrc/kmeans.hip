@@ -490,7 +490,9 @@ int kmeans_train_batched(lance_hip_ctx *ctx, int metric, const float *x, int64_t
   return LANCE_HIP_OK;
 }
 
-__global__ __launch_bounds__(256) void counts_to_float_kernel(const uint32_t *__restrict__ starts, int k, float *__restrict__ out) {
+__global__ __launch_bounds__(256) void counts_to_float_kernel(const uint32_t *__restrict__ starts, int k, float *__restrict__ out,
+                                                              const uint8_t *__restrict__ active) {
+  if (active && !active[0]) return;
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c < k) out[c] = (float)(starts[c + 1] - starts[c]);
 }
@@ -773,7 +775,7 @@ int lance_hip_kmeans_estep_partial(lance_hip_ctx *ctx, int dtype, int metric, co
                                    const void *centroids, uint32_t k, const float *bias, float *buf, double *losses,
                                    float *radius, double *loss_out_host) {
   lh::CtxLock _ctx_lock(ctx);
-  LH_REQUIRE(ctx && x && centroids && buf, "kmeans_estep_partial: NULL argument");
+  LH_REQUIRE(ctx && centroids && buf && (n == 0 || x), "kmeans_estep_partial: NULL argument");
   LH_REQUIRE(dtype == LANCE_HIP_F32, "kmeans_estep_partial: only f32 is implemented in this version");
   LH_REQUIRE(n < (1ull << 32) && k <= 4096, "kmeans_estep_partial: n or k too large for this version");
   LH_CHECK_HIP(hipSetDevice(ctx->device));
@@ -791,14 +793,15 @@ int lance_hip_kmeans_estep_partial(lance_hip_ctx *ctx, int dtype, int metric, co
   pa.x = static_cast<const float *>(x); pa.n = (int64_t)n; pa.ldx = d;
   pa.cent = static_cast<const float *>(centroids); pa.k = (int)k; pa.bias = bias;
   pa.ids = ids; pa.dists = dists; pa.out_batch_stride = (int64_t)n;
-  LH_TRY(launch_assign(ctx, pa, (int)d, metric == LANCE_HIP_COSINE ? LANCE_HIP_L2 : metric, 1));
+  if (n > 0) LH_TRY(launch_assign(ctx, pa, (int)d, metric == LANCE_HIP_COSINE ? LANCE_HIP_L2 : metric, 1));   // (a rank without rows: zeros)
   LH_TRY(stable_group(ctx, ids, (int64_t)n, (int64_t)n, (int)k, 1, starts, sorted_rows, (int64_t)n, nullptr));
   hipLaunchKernelGGL(kmeans_stats_kernel, dim3((unsigned)cdiv(k, 4), 1), dim3(256), 0, ctx->stream, dists, (int64_t)n, (int)k,
                      sorted_rows, (int64_t)n, starts, losses_d, radius_d, last_d, (const uint8_t *)nullptr);
   hipLaunchKernelGGL(kmeans_accumulate_kernel, dim3((unsigned)cdiv((uint64_t)k * d, 256), 1), dim3(256), 0, ctx->stream,
                      static_cast<const float *>(x), (int64_t)d, 0, (int)d, (int)k, sorted_rows, (int64_t)n, starts, buf, (int64_t)k * d,
                      (const uint8_t *)nullptr, 0, 0);
-  hipLaunchKernelGGL(counts_to_float_kernel, dim3((unsigned)cdiv(k, 256)), dim3(256), 0, ctx->stream, starts, (int)k, buf + (size_t)k * d);
+  hipLaunchKernelGGL(counts_to_float_kernel, dim3((unsigned)cdiv(k, 256)), dim3(256), 0, ctx->stream, starts, (int)k, buf + (size_t)k * d,
+                     (const uint8_t *)nullptr);
   LH_CHECK_HIP(hipGetLastError());
   if (losses) LH_CHECK_HIP(hipMemcpyAsync(losses, losses_d, (size_t)k * 8, hipMemcpyDeviceToDevice, ctx->stream));
   if (radius) LH_CHECK_HIP(hipMemcpyAsync(radius, radius_d, (size_t)k * 4, hipMemcpyDeviceToDevice, ctx->stream));
@@ -911,7 +914,8 @@ __global__ void kmeans_shard_init_kernel(KmShardState *st, float *bias, int k, f
 }
 
 // a converged run must keep contributing ZEROS? no: every rank converges at the same iteration (same reduced numbers), and
-// the caller stops issuing collectives once shard_end reports inactive; estep on an inactive state leaves the buffers as is.
+// the caller stops issuing collectives once shard_end reports inactive; estep on an inactive state leaves the buffers as is
+// (every kernel it enqueues is gated, the count conversion included: the reduced counts must not fall back to this rank's).
 __global__ void kmeans_shard_gate_kernel(const KmShardState *st, uint8_t *active_byte) { *active_byte = st->active ? 1 : 0; }
 
 // kmeans_random_init's row choice (kmeans.rs:149-170 shape; the engine's seeded reservoir, rng.h) -- host only
@@ -972,7 +976,7 @@ int lance_hip_kmeans_shard_estep(lance_hip_ctx *ctx, int metric, const float *x,
                      (int64_t)n, starts, losses, radius, last_d, act);
   hipLaunchKernelGGL(kmeans_accumulate_kernel, dim3((unsigned)cdiv((uint64_t)k * d, 256), 1), dim3(256), 0, ctx->stream, x, (int64_t)d, 0,
                      (int)d, (int)k, sorted_rows, (int64_t)n, starts, buf, (int64_t)k * d, act, 0, 0);
-  hipLaunchKernelGGL(counts_to_float_kernel, dim3((unsigned)cdiv(k, 256)), dim3(256), 0, ctx->stream, starts, (int)k, buf + (size_t)k * d);
+  hipLaunchKernelGGL(counts_to_float_kernel, dim3((unsigned)cdiv(k, 256)), dim3(256), 0, ctx->stream, starts, (int)k, buf + (size_t)k * d, act);
   LH_CHECK_HIP(hipGetLastError());
   return LANCE_HIP_OK;
 }

@@ -15,9 +15,14 @@ The reference has no distributed path; this is the MI355X-native ext
     index for search (16 MB of codes for SIFT-1M).
   * search: replicas, the query batch is split by the caller -- no data-path collective.
 
-Sharded sums are added in a different order than the single-GPU row-order chain, so the
-multi-GPU centroids agree with the single-GPU ones to f32 round-off, not bit for bit; the
-inference kernels (assign / encode / search) stay bit-exact given the same model.
+What the sharded trainer computes is defined exactly (tests/sharded_kmeans_spec.py): a rank's partials are summed in ITS row
+order (f32 sums, f64 losses), the ranks' partials are added in rank order, and every rank runs the same update on the reduced
+numbers.  So the model is bit-identical to the single-GPU trainer on one rank and wherever the partial sums are exact
+(integer-valued rows, sums below 2^24), for any shard layout; on other data each layout has its own, reproducible, result that
+differs from the single-GPU one by f32 summation order.  One known divergence from the reference beyond summation order: among
+clusters that TIE for largest the reference takes the one whose last member comes first in row order, the reduced buffers carry no
+last row and the sharded update takes the smallest id -- it matters only when such a tie happens in an iteration whose `adjusted`
+is the binding term of the balance factor.  The inference kernels (assign / encode / search) stay bit-exact given the same model.
 
 The loop is written against a small engine interface (estep_partial / finalize) so the
 world_size-2 gloo tests can drive it on CPU with a stand-in engine.
@@ -94,6 +99,8 @@ def _split_clusters(n, cnts, centroids, rng):
     eps = f32(1.0 / 1024.0)
     for i in range(k):
         if cnts[i] == 0:
+            if not (np.asarray(cnts) >= 2).any():      # no cluster left to halve: the rejection loop would never end (the kernel's `splittable`)
+                break
             j = 0
             while True:
                 p = (f32(cnts[j]) - f32(1.0)) / f32(n - k)
@@ -113,7 +120,11 @@ def train_kmeans_sharded(engine, x_local, k, n_total, max_iters=50, tol=1e-4, ba
                          metric="l2", group=None):
     """Distributed KMeans::train_kmeans.  x_local: this rank's rows; n_total: rows over all ranks.
     init: [k,d] initial centroids (identical on all ranks) or None -> rank 0 draws k of ITS rows
-    (kmeans_random_init shape) and broadcasts them.  -> (centroids, loss, iters)"""
+    (kmeans_random_init shape) and broadcasts them.  -> (centroids, loss, iters)
+    Contract (tests/sharded_kmeans_spec.py): per-rank partials in row order, folded in rank order; bit-identical to the single-GPU
+    trainer on one rank and wherever the sums are exact; the first cluster of maximal size by id where the reference takes the one
+    whose last member comes first (differs only on a tie for largest while `adjusted` binds).  A CUDA shard takes the device loop,
+    anything else the host loop below; both follow the same contract."""
     f32 = np.float32
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
@@ -141,7 +152,7 @@ def train_kmeans_sharded(engine, x_local, k, n_total, max_iters=50, tol=1e-4, ba
     iters = 0
     for it in range(1, max_iters + 1):
         iters = it
-        bf = min(adjusted, bf_param)
+        bf = adjusted if adjusted < bf_param else bf_param      # f32::min as the update kernel spells it
         bias = None
         if bf_param != 0:
             bias = torch.from_numpy((f32(bf) * sizes.astype(f32)).astype(f32)).to(dev)
@@ -159,7 +170,10 @@ def train_kmeans_sharded(engine, x_local, k, n_total, max_iters=50, tol=1e-4, ba
         adjusted = (f32(rh[max_id]) - f32(lh[max_id]) / f32(sizes[max_id])) / f32(n_total)
         size_loss = f32(int((sizes.astype(object) ** 2).sum()))
         balance_loss = f32(bf) * (size_loss - f32(int(n_total) ** 2) / f32(k))
-        last_loss = float(lh.sum()) + float(balance_loss)
+        lsum = 0.0
+        for v in lh.tolist():                                # f64 chain in cluster order (np.sum adds pairwise)
+            lsum = lsum + v
+        last_loss = lsum + float(balance_loss)
         if (sizes == 0).any():
             ch = cent.cpu().numpy()
             _split_clusters(int(n_total), sizes, ch, split_rng)

@@ -104,10 +104,12 @@ def test_sharded_kmeans_two_ranks(case):
     # every rank holds the same model, bit for bit, and took the same decisions
     assert (c0.view(np.uint32) == c1.view(np.uint32)).all() and l0 == l1 and i0 == i1
     assert (d0.view(np.uint32) == d1.view(np.uint32)).all()
-    # and it agrees with the single-process reference loop up to f32 summation order
+    # and it agrees with the single-process reference loop up to f32 summation order (real-valued rows on two ranks: the partials are
+    # added in rank order; tests/test_sharded_kmeans_spec.py pins this loop to its specification bit for bit on one rank)
     x, k, bf = _data(case)
     oc, ol, oit, _ = oracle.kmeans_train(x, k, max_iters=15, balance_factor=f32(bf) / f32(x.shape[0]), init=x[:k].copy(), seed=5)
-    if case != "dups":          # split perturbations amplify round-off; only the structure is compared there
+    if case != "dups":          # split perturbations amplify the summation-order difference: this loop is compared bit for bit, splits included, on ONE rank in
+        # tests/test_sharded_kmeans_spec.py; on two ranks a split is covered only by the c0 == c1 equality above
         assert i0 == oit
         assert np.allclose(c0, oc, rtol=1e-4, atol=1e-4)
         assert abs(l0 - ol) <= 1e-5 * abs(ol)
@@ -468,7 +470,7 @@ def test_hierarchical_kmeans_spread_over_ranks_is_the_single_trainer_bit_for_bit
     """k = 700 > 256: the reference trains hierarchically (kmeans.rs:746-1003).  The multi-GPU trainer computes the splits of the largest
     clusters on different ranks and applies them in the reference's order: centroids equal to the oracle's single-process trainer bit
     for bit -- one process with speculation windows 1 (the plain loop), 4 and 9, and gloo worlds of 2 and 3 (sharded
-    training for nlist > 4096 / north_star config 5; a row-sharded Lloyd loop would only agree to round-off)."""
+    training for nlist > 4096 / north_star config 5; a row-sharded Lloyd loop equals it only where its sums are exact)."""
     import oracle
     sys.path.insert(0, ROOT)
     from lance_amd import dist as ld
