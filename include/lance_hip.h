@@ -271,6 +271,31 @@ int lance_hip_index_info(const lance_hip_index *idx, uint64_t *n_rows, uint32_t 
 int lance_hip_index_export(lance_hip_ctx *ctx, const lance_hip_index *idx, uint32_t *part_offsets_host,
                            uint8_t *codes_transposed_host, uint64_t *row_ids_host);
 
+/* ---- index maintenance: append / merge, remap / delete, row-major read side ------------------------------------------------
+ * optimize_indices (rust/lance/src/index/vector/ivf.rs:355-560; builder.rs:685-935 take_partition_batches + StorageBuilder::build)
+ * and remap (builder.rs:256-359, pq/storage.rs:499-560, quantizer.rs:244-280) for IVF_PQ (8- and 4-bit), IVF_FLAT and IVF_SQ
+ * handles.  A source is never modified: every call returns a NEW handle (own copy of the model, no raw vectors attached -- see
+ * lance_hip_index_set_raw), destroyed with lance_hip_index_destroy.  The rows move HBM -> HBM; until the caller destroys the
+ * sources, sources and result are resident together.  Partitions are neither split (builder.rs:1152-1176) nor joined (:1343-1400). */
+/* new_ids[i] of lance_hip_index_remap: the row is deleted.  (The same value marks a missing result id in the search outputs.) */
+#define LANCE_HIP_ROW_DELETED 0xFFFFFFFFFFFFFFFFull
+/* For every partition: the rows of srcs[0] in stored order, then those of srcs[1], ...  1 <= n_srcs <= 64.  The sources must agree
+ * on kind, metric, dtype, d, nlist, m, nbits and (IVF_SQ) bounds, and carry bitwise equal centroids and codebook: otherwise
+ * LANCE_HIP_EINVAL, the message naming the first field that differs.  Fewer than 2^32 rows in all.                                */
+int lance_hip_index_merge(lance_hip_ctx *ctx, const lance_hip_index *const *srcs, uint32_t n_srcs, lance_hip_index **out);
+/* old_ids / new_ids: n_map DEVICE words each, old_ids strictly ascending (checked; LANCE_HIP_EINVAL otherwise).  For every stored
+ * row, in stored order: id == old_ids[i] -> the row is kept with id new_ids[i], or dropped when new_ids[i] == LANCE_HIP_ROW_DELETED;
+ * id not among old_ids -> kept unchanged.  Every lookup is against the ids BEFORE the call (a mapping that swaps two ids swaps
+ * them).  n_map == 0: an equal copy.                                                                                              */
+int lance_hip_index_remap(lance_hip_ctx *ctx, const lance_hip_index *src, const uint64_t *old_ids, const uint64_t *new_ids,
+                          uint64_t n_map, lance_hip_index **out);
+/* The stored rows of any index kind in stored order, row-major and unpadded (HOST pointers, any may be NULL): part_offsets
+ * [nlist + 1]; rows = code bytes per row (IVF_PQ: m, or m / 2 for 4-bit), d f32 (IVF_FLAT) or d code bytes (IVF_SQ); aux = the
+ * per-row sums of squared codes (IVF_SQ only, ignored otherwise); row ids.  lance_hip_index_export keeps the reference's
+ * transposed layout.                                                                                                              */
+int lance_hip_index_export_rows(lance_hip_ctx *ctx, const lance_hip_index *idx, uint32_t *part_offsets_host, void *rows_host,
+                                uint32_t *aux_host, uint64_t *row_ids_host);
+
 /* ---- a14: IvfModel::find_partitions (ivf/storage.rs:107-119, kmeans.rs:1134-1158) -- */
 /* Batched.  Ascending by distance; equal distances ordered by partition id (the
  * reference's partial sort is unstable, so any order of equals is a valid outcome).

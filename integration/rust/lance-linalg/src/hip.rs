@@ -111,6 +111,14 @@ extern "C" {
         ids: *mut u64, dists: *mut f32) -> i32;
     pub fn lance_hip_ivfsq_search_filtered(ctx: *mut LanceHipCtx, idx: *const LanceHipIndex, q: *const c_void, nq: u32, k: u32,
         nprobes: u32, allow_by_rowid: *const u8, n_allow: u64, ids: *mut u64, dists: *mut f32) -> i32;
+    // index maintenance (optimize_indices: ivf.rs:355-560, builder.rs:685-935; remap: builder.rs:256-359): every call returns a new
+    // handle and leaves its sources untouched; new_ids[i] == u64::MAX (LANCE_HIP_ROW_DELETED) drops the row
+    pub fn lance_hip_index_merge(ctx: *mut LanceHipCtx, srcs: *const *const LanceHipIndex, n_srcs: u32,
+        out: *mut *mut LanceHipIndex) -> i32;
+    pub fn lance_hip_index_remap(ctx: *mut LanceHipCtx, src: *const LanceHipIndex, old_ids: *const u64, new_ids: *const u64,
+        n_map: u64, out: *mut *mut LanceHipIndex) -> i32;
+    pub fn lance_hip_index_export_rows(ctx: *mut LanceHipCtx, idx: *const LanceHipIndex, part_offsets_host: *mut u32,
+        rows_host: *mut c_void, aux_host: *mut u32, row_ids_host: *mut u64) -> i32;
     pub fn lance_hip_flat_topk(ctx: *mut LanceHipCtx, dtype: i32, metric: i32, x: *const c_void, row_ids: *const u64,
         n: u64, d: u32, q: *const c_void, nq: u32, k: u32, ids: *mut u64, dists: *mut f32) -> i32;
     /// multivec_distance (distance.rs:107-206) of one multivector query to every row of a List<FixedSizeList> column: `values` is the

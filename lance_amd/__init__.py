@@ -11,7 +11,7 @@ from ._lib import LanceHipError
 
 __all__ = ["_lib", "LanceHipError", "Engine", "DeviceIndex", "KMeans", "IvfPqParams", "IvfPqIndex", "IvfSqIndex", "DeviceSqIndex", "create_index",
            "flat_knn", "multivector_distance", "multivector_flat_knn", "train_ivf_centroids", "train_pq_codebook", "train_sq_bounds", "default_engine", "load_index",
-           "validate_vector_index", "IndicesBuilder", "IvfModel", "PqModel"]
+           "validate_vector_index", "merge_indices", "IndicesBuilder", "IvfModel", "PqModel"]
 
 
 def __getattr__(name):
@@ -21,7 +21,7 @@ def __getattr__(name):
         return getattr(engine, name)
     if name in ("KMeans", "IvfPqParams", "IvfPqIndex", "create_index", "flat_knn", "multivector_distance", "multivector_flat_knn",
                 "train_ivf_centroids", "IvfSqIndex", "train_sq_bounds",
-                "train_pq_codebook", "default_engine", "load_index", "validate_vector_index"):
+                "train_pq_codebook", "default_engine", "load_index", "validate_vector_index", "merge_indices"):
         from . import vector
         return getattr(vector, name)
     if name in ("IndicesBuilder", "IvfModel", "PqModel"):

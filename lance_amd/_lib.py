@@ -17,6 +17,7 @@ NONE = 0xFFFFFFFF
 SQ_MAX_DIM = 16384                   # LANCE_HIP_SQ_MAX_DIM (include/lance_hip.h)
 MULTIVEC_MAX_QUERY_VECTORS = 256     # LANCE_HIP_MULTIVEC_MAX_QUERY_VECTORS (include/lance_hip.h)
 U64_MAX = 0xFFFFFFFFFFFFFFFF
+ROW_DELETED = U64_MAX               # LANCE_HIP_ROW_DELETED (include/lance_hip.h)
 
 METRICS = {"l2": L2, "L2": L2, "euclidean": L2, "cosine": COSINE, "dot": DOT, 0: L2, 1: COSINE, 2: DOT}
 
@@ -41,6 +42,7 @@ SYMBOLS = [
     "lance_hip_shuffle_buffer_write",
     "lance_hip_comm_unique_id", "lance_hip_comm_create", "lance_hip_comm_adopt", "lance_hip_comm_from_callback", "lance_hip_comm_destroy", "lance_hip_kmeans_train_sharded", "lance_hip_kmeans_train_sharded_x",
     "lance_hip_kmeans_shard_estep_x",
+    "lance_hip_index_merge", "lance_hip_index_remap", "lance_hip_index_export_rows",
 ]
 
 
@@ -122,6 +124,9 @@ def load():
         "lance_hip_index_prewarm": (i32, [vp, vp]),
         "lance_hip_index_info": (i32, [vp, C.POINTER(u64), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]),
         "lance_hip_index_export": (i32, [vp, vp, vp, vp, vp]),
+        "lance_hip_index_merge": (i32, [vp, C.POINTER(vp), u32, C.POINTER(vp)]),
+        "lance_hip_index_remap": (i32, [vp, vp, vp, vp, u64, C.POINTER(vp)]),
+        "lance_hip_index_export_rows": (i32, [vp, vp, vp, vp, vp, vp]),
         "lance_hip_find_partitions": (i32, [vp, i32, i32, vp, u32, u32, vp, u32, u32, vp, vp]),
         "lance_hip_pq_scan_topk": (i32, [vp, i32, i32, vp, u32, vp, u32, u32, vp, vp, u64, u32, i32, f32, f32, vp, vp,
                                          C.POINTER(u32)]),

@@ -494,8 +494,9 @@ int lance_hip_ivfpq_encode(lance_hip_ctx *ctx, int dtype, int metric, const void
   return encode_finish(ctx, n, nlist, dists, part_ids, loss_out_host);
 }
 
-static int index_alloc_common(lance_hip_ctx *ctx, int dtype, int metric, uint32_t d, const void *centroids, uint32_t nlist,
-                              const void *codebook, uint32_t m, uint32_t nbits, lance_hip_index **out) {
+// model_dt: the element type the model arrives in -- model_dtype(dtype) from a caller, LANCE_HIP_F32 when it is another handle's widened copy
+static int index_alloc_model(lance_hip_ctx *ctx, int dtype, int model_dt, int metric, uint32_t d, const void *centroids, uint32_t nlist,
+                             const void *codebook, uint32_t m, uint32_t nbits, lance_hip_index **out) {
   LH_REQUIRE(ctx && centroids && codebook && out, "index: NULL argument");
   LH_TRY(check_dtype(dtype, "index"));
   // f16 columns under dot: the table entries are dot products of f16 sub-vectors (32-lane dot_scalar, dot.rs:91-102) -- identical
@@ -510,15 +511,29 @@ static int index_alloc_common(lance_hip_ctx *ctx, int dtype, int metric, uint32_
   ix->dtype = dtype;
   // the index keeps f32 copies of the model (f16 widens exactly); the scan rounds the residual query to f16 when dtype is f16
   int r = dev_dup(ctx, nullptr, (size_t)nlist * d * 4, reinterpret_cast<void **>(&ix->centroids));
-  if (r == LANCE_HIP_OK) r = widen_into(ctx, model_dtype(dtype), centroids, (size_t)nlist * d, ix->centroids);
+  if (r == LANCE_HIP_OK) r = widen_into(ctx, model_dt, centroids, (size_t)nlist * d, ix->centroids);
   const size_t cb_elems = (size_t)m * ((size_t)1 << nbits) * (d / m);
   if (r == LANCE_HIP_OK) r = dev_dup(ctx, nullptr, cb_elems * 4, reinterpret_cast<void **>(&ix->codebook));
-  if (r == LANCE_HIP_OK) r = widen_into(ctx, model_dtype(dtype), codebook, cb_elems, ix->codebook);
+  if (r == LANCE_HIP_OK) r = widen_into(ctx, model_dt, codebook, cb_elems, ix->codebook);
   if (r == LANCE_HIP_OK && m != 0 && nbits == 8) r = qscan_index_constants(ctx, ix);
   if (r == LANCE_HIP_OK) r = dev_dup(ctx, nullptr, (size_t)(nlist + 1) * 4, reinterpret_cast<void **>(&ix->part_offsets));
   if (r != LANCE_HIP_OK) { delete ix; return r; }
   *out = ix;
   return LANCE_HIP_OK;
+}
+
+static int index_alloc_common(lance_hip_ctx *ctx, int dtype, int metric, uint32_t d, const void *centroids, uint32_t nlist,
+                              const void *codebook, uint32_t m, uint32_t nbits, lance_hip_index **out) {
+  return index_alloc_model(ctx, dtype, model_dtype(dtype), metric, d, centroids, nlist, codebook, m, nbits, out);
+}
+
+extern "C++" {
+namespace lh {
+// an empty IVF_PQ handle whose model is `src`'s f32 copies (index_update.hip): same search constants as any new handle
+int index_alloc_like_pq(lance_hip_ctx *ctx, const lance_hip_index *src, lance_hip_index **out) {
+  return index_alloc_model(ctx, src->dtype, LANCE_HIP_F32, src->metric, src->d, src->centroids, src->nlist, src->codebook, src->m, src->nbits, out);
+}
+}  // namespace lh
 }
 
 static int index_finish_offsets(lance_hip_ctx *ctx, lance_hip_index *ix) {

@@ -172,6 +172,7 @@ int launch_normalize_planes(lance_hip_ctx *ctx, const float *x, int64_t n, int d
 
 // quantised 4-query filter scan + exact re-evaluation (search_q.hip), driven by ivfpq_scan_merge_pm
 int qscan_index_constants(lance_hip_ctx *ctx, lance_hip_index *ix);
+int index_alloc_like_pq(lance_hip_ctx *ctx, const lance_hip_index *src, lance_hip_index **out);   // build.hip
 constexpr int QSCAN_SEG_CAP = 256;   // survivors kept per (query, probe)
 struct SelectOut;
 bool qscan_supported(const lance_hip_index *ix, uint32_t nq, uint32_t nprobes);

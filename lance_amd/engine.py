@@ -550,6 +550,44 @@ def _torch_inputs_ready():
     non-blocking: torch's stream has no implicit dependency on them."""
     torch.cuda.current_stream().synchronize()
 
+# ---- index maintenance (lance_amd/csrc/index_update.hip): shared by the three handle classes -----------------------------------
+def _merge_handles(engine, indices):
+    """lance_hip_index_merge over the handles of `indices`, in that order -> a new handle"""
+    arr = (C.c_void_p * max(1, len(indices)))(*[ix.h.value for ix in indices])
+    h = C.c_void_p()
+    torch.cuda.synchronize()
+    check(engine.lib.lance_hip_index_merge(engine.h, arr, len(indices), C.byref(h)))
+    return h
+
+
+def _remap_handle(engine, handle, old_ids, new_ids):
+    """lance_hip_index_remap: old_ids strictly ascending (as unsigned), new_ids with _lib.ROW_DELETED (-1 as int64) for a deleted row;
+    both int64 bit patterns of the u64 ids -> a new handle"""
+    old = to_device(old_ids, torch.int64).reshape(-1)
+    new = to_device(new_ids, torch.int64).reshape(-1)
+    if old.numel() != new.numel():
+        raise ValueError(f"remap: {old.numel()} old ids but {new.numel()} new ids")
+    h = C.c_void_p()
+    torch.cuda.synchronize()
+    check(engine.lib.lance_hip_index_remap(engine.h, handle, _ptr(old), _ptr(new), old.numel(), C.byref(h)))
+    return h
+
+
+def _export_rows(engine, handle, nlist, row_bytes, aux=False):
+    """lance_hip_index_export_rows -> (part_offsets u32[nlist + 1], rows u8 [n, row_bytes], aux u32[n] | None, row_ids u64[n])"""
+    n = C.c_uint64()
+    check(engine.lib.lance_hip_index_info(handle, C.byref(n), None, None, None))
+    n = n.value
+    offs = np.empty(nlist + 1, np.uint32)
+    rows = np.empty((n, row_bytes), np.uint8)
+    xx = np.empty(n, np.uint32) if aux else None
+    rid = np.empty(n, np.uint64)
+    torch.cuda.synchronize()
+    check(engine.lib.lance_hip_index_export_rows(engine.h, handle, offs.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p),
+                                                 None if xx is None else xx.ctypes.data_as(C.c_void_p), rid.ctypes.data_as(C.c_void_p)))
+    return offs, rows, xx, rid
+
+
 class DeviceFlatIndex:
     """Handle of a device-resident IVF_FLAT index (FlatIndex sub-index over the raw vectors of each partition)."""
 
@@ -585,6 +623,23 @@ class DeviceFlatIndex:
         torch.cuda.synchronize()
         check(engine.lib.lance_hip_index_load(engine.h, os.fspath(index_dir).encode(), dt, C.byref(h)))
         return cls(engine, h, c.metric, to_device(c.centroids, torch.float16 if c.dtype == "float16" else torch.float32), ddt)
+
+    @classmethod
+    def merge(cls, indices, raw=None):
+        """For every partition the rows of indices[0], then those of indices[1], ... (lance_hip_index_merge) -> a new index; the
+        sources stay as they are.  raw is accepted for symmetry with DeviceIndex.merge and ignored (no refine on this kind)."""
+        first = indices[0]
+        return cls(first.engine, _merge_handles(first.engine, indices), first.metric, first.centroids, first.data_dtype)
+
+    def remap(self, old_ids, new_ids):
+        """lance_hip_index_remap with a mapping already sorted by old id -> a new index"""
+        return type(self)(self.engine, _remap_handle(self.engine, self.h, old_ids, new_ids), self.metric, self.centroids, self.data_dtype)
+
+    def export_rows(self):
+        """-> (part_offsets u32[nlist + 1], vectors f32 [n, d], row_ids u64[n]) in stored order"""
+        nlist, d = self.centroids.shape
+        offs, rows, _, rid = _export_rows(self.engine, self.h, nlist, 4 * d)
+        return offs, rows.view(np.float32), rid
 
     def save(self, index_dir, loss=None):
         torch.cuda.synchronize()
@@ -650,6 +705,22 @@ class DeviceSqIndex:
         check(engine.lib.lance_hip_ivfsq_create(engine.h, dt, METRICS[metric], d, _ptr(cent), cent.shape[0], _ptr(codes), _ptr(part),
                                                 _ptr(rid), n, b, C.byref(h)))
         return cls(engine, h, metric, cent, cent.dtype, (float(bounds[0]), float(bounds[1])))
+
+    @classmethod
+    def merge(cls, indices, raw=None):
+        """as DeviceFlatIndex.merge; the sources must share the quantiser's bounds bit for bit"""
+        first = indices[0]
+        return cls(first.engine, _merge_handles(first.engine, indices), first.metric, first.centroids, first.data_dtype, first.bounds)
+
+    def remap(self, old_ids, new_ids):
+        """lance_hip_index_remap with a mapping already sorted by old id -> a new index"""
+        return type(self)(self.engine, _remap_handle(self.engine, self.h, old_ids, new_ids), self.metric, self.centroids, self.data_dtype,
+                          self.bounds)
+
+    def export_rows(self):
+        """-> (part_offsets u32[nlist + 1], codes u8 [n, d], sums of squared codes u32[n], row_ids u64[n]) in stored order"""
+        nlist, d = self.centroids.shape
+        return _export_rows(self.engine, self.h, nlist, d, aux=True)
 
     def save(self, index_dir, loss=None):
         raise NotImplementedError("IVF_SQ index files are not supported (IVF_PQ and IVF_FLAT are)")
@@ -751,6 +822,24 @@ class DeviceIndex:
         mod, rem = (1, 0) if lists is None else (int(lists[0]), int(lists[1]))
         check(engine.lib.lance_hip_index_load_lists(engine.h, os.fspath(index_dir).encode(), dt, mod, rem, C.byref(h)))
         return cls(engine, h, c.metric, to_device(c.centroids, mdt), to_device(c.codebook, mdt), raw, ddt)
+
+    @classmethod
+    def merge(cls, indices, raw=None):
+        """For every partition the rows of indices[0], then those of indices[1], ... (lance_hip_index_merge) -> a new index; the
+        sources stay as they are.  raw: the vectors for refine, indexed by row id (the sources' attachments are not inherited)."""
+        first = indices[0]
+        return cls(first.engine, _merge_handles(first.engine, indices), first.metric, first.centroids, first.codebook, raw, first.data_dtype)
+
+    def remap(self, old_ids, new_ids, raw=None):
+        """lance_hip_index_remap with a mapping already sorted by old id -> a new index"""
+        return type(self)(self.engine, _remap_handle(self.engine, self.h, old_ids, new_ids), self.metric, self.centroids, self.codebook, raw,
+                          self.data_dtype)
+
+    def export_rows(self):
+        """-> (part_offsets u32[nlist + 1], codes u8 [n, code bytes] row-major, row_ids u64[n]) in stored order"""
+        m = self.codebook.shape[0]
+        offs, rows, _, rid = _export_rows(self.engine, self.h, self.centroids.shape[0], m if _nbits(self.codebook) == 8 else m // 2)
+        return offs, rows, rid
 
     def save(self, index_dir, loss=None):
         """HBM -> the file pair, in the layout merge_partitions writes (builder.rs:938-1079), through lance_hip_index_save."""

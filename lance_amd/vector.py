@@ -20,7 +20,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from ._lib import METRICS, NONE
+from ._lib import EINVAL, METRICS, NONE, ROW_DELETED, LanceHipError
 from .engine import DeviceFlatIndex, DeviceIndex, DeviceSqIndex, Engine, _dtype_name, check_multivector, to_device
 
 _engine = None
@@ -125,7 +125,121 @@ class BuildStats:
         return sum(self.seconds.values())
 
 
-class IvfPqIndex:
+def _mapping_arrays(mapping):
+    """dict {old: new | None} or (old_ids, new_ids) with None / -1 for a deleted row -> (old u64, new u64) numpy arrays"""
+    def ids(seq, allow_deleted):
+        if isinstance(seq, torch.Tensor):
+            seq = seq.detach().cpu().numpy()
+        if isinstance(seq, np.ndarray) and seq.dtype.kind in "iu":
+            return np.ascontiguousarray(seq.astype(np.int64) if seq.dtype.kind == "i" else seq.astype(np.uint64)).view(np.uint64).reshape(-1)
+        out = np.empty(len(seq), np.uint64)
+        for i, v in enumerate(seq):
+            if v is None or int(v) == -1:
+                if not allow_deleted:
+                    raise ValueError("remap: an old id cannot be None / -1")
+                out[i] = ROW_DELETED
+            else:
+                out[i] = int(v)
+        return out
+    if isinstance(mapping, dict):
+        old, new = list(mapping.keys()), list(mapping.values())
+    else:
+        old, new = mapping
+    old, new = ids(old, False), ids(new, True)
+    if old.size != new.size:
+        raise ValueError(f"remap: {old.size} old ids but {new.size} new ids")
+    return old, new
+
+
+class _Maintenance:
+    """append / remap / delete of an index wrapper (lance_hip_index_merge / _remap): every call returns a NEW index and leaves this one
+    as it is -- both are resident until the caller drops one.  What is built is the reference's no-split / no-join branch of
+    optimize_indices and remap (rust/lance/src/index/vector/ivf.rs:355-560, builder.rs:256-359)."""
+    _rows_offered = None      # rows handed to create_index / append so far: the next positional row id (None: opened from files, merged)
+
+    def _wrap(self, dev_index, rows_offered):
+        raise NotImplementedError
+
+    def _delta(self, x_new, row_ids):
+        raise NotImplementedError
+
+    def export_rows(self):
+        """the stored rows in stored order, row-major (DeviceIndex / DeviceFlatIndex / DeviceSqIndex.export_rows)"""
+        return self._ix.export_rows()
+
+    def append(self, x_new, row_ids=None, raw=None):
+        """The index with the rows x_new added: they are transformed with THIS index's model (centroids, codebook, SQ bounds -- nothing is
+        re-trained, ivf.rs:377-378) through the calls create_index makes, grouped into a delta index and merged behind the stored rows of
+        every partition.  Non-finite rows are dropped.  row_ids: one id per row of x_new; None continues create_index's position
+        convention (rows offered so far + i), which an index opened from files cannot do.  raw (IVF_PQ): the vectors for refine."""
+        x_new = to_device(x_new)
+        if x_new.dim() != 2 or x_new.shape[1] != self._ix.centroids.shape[1]:
+            raise ValueError(f"append: rows must be [n][{self._ix.centroids.shape[1]}], got {tuple(x_new.shape)}")
+        n_new = x_new.shape[0]
+        if row_ids is None:
+            if self._rows_offered is None:
+                raise ValueError("append: this index does not know how many rows it was built from (opened from files or merged): pass row_ids")
+            rid = torch.arange(self._rows_offered, self._rows_offered + n_new, dtype=torch.int64, device=x_new.device)
+        else:
+            rid = to_device(_ids_u64(row_ids))
+            if rid.numel() != n_new:
+                raise ValueError(f"append: row_ids must hold one id per row ({n_new}), got {rid.numel()}")
+        delta = self._delta(x_new, rid)
+        try:
+            merged = type(self._ix).merge([self._ix, delta], raw=raw)
+        finally:
+            delta.close()
+        return self._wrap(merged, None if self._rows_offered is None else self._rows_offered + n_new)
+
+    def remap(self, mapping, raw=None):
+        """The index after a compaction or a delete: mapping = dict {old id: new id | None} or a pair (old_ids, new_ids) with None / -1 for
+        a deleted row.  Stored rows keep their order; a row whose id is not an old id stays as it is; all lookups are against the ids
+        before the call (a swap swaps).  Duplicate old ids raise ValueError."""
+        old, new = _mapping_arrays(mapping)
+        old_t, new_t = to_device(old), to_device(new)
+        key = old_t ^ torch.iinfo(torch.int64).min          # signed order of the key = unsigned order of the id
+        key, order = torch.sort(key)
+        if key.numel() > 1 and bool((key[1:] == key[:-1]).any()):
+            raise ValueError("remap: duplicate old ids in the mapping")
+        kw = {"raw": raw} if raw is not None else {}
+        return self._wrap(self._ix.remap(old_t[order], new_t[order], **kw), self._rows_offered)
+
+    def delete(self, row_ids, raw=None):
+        """remap with every given id mapped to deleted"""
+        ids = np.unique(_ids_u64(row_ids))
+        return self.remap((ids, np.full(ids.size, ROW_DELETED, np.uint64)), raw=raw)
+
+
+def _ids_u64(row_ids):
+    """row ids (numpy / torch / sequence, signed or unsigned) -> u64 numpy array"""
+    if isinstance(row_ids, torch.Tensor):
+        row_ids = row_ids.detach().cpu().numpy()
+    a = np.asarray(row_ids)
+    if a.dtype.kind == "i":
+        return np.ascontiguousarray(a.astype(np.int64)).view(np.uint64).reshape(-1)
+    return np.ascontiguousarray(a.astype(np.uint64)).reshape(-1)
+
+
+def merge_indices(indices, raw=None):
+    """Several indices over the same model -> one (the reference's merge of delta indices, `optimize_indices(num_indices_to_merge)`,
+    builder.rs:742-756,849-935): for every partition the rows of indices[0] in stored order, then those of indices[1], ...  The
+    sources are not modified.  ValueError (with the library's message) for mixed kinds or different models."""
+    indices = list(indices)
+    if not indices:
+        raise ValueError("merge_indices: no index given")
+    kinds = {type(ix) for ix in indices}
+    if len(kinds) != 1 or not isinstance(indices[0], _Maintenance):
+        raise ValueError(f"merge_indices: the indices must be of one kind, got {sorted(k.__name__ for k in kinds)}")
+    try:
+        merged = type(indices[0]._ix).merge([ix._ix for ix in indices], raw=raw)
+    except LanceHipError as e:
+        if e.code == EINVAL:
+            raise ValueError(str(e)) from e
+        raise
+    return indices[0]._wrap(merged, None)
+
+
+class IvfPqIndex(_Maintenance):
     """An IVF_PQ index resident in HBM with the reference's query semantics."""
 
     def __init__(self, dev_index, params, stats=None, part_ids=None, codes=None):
@@ -150,9 +264,24 @@ class IvfPqIndex:
     def export_storage(self):
         return self._ix.export()
 
+    def _wrap(self, dev_index, rows_offered):
+        out = IvfPqIndex(dev_index, self.params, self.stats)
+        out._rows_offered = rows_offered
+        return out
+
+    def _delta(self, x_new, row_ids):
+        ix = self._ix
+        part, codes = _transform_rows(ix.engine, "IVF_PQ", self.params.metric, x_new, ix.centroids, codebook=ix.codebook)
+        dtype = {torch.float16: "float16", torch.int8: "int8"}.get(ix.data_dtype, "float32")
+        return DeviceIndex.create(ix.engine, ix.metric, ix.centroids, ix.codebook, part, codes, row_ids, dtype=dtype)
+
     def shuffle_buffers(self):
         """(row_id u64, __ivf_part_id u32, __pq_code u8[M]) as numpy -- the artefact the reference's
-        `precomputed_shuffle_buffers` hand-off consumes (python/lance/vector.py:659-665)."""
+        `precomputed_shuffle_buffers` hand-off consumes (python/lance/vector.py:659-665).  An index without the retained columns
+        (opened from files, merged, appended to, remapped) hands back its stored rows: real row ids, partition order."""
+        if self.part_ids is None or self.codes is None:
+            offs, codes, rid = self._ix.export_rows()
+            return rid, np.repeat(np.arange(offs.size - 1, dtype=np.uint32), np.diff(offs.astype(np.int64))), codes
         part = self.part_ids.cpu().numpy().view(np.uint32)
         keep = part != NONE
         rid = np.arange(part.size, dtype=np.uint64)[keep]
@@ -224,18 +353,21 @@ class IvfPqIndex:
         whose stable grouping by partition is the stored order"""
         if self.part_ids is not None and self.codes is not None:
             return self.part_ids, self.codes, None
-        offs, codes_t, rid = self._ix.export()          # an index opened from files: undo the per-partition transpose,
-        n, nlist = len(rid), len(offs) - 1              # on the device (torch is only moving bytes here)
+        if hasattr(self._ix, "export_rows"):            # no retained columns: the stored rows, row-major
+            offs, codes, rid = self._ix.export_rows()
+            lens = to_device(np.diff(offs.astype(np.int64)))
+            part = torch.repeat_interleave(torch.arange(offs.size - 1, dtype=torch.int32, device=lens.device), lens)
+            return part, to_device(codes), to_device(rid)
+        offs, codes_t, rid = self._ix.export()          # a handle that only hands out the reference's layout: undo the per-partition
+        n = len(rid)                                    # transpose with one gather (row r, byte j sits at off*cb + j*n_p + r - off)
         cb = codes_t.size // n if n else 1
         ct = to_device(codes_t)
-        rm = torch.empty((n, cb), dtype=torch.uint8, device=ct.device)
-        for p in range(nlist):
-            a, b = int(offs[p]), int(offs[p + 1])
-            if b > a:
-                rm[a:b] = ct[a * cb:b * cb].view(cb, b - a).t()
         lens = to_device(np.diff(offs.astype(np.int64)))
-        part = torch.repeat_interleave(torch.arange(nlist, dtype=torch.int32, device=ct.device), lens)
-        return part, rm, to_device(rid)
+        part = torch.repeat_interleave(torch.arange(offs.size - 1, dtype=torch.int32, device=ct.device), lens)
+        start = to_device(offs[:-1].astype(np.int64))[part.long()]
+        row = torch.arange(n, device=ct.device) - start
+        src = (start * cb + row)[:, None] + torch.arange(cb, device=ct.device)[None, :] * lens[part.long()][:, None]
+        return part, ct[src.reshape(-1)].view(n, cb), to_device(rid)
 
     def prefiltered(self, allow):
         """The index restricted to the rows whose id is selected by `allow` (bool over row ids).  Under a prefilter the
@@ -282,7 +414,7 @@ class IvfPqIndex:
                 arrow_io.shuffle_buffer_batches(rid, part, codes, batch_size))
 
 
-class IvfFlatIndex:
+class IvfFlatIndex(_Maintenance):
     """IVF_FLAT: IVF partitions over the raw vectors (exact distances inside the probed partitions)."""
 
     def __init__(self, ix, params, stats, part_ids):
@@ -294,6 +426,16 @@ class IvfFlatIndex:
     @property
     def centroids(self):
         return self._ix.centroids.cpu().numpy()
+
+    def _wrap(self, dev_index, rows_offered):
+        out = IvfFlatIndex(dev_index, self.params, self.stats, None)
+        out._rows_offered = rows_offered
+        return out
+
+    def _delta(self, x_new, row_ids):
+        ix = self._ix
+        part, xs = _transform_rows(ix.engine, "IVF_FLAT", self.params.metric, x_new.to(ix.data_dtype), ix.centroids)
+        return DeviceFlatIndex.create(ix.engine, ix.metric, ix.centroids, xs, part, row_ids)
 
     def search_device(self, q, k, nprobes):
         return self._ix.search(q, k, nprobes)
@@ -326,7 +468,7 @@ class IvfFlatIndex:
         self._ix.save(index_dir, None if self.stats is None else self.stats.ivf_loss)
 
 
-class IvfSqIndex:
+class IvfSqIndex(_Maintenance):
     """IVF_SQ: IVF partitions over 8-bit scalar-quantised codes (lance-index/src/vector/sq.rs, sq/storage.rs): IVF_FLAT's search
     over a quarter of its bytes, distances computed between codes."""
 
@@ -345,6 +487,16 @@ class IvfSqIndex:
     def bounds(self):
         """the quantiser's Range<f64> as (start, end)"""
         return self._ix.bounds
+
+    def _wrap(self, dev_index, rows_offered):
+        out = IvfSqIndex(dev_index, self.params, self.stats, None)
+        out._rows_offered = rows_offered
+        return out
+
+    def _delta(self, x_new, row_ids):
+        ix = self._ix
+        part, codes = _transform_rows(ix.engine, "IVF_SQ", self.params.metric, x_new.to(ix.data_dtype), ix.centroids, bounds=ix.bounds)
+        return DeviceSqIndex.create(ix.engine, ix.metric, ix.centroids, codes, part, ix.bounds, row_ids)
 
     def search_device(self, q, k, nprobes):
         return self._ix.search(q, k, nprobes)
@@ -494,6 +646,38 @@ def train_pq_codebook(x, centroids, params: IvfPqParams, engine=None, sample_idx
     return eng.pq_train(sample, params.num_sub_vectors, params.num_bits, params.max_iters, params.sample_rate, params.seed + 2)
 
 
+def _transform_rows(eng, itype, metric, x, cent, codebook=None, bounds=None, timed=None):
+    """The rows x through the IvfTransformer chain of an index kind with a GIVEN model -> (part ids, what the storage keeps: PQ codes,
+    the rows as IVF_FLAT stores them, SQ codes).  One code path for create_index and for append (which brings the index's own model).
+    timed(name, fn): create_index's clock."""
+    if timed is None:
+        timed = lambda name, fn: fn()
+    if itype == "IVF_FLAT":
+        if metric == "cosine":
+            # IvfTransformer::new_flat (rust/lance-index/src/vector/ivf.rs:147-175): rows are normalised, assigned with L2 and
+            # STORED normalised; the sub-index keeps the cosine distance function (ivf/v2.rs:405-411)
+            if x.dtype not in (torch.float32, torch.float16):
+                raise NotImplementedError("IVF_FLAT with the cosine metric needs float32 or float16 vectors (normalize_fsl accepts float arrays only)")
+            xs = timed("normalize", lambda: eng.normalize(x))
+            part, _ = timed("transform", lambda: eng.assign(xs, cent, "l2"))
+        else:
+            xs = x
+            part, _ = timed("transform", lambda: eng.assign(x, cent, metric))
+        return part, xs
+    if itype == "IVF_SQ":
+        # the transform chain of IVF_FLAT (normalise for cosine, assign in L2 / under dot) followed by SQTransformer
+        def transform():
+            xs = eng.normalize(x) if metric == "cosine" else x
+            part, _ = eng.assign(xs, cent, "l2" if metric == "cosine" else metric)
+            # KeepFiniteVectors runs ahead of the partition transform (ivf.rs new_ivf_transformer_with_quantizer): a row with a
+            # NaN or an infinity has no partition under any metric
+            part = torch.where(torch.isfinite(xs).all(dim=1), part, torch.full_like(part, -1))
+            return part, eng.sq_encode(xs, bounds)
+        return timed("transform", transform)
+    part, codes, _ = timed("transform", lambda: eng.ivfpq_encode(x, cent, codebook, metric, want_loss=False))
+    return part, codes
+
+
 def create_index(x, index_type="IVF_PQ", metric="l2", num_partitions=256, num_sub_vectors=16, num_bits=8, max_iters=50,
                  sample_rate=256, ivf_centroids=None, pq_codebook=None, seed=42, keep_raw=True, engine=None):
     """Dataset.create_index(column, "IVF_PQ", ...) for a vector matrix resident (or copied) in HBM."""
@@ -575,35 +759,20 @@ def create_index(x, index_type="IVF_PQ", metric="l2", num_partitions=256, num_su
                 pq_pool.shutdown(wait=True)
             raise
     if itype == "IVF_FLAT":
-        if params.metric == "cosine":
-            # IvfTransformer::new_flat (rust/lance-index/src/vector/ivf.rs:147-175): rows are normalised, assigned with L2 and
-            # STORED normalised; the sub-index keeps the cosine distance function (ivf/v2.rs:405-411)
-            if x.dtype not in (torch.float32, torch.float16):
-                raise NotImplementedError("IVF_FLAT with the cosine metric needs float32 or float16 vectors (normalize_fsl accepts float arrays only)")
-            xs = timed("normalize", lambda: eng.normalize(x))
-            part, _ = timed("transform", lambda: eng.assign(xs, cent, "l2"))
-        else:
-            xs = x
-            part, _ = timed("transform", lambda: eng.assign(x, cent, params.metric))
+        part, xs = _transform_rows(eng, itype, params.metric, x, cent, timed=timed)
         fx = timed("build_partitions", lambda: DeviceFlatIndex.create(eng, params.metric, cent, xs, part))
         out = IvfFlatIndex(fx, params, stats, part)
         out._x = xs if keep_raw else None     # the stored rows (borrowed): needed to re-partition under a prefilter
+        out._rows_offered = n
         return out
     if itype == "IVF_SQ":
-        # the transform chain of IVF_FLAT (normalise for cosine, assign in L2 / under dot) followed by SQTransformer; the
-        # quantiser trains on its own sample of the column (train_sq_bounds)
+        # the quantiser trains on its own sample of the column (train_sq_bounds)
         bounds = timed("train_sq", lambda: train_sq_bounds(x, params, eng))
-
-        def transform():
-            xs = eng.normalize(x) if params.metric == "cosine" else x
-            part, _ = eng.assign(xs, cent, "l2" if params.metric == "cosine" else params.metric)
-            # KeepFiniteVectors runs ahead of the partition transform (ivf.rs new_ivf_transformer_with_quantizer): a row with a
-            # NaN or an infinity has no partition under any metric
-            part = torch.where(torch.isfinite(xs).all(dim=1), part, torch.full_like(part, -1))
-            return part, eng.sq_encode(xs, bounds)
-        part, codes = timed("transform", transform)
+        part, codes = _transform_rows(eng, itype, params.metric, x, cent, bounds=bounds, timed=timed)
         sx = timed("build_partitions", lambda: DeviceSqIndex.create(eng, params.metric, cent.to(x.dtype), codes, part, bounds))
-        return IvfSqIndex(sx, params, stats, part, codes if keep_raw else None)
+        out = IvfSqIndex(sx, params, stats, part, codes if keep_raw else None)
+        out._rows_offered = n
+        return out
     if num_bits not in (4, 8):
         raise ValueError(f"ProductQuantization: num_bits {num_bits} not supported")
     if pq_codebook is not None:
@@ -614,14 +783,16 @@ def create_index(x, index_type="IVF_PQ", metric="l2", num_partitions=256, num_su
         finally:
             if pq_pool is not None:
                 pq_pool.shutdown(wait=True)
-    part, codes, _ = timed("transform", lambda: eng.ivfpq_encode(x, cent, cb, params.metric, want_loss=False))
+    part, codes = _transform_rows(eng, itype, params.metric, x, cent, codebook=cb, timed=timed)
     ix = timed("build_partitions", lambda: DeviceIndex.create(eng, params.metric, cent, cb, part, codes, None,
                                                               raw=x if keep_raw else None,
                                                               dtype="int8" if x.dtype == torch.int8 else None))
     # Index::prewarm (ivf/v2.rs:349-352): the search-side constants (matrix-core scan tables, the lossless u8 refine copy of an
     # integer-valued f32 column) are built here, inside the build's clock, instead of inside the first search
     timed("prewarm", ix.prewarm)
-    return IvfPqIndex(ix, params, stats, part, codes)
+    out = IvfPqIndex(ix, params, stats, part, codes)
+    out._rows_offered = n
+    return out
 
 
 class _MaskedIndexView:
