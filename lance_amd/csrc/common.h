@@ -41,6 +41,10 @@ void set_error(const char *fmt, ...);
     if (_r != LANCE_HIP_OK) return _r; \
   } while (0)
 
+// flat.hip: "this launcher does not serve the call, take the other route": POSITIVE, because every LANCE_HIP_E* error code is negative
+// (-1 doubled as EINVAL and a failure inside the launcher fell back silently)
+constexpr int LH_NOT_TAKEN = 1;
+
 // a captured search (search.hip: ivfpq_search_enqueue): the ~25 launches of one batch replayed as one hipGraphLaunch
 struct GraphEntry {
   hipGraphExec_t exec = nullptr;

@@ -3,6 +3,7 @@
 #include <stdint.h>
 
 #include "common.h"
+#include "search_plan.h"
 
 namespace lh {
 
@@ -152,8 +153,8 @@ int from_f32(lance_hip_ctx *ctx, int dtype, const float *src, void *dst, size_t 
 int launch_residual(lance_hip_ctx *ctx, const float *x, int64_t n, int d, const float *cent, const uint32_t *part_ids, float *out, bool f16);
 
 
-bool pm_supported(const lance_hip_index *ix, uint32_t keff, int has_range, uint32_t nq, uint32_t nprobes);
-int ivfpq_scan_merge_pm(lance_hip_ctx *ctx, const lance_hip_index *ix, const float *qs, uint32_t nq, const uint32_t *probes,
+// search_pm.hip: a plan (search_plan.h) with route ROUTE_PAIR_SCAN or ROUTE_QUANTISED; the launchers below follow plan.bound / plan.main
+int ivfpq_scan_merge_pm(lance_hip_ctx *ctx, const lance_hip_index *ix, const IvfpqPlan &plan, const float *qs, uint32_t nq, const uint32_t *probes,
                         uint32_t nprobes, uint32_t keff, uint32_t k, bool do_refine, uint64_t *ids, float *dists,
                         uint64_t *cand_rid, uint32_t *cand_cnt, uint32_t *flags, const uint32_t *allow);
 int find_partitions_f32(lance_hip_ctx *ctx, int metric, const float *qf, uint32_t nq, uint32_t d, const float *cf, uint32_t nlist,
@@ -175,12 +176,9 @@ int qscan_index_constants(lance_hip_ctx *ctx, lance_hip_index *ix);
 int index_alloc_like_pq(lance_hip_ctx *ctx, const lance_hip_index *src, lance_hip_index **out);   // build.hip
 constexpr int QSCAN_SEG_CAP = 256;   // survivors kept per (query, probe)
 struct SelectOut;
-bool qscan_supported(const lance_hip_index *ix, uint32_t nq, uint32_t nprobes);
 // search_qt.hip: M = 48 / 64 / 96 (table tiled over the sub-quantisers); class-B queries of those shapes go to the rescan kernel
-bool qscan_tiled_shape(int m, int sd);
 int qscan_classb_to_rescan(lance_hip_ctx *ctx, const uint32_t *tbound, uint32_t nq, uint32_t nprobes, uint32_t *seg_cnt, uint32_t *qovf);
 int qscan_nearest_keys(lance_hip_ctx *ctx, const uint32_t *probes, uint32_t nq, uint32_t nprobes, uint32_t *keys, uint32_t nb = 1);
-int qscan_item_tables(lance_hip_ctx *ctx, const uint32_t *pair_starts, int nlist, int G, uint32_t *item_start, int4 *desc, uint32_t max_items);
 // G = queries per work item of the main pass
 int qscan_group(lance_hip_ctx *ctx, const uint32_t *probes, uint32_t nq, uint32_t nprobes, int nlist, const uint32_t *tglobal,
                 uint32_t *keys, uint32_t *tbound, uint32_t *pair_starts, uint32_t *pair_idx, uint32_t *item_start4, int4 *desc4,
@@ -189,33 +187,26 @@ int qbound_launch(lance_hip_ctx *ctx, const lance_hip_index *ix, const float *qs
                   const uint32_t *pair_idx0, uint32_t *item_start, int4 *desc, uint32_t max_items, uint32_t *tglobal, const uint32_t *allow);
 int qscan_launch(lance_hip_ctx *ctx, const lance_hip_index *ix, const float *qs, uint32_t nq, uint32_t nprobes, const uint32_t *pair_idx,
                  const uint32_t *item_start4, const int4 *desc4, uint32_t max_items4, const uint32_t *tbound, uint32_t *seg_cnt,
-                 uint32_t *seg_pos, uint32_t *qovf, const uint32_t *allow, const uint32_t *probes = nullptr);
-// search_qt.hip: per-query tables + per-row bias instead of a table per (query, partition) (M = 48 / 64 / 96; LANCE_HIP_QPT=1)
-bool qscan_pt_enabled(const lance_hip_index *ix);
-int qscan_pt_mode(const lance_hip_index *ix);      // 0 off, 1 tables after the bound pass, 2 tables before it (shared by both passes)
+                 uint32_t *seg_pos, uint32_t *qovf, const uint32_t *allow, const uint32_t *probes, const IvfpqPlan &plan);
+// search_qt.hip: per-query tables + per-row bias instead of a table per (query, partition) (M = 48 / 64 / 96; LANCE_HIP_QPT)
 int qbound_pt_launch(lance_hip_ctx *ctx, const lance_hip_index *ix, const float *qs, uint32_t nq, uint32_t nprobes, uint32_t keff,
                      const uint32_t *probes, const uint32_t *pair_starts0, const uint32_t *pair_idx0, uint32_t *item_start, int4 *desc,
                      uint32_t max_items, uint32_t *tglobal, const uint32_t *allow);
 int qmerge_launch(lance_hip_ctx *ctx, const lance_hip_index *ix, const float *qs, uint32_t nq, const uint32_t *probes, uint32_t nprobes,
                   const uint32_t *tbound, uint32_t *tglobal, const uint32_t *seg_cnt, const uint32_t *seg_pos, const uint32_t *qovf,
                   uint32_t *pool_key, uint32_t *pool_pos, uint32_t *pool_cnt, int pool_cap, const SelectOut &o, const uint32_t *allow,
-                  const uint32_t *qslack = nullptr, const float *seg_val = nullptr, const float *seg_scale = nullptr);
-// "this launcher does not serve the call, take the other route": POSITIVE, because every LANCE_HIP_E* error code is negative (ADVICE r05:
-// -1 doubled as EINVAL and a failure inside the launcher fell back silently)
-constexpr int LH_NOT_TAKEN = 1;
+                  PlanMain main, const uint32_t *qslack = nullptr, const float *seg_val = nullptr, const float *seg_scale = nullptr);
 // search_ms.hip: the filter scan as a [rows x d] x [d x queries] product per partition on the matrix cores (8-bit PQ, d = 64 / 128, M = 16 / 32)
-bool mscan_supported(const lance_hip_index *ix, uint32_t nq, uint32_t nprobes);
-bool mscan_batch_shape(const lance_hip_index *ix, uint32_t nq, uint32_t nprobes);
-bool mscan_dot_ready(const lance_hip_index *ix, uint32_t nq, uint32_t nprobes);   // dot metric: the batch can take the matrix-core bound pass + scan   // shape + batch-size part of mscan_supported
+PlanMsState mscan_state(const lance_hip_index *ix);
+int mscan_prepare(lance_hip_ctx *ctx, lance_hip_index *ix);   // builds lance_hip_index::ms once (allocates and synchronises: never during a capture)
 int mscan_launch(lance_hip_ctx *ctx, const lance_hip_index *ix, const float *qs, uint32_t nq, uint32_t nprobes, const uint32_t *probes,
                  const uint32_t *pair_starts, const uint32_t *pair_idx, const uint32_t *tbound, uint32_t *seg_cnt, uint32_t *seg_pos,
                  uint32_t *qovf, const uint32_t *allow, uint32_t **qslack_out, float **seg_val_out, float **seg_scale_out);
 void mscan_cut_params(int *cut_shift, uint32_t *cut_slack);
-int mscan_prewarm(lance_hip_ctx *ctx, const lance_hip_index *ix);
 int msbound_launch(lance_hip_ctx *ctx, const lance_hip_index *ix, const float *qs, uint32_t nq, uint32_t keff, const uint32_t *pair_starts0,
                    const uint32_t *pair_idx0, uint32_t *item_start, int4 *desc, uint32_t max_items, uint32_t *tglobal, const uint32_t *allow,
-                   uint32_t nb = 1);   // search_ms.hip: LH_NOT_TAKEN = the integer bound pass serves the batch
-int qscan_items(lance_hip_ctx *ctx, const uint32_t *pair_starts, int nvp, int G, uint32_t *item_start, int4 *desc, uint32_t max_items);   // search_q.hip: work items of G grouped pairs      // builds the scan's index constants now (lance_hip_index_prewarm)
+                   uint32_t nb = 1);   // search_ms.hip: the bound pass of a plan with bound == BOUND_MATRIX
+int qscan_items(lance_hip_ctx *ctx, const uint32_t *pair_starts, int nvp, int G, uint32_t *item_start, int4 *desc, uint32_t max_items);   // search_q.hip: work items of G grouped pairs
 const uint8_t *raw_compact_prepare(lance_hip_ctx *ctx, const lance_hip_index *ix);   // search.hip: lossless u8 refine copy (index.h), or nullptr
 
 }  // namespace lh

@@ -130,7 +130,7 @@ struct QboundArgs {
 
 // search_qt.hip
 int qscan_pt_launch(lance_hip_ctx *ctx, const lance_hip_index *ix, const QscanArgs &a, const float *qs, uint32_t nq, const uint32_t *probes,
-                    unsigned grid);
+                    unsigned grid, bool shared_tables);
 bool qscan_tiled_launch(lance_hip_ctx *ctx, const QscanArgs &a, int m, int sd, unsigned grid);
 bool qbound_tiled_launch(lance_hip_ctx *ctx, const QboundArgs &a, int m, int sd, unsigned grid);
 

@@ -1475,6 +1475,34 @@ int ivfpq_search_enqueue(lance_hip_ctx *ctx, const lance_hip_index *ix, const fl
   return prc;
 }
 
+// The route switches (search_plan.h: PlanSwitches), read once per process
+static const PlanSwitches &plan_switches_from_env() {
+  static const PlanSwitches sw = [] {
+    PlanSwitches s;
+    auto on = [](const char *nm) { return getenv(nm) != nullptr; };
+    auto num = [](const char *nm, uint32_t dflt) { const char *e = getenv(nm); return e ? (uint32_t)std::max(1, atoi(e)) : dflt; };
+    s.no_pm = on("LANCE_HIP_NO_PM"); s.no_qscan = on("LANCE_HIP_NO_QSCAN"); s.no_mscan = on("LANCE_HIP_NO_MSCAN"); s.no_msbound = on("LANCE_HIP_NO_MSBOUND");
+    s.no_dot_flow = on("LANCE_HIP_NO_DOT_FLOW"); s.exact_bound = on("LANCE_HIP_EXACT_BOUND"); s.pm_nobound = on("LANCE_HIP_PM_NOBOUND");
+    if (const char *e = getenv("LANCE_HIP_QPT")) s.qpt = e[0] == '2' ? 2 : (e[0] != '0' ? 1 : 0);
+    s.mscan_minq = num("LANCE_HIP_MSCAN_MINQ", s.mscan_minq); s.bound_lists = num("LANCE_HIP_BOUND_LISTS", s.bound_lists);
+    s.dot_bound_lists = num("LANCE_HIP_DOT_BOUND_LISTS", s.dot_bound_lists);
+    if (const char *e = getenv("LANCE_HIP_DOT_FLOW_SKEW")) s.dot_flow_skew = atof(e);
+    return s;
+  }();
+  return sw;
+}
+
+// what the plan reads of an index (qs: the batch's query rows, nullptr = any aligned buffer)
+static PlanIndex plan_index(const lance_hip_index *ix, const float *qs) {
+  auto aligned = [](const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; };
+  PlanIndex pi;
+  pi.metric = ix->metric; pi.dtype = ix->dtype; pi.d = ix->d; pi.m = ix->m; pi.nbits = ix->nbits; pi.nlist = ix->nlist; pi.n = ix->n; pi.max_part = ix->max_part;
+  pi.model_finite = ix->model_finite; pi.has_cb_mean = ix->cb_mean != nullptr; pi.ms_state = mscan_state(ix);
+  pi.codes_aligned16 = aligned(ix->codes, 16); pi.codebook_aligned16 = aligned(ix->codebook, 16);
+  pi.centroids_aligned8 = aligned(ix->centroids, 8); pi.query_aligned8 = aligned(qs, 8);
+  return pi;
+}
+
 static int ivfpq_search_enqueue_impl(lance_hip_ctx *ctx, const lance_hip_index *ix, const float *q, uint32_t nq, uint32_t k,
                                      uint32_t nprobes, uint32_t refine_factor, int has_range, float lower, float upper,
                                      uint64_t *ids, float *dists, uint32_t **flags_out, const uint32_t *allow) {
@@ -1487,7 +1515,6 @@ static int ivfpq_search_enqueue_impl(lance_hip_ctx *ctx, const lance_hip_index *
   // the reference has no limit on k * refine_factor; here the exact kernel's heap and the refine sort live in LDS (8192 entries)
   LH_REQUIRE(keff64 <= 8192, "search: k * refine_factor = %llu > 8192 is not supported", (unsigned long long)keff64);
   const uint32_t keff = (uint32_t)keff64;
-  const bool fast = keff <= (uint32_t)SCAN_MAX_KEFF;  // larger k: every query takes the exact (slow) kernel
   const bool do_refine = refine_factor >= 1;  // Some(rf): re-rank even when rf == 1 (scanner.rs:2884)
   LH_REQUIRE(!do_refine || ix->raw != nullptr, "search: refine_factor needs raw vectors (lance_hip_index_set_raw)");
   const int d = (int)ix->d, m = (int)ix->m, sd = d / m, nlist = (int)ix->nlist;
@@ -1501,13 +1528,21 @@ static int ivfpq_search_enqueue_impl(lance_hip_ctx *ctx, const lance_hip_index *
   if (flags_out) *flags_out = flags;
   if (nq == 0) return LANCE_HIP_OK;
 
-  const float *qs = q;
-  if (ix->metric == LANCE_HIP_COSINE) {  // knn.rs:495-498
-    float *qn = ctx->scratch_t<float>("search.qnorm", (size_t)nq * d);
-    if (!qn) return LANCE_HIP_ENOMEM;
-    LH_TRY(launch_normalize(ctx, q, (int64_t)nq, d, qn, ix->dtype == LANCE_HIP_F16));   // an f16 key is normalised in f16 arithmetic
-    qs = qn;
+  float *qn = ix->metric == LANCE_HIP_COSINE ? ctx->scratch_t<float>("search.qnorm", (size_t)nq * d) : nullptr;  // knn.rs:495-498
+  if (ix->metric == LANCE_HIP_COSINE && !qn) return LANCE_HIP_ENOMEM;
+  const float *qs = qn ? qn : q;
+  // the route, decided once and before any stage is enqueued (search_plan.h; the second plan is the final one)
+  PlanBatch pb;
+  pb.nq = nq; pb.nprobes = nprobes; pb.keff = keff; pb.has_range = has_range != 0;
+  IvfpqPlan plan = plan_ivfpq_search(plan_index(ix, qs), pb, plan_switches_from_env());
+  if (plan.wants_ms_constants) {
+    LH_REQUIRE(!ctx->capturing, "search: the index's matrix-core constants would have to be built during a graph capture");
+    LH_TRY(mscan_prepare(ctx, const_cast<lance_hip_index *>(ix)));   // the constants are a cache attached to the index
+    plan = plan_ivfpq_search(plan_index(ix, qs), pb, plan_switches_from_env());
   }
+  static const bool q_stats = getenv("LANCE_HIP_Q_STATS") != nullptr;
+  if (q_stats && plan.route != ROUTE_QUANTISED) fprintf(stderr, "[plan] nq=%u nprobes=%u keff=%u route %d: %s\n", nq, nprobes, keff, (int)plan.route, plan.why);
+  if (qn) LH_TRY(launch_normalize(ctx, q, (int64_t)nq, d, qn, ix->dtype == LANCE_HIP_F16));   // an f16 key is normalised in f16 arithmetic
   // coarse quantiser: all distances, then per-query partial sort
   float *matrix = ctx->scratch_t<float>("search.matrix", (size_t)nq * nlist);
   uint32_t *probes = ctx->scratch_t<uint32_t>("search.probes", (size_t)nq * nprobes);
@@ -1537,12 +1572,8 @@ static int ivfpq_search_enqueue_impl(lance_hip_ctx *ctx, const lance_hip_index *
     cand_cnt = ctx->scratch_t<uint32_t>("search.cand_cnt", nq);
     if (!cand_rid || !cand_cnt) return LANCE_HIP_ENOMEM;
   }
-  // scan: partition-major (two queries per LDS gather) when the batch is large enough to pair queries,
-  // query-major otherwise
-  static const bool no_pm = getenv("LANCE_HIP_NO_PM") != nullptr;
-  // (tiled shapes, M >= 48: a work item's table build is as long as a query-major workgroup's, so sharing it pays earlier)
-  const uint64_t pm_min_pairs = qscan_tiled_shape(m, sd) ? 2048 : 4096;
-  const bool use_pm = fast && !no_pm && pm_supported(ix, keff, has_range, nq, nprobes) && (uint64_t)nq * nprobes >= pm_min_pairs;
+  const bool fast = plan.route != ROUTE_EXACT_ONLY;  // else every query takes the exact (slow) kernel
+  const bool use_pm = plan.route == ROUTE_PAIR_SCAN || plan.route == ROUTE_QUANTISED;
   int nsplit = 1;
   if (nq < (uint32_t)(2 * ctx->num_cus)) {
     nsplit = (int)std::min<uint64_t>({8ull, (uint64_t)nprobes, cdiv(2ull * ctx->num_cus, nq)});
@@ -1582,13 +1613,13 @@ static int ivfpq_search_enqueue_impl(lance_hip_ctx *ctx, const lance_hip_index *
     const size_t lds = (size_t)dpad * 4 + (size_t)m * 256 * 4 + (size_t)SCAN_CAP * 8 + 256 * 4 + 8 * 4;
     LH_REQUIRE(lds <= 160 * 1024, "search: LUT of %d sub-vectors does not fit in LDS", m);
     if (use_pm) {
-      LH_TRY(ivfpq_scan_merge_pm(ctx, ix, qs, nq, probes, nprobes, keff, k, do_refine, ids, dists, cand_rid, cand_cnt, flags, allow));
-    } else if (fast && ix->nbits == 4) {
+      LH_TRY(ivfpq_scan_merge_pm(ctx, ix, plan, qs, nq, probes, nprobes, keff, k, do_refine, ids, dists, cand_rid, cand_cnt, flags, allow));
+    } else if (plan.route == ROUTE_QM4) {
       const size_t lds4 = (size_t)dpad * 4 + (size_t)m * 16 * 4 + (size_t)SCAN_CAP * 8 + 256 * 4 + 8 * 4 + 16 + 256 * 4 + (size_t)m * 16 + 16;
       ScopedTimer t(ctx, "ivfpq_scan");
       if (scan_metric == LANCE_HIP_DOT) hipLaunchKernelGGL((ivfpq_scan4_kernel<METRIC_DOT>), dim3((unsigned)nblk), dim3(256), lds4, ctx->stream, a);
       else hipLaunchKernelGGL((ivfpq_scan4_kernel<METRIC_L2>), dim3((unsigned)nblk), dim3(256), lds4, ctx->stream, a);
-    } else if (fast) {
+    } else if (plan.route == ROUTE_QM8) {
       ScopedTimer t(ctx, "ivfpq_scan");
       if (scan_metric == LANCE_HIP_DOT) launch_scan<METRIC_DOT>(ctx, a, (int)nblk, lds);
       else launch_scan<METRIC_L2>(ctx, a, (int)nblk, lds);
@@ -1683,7 +1714,7 @@ int lance_hip_index_prewarm(lance_hip_ctx *ctx, lance_hip_index *idx) {
   lh::CtxLock _ctx_lock(ctx);
   LH_REQUIRE(ctx && idx, "index_prewarm: NULL argument");
   LH_CHECK_HIP(hipSetDevice(ctx->device));
-  if (idx->m > 0 && idx->nbits == 8) LH_TRY(mscan_prewarm(ctx, idx));
+  if (idx->m > 0 && !plan_index_ms_refusal(plan_index(idx, nullptr), plan_switches_from_env())) LH_TRY(mscan_prepare(ctx, idx));   // the search's own rule
   if (coarse_groups_shape((int)idx->d, idx->nlist) && (reinterpret_cast<uintptr_t>(idx->centroids) & 15) == 0)
     LH_TRY(coarse_planes_prepare(ctx, idx, idx->metric == LANCE_HIP_COSINE ? LANCE_HIP_L2 : idx->metric));
   (void)raw_compact_prepare(ctx, idx);      // nullptr = the column stays f32 (not integer-valued, or not an f32 L2 / dot index): not an error

@@ -937,55 +937,14 @@ __global__ __launch_bounds__(1024) void ms_bound_kernel(MsBoundArgs p) {
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------
-static bool ms_shape(const lance_hip_index *ix, int *sd_out, int *ks_out) {
-  if (!ix || ix->m == 0 || ix->nbits != 8 || ix->d % ix->m != 0) return false;
-  const int d = (int)ix->d, m = (int)ix->m, sd = d / m;
-  if (!(m == 16 || m == 32)) return false;
-  const bool ok = (d == 128 && (sd == 8 || sd == 4)) || (d == 64 && sd == 4);
-  if (!ok) return false;
-  if (sd_out) *sd_out = sd;
-  if (ks_out) *ks_out = d / 16;
-  return true;
-}
-
-// The matrix-core scan pays once a partition sees a few tiles' worth of queries: a wave's 32-row chunk costs a gather (codes -> 8
-// codewords -> |c^|^2) worth ~4 tiles before its first MFMA.  Measured (gpurun r04v): 390 pairs per partition (C2) 0.188 + 0.047 ms
-// against 0.354 + 0.021 for the integer scan; 24 pairs per partition (C4 shape, nlist 4096, 10k x 10) 0.463 + 0.110 against
-// 0.324 + 0.023 -- slower.  Per (row, query) cell the model (G + t C) / (1024 t) crosses the integer scan's cost near t = 3 tiles.
-bool mscan_batch_shape(const lance_hip_index *ix, uint32_t nq, uint32_t nprobes) {
-  static const bool off = getenv("LANCE_HIP_NO_MSCAN") != nullptr;
-  static const uint32_t minq = getenv("LANCE_HIP_MSCAN_MINQ") ? (uint32_t)std::max(1, atoi(getenv("LANCE_HIP_MSCAN_MINQ"))) : 96u;
-  if (off || !ms_shape(ix, nullptr, nullptr)) return false;
-  if (ix->metric != LANCE_HIP_L2 && ix->metric != LANCE_HIP_COSINE && ix->metric != LANCE_HIP_DOT) return false;
-  return (uint64_t)nq * nprobes >= (uint64_t)minq * ix->nlist;
-}
-
-static bool ms_dot_skew_ok(const lance_hip_index *ix) {      // (see mscan_dot_ready)
-  static const double skew = getenv("LANCE_HIP_DOT_FLOW_SKEW") ? atof(getenv("LANCE_HIP_DOT_FLOW_SKEW")) : 1e18;
-  return (double)ix->max_part * (double)ix->nlist <= skew * (double)ix->n;
-}
-
-// dot metric: the quantised flow is the matrix-core bound pass + scan or nothing (the integer tables need entries >= 0).  What can only be
-// known inside the launchers (an all-zero codebook, unaligned query rows) makes them return LH_NOT_TAKEN and the caller keeps the exact pair scan.
-bool mscan_dot_ready(const lance_hip_index *ix, uint32_t nq, uint32_t nprobes) {
-  static const bool off = getenv("LANCE_HIP_NO_MSBOUND") != nullptr || getenv("LANCE_HIP_NO_DOT_FLOW") != nullptr;
-  if (off || !mscan_batch_shape(ix, nq, nprobes) || !ix->cb_mean) return false;
-  // Lists as uneven as the rows' norms (dot over unnormalised rows with components of one sign: at the C2 shape the largest of 256 lists held 82,424
-  // of the 10^6 rows and was every query's nearest): with the bound of the NEAREST list alone a fifth of the segments overflowed into exact rescans of
-  // whole lists and the flow measured slower than the exact pair scan (3.94 against 3.46 ms per 10,000-query batch, gpurun r06zu); with the bound pass
-  // over three lists it is 1.88 (gpurun r06zzg).  LANCE_HIP_DOT_FLOW_SKEW keeps a guard for A/B runs: the largest list / mean list ratio up to which
-  // the flow is taken (default: no limit).
-  if (!ms_dot_skew_ok(ix)) return false;
-  lance_hip_index *mix = const_cast<lance_hip_index *>(ix);      // (the constants are published under this lock by the first search of any context)
+// lance_hip_index::ms as the plan sees it (search_plan.h); the constants are published under the lock by the first search of any context
+PlanMsState mscan_state(const lance_hip_index *ix) {
+  lance_hip_index *mix = const_cast<lance_hip_index *>(ix);
   std::lock_guard<std::mutex> lk(mix->lazy_mu);
-  return !mix->ms || mix->ms->usable;
+  return !mix->ms ? MS_NOT_BUILT : (mix->ms->usable ? MS_USABLE : MS_UNUSABLE);
 }
 
-bool mscan_supported(const lance_hip_index *ix, uint32_t nq, uint32_t nprobes) {
-  return mscan_batch_shape(ix, nq, nprobes) && qscan_supported(ix, nq, nprobes);
-}
-
-static int mscan_prepare(lance_hip_ctx *ctx, lance_hip_index *ix) {
+int mscan_prepare(lance_hip_ctx *ctx, lance_hip_index *ix) {
   std::lock_guard<std::mutex> lk(ix->lazy_mu);   // the first search of any context builds the constants, the others wait for it
   if (ix->ms) return LANCE_HIP_OK;
   const int d = (int)ix->d, m = (int)ix->m, sd = d / m;
@@ -1066,18 +1025,13 @@ static int mscan_prepare(lance_hip_ctx *ctx, lance_hip_index *ix) {
   return LANCE_HIP_OK;
 }
 
-// -1: this index cannot take the matrix-core scan (the caller falls back to the integer scan); otherwise a status code.
-// Replaces qscan_launch: same segment outputs (seg_cnt / seg_pos / qovf / ovf) with the survivors' accumulator values (seg_val) and the
+// The main pass of a plan with main == MAIN_MATRIX (search_plan.h).  Replaces qscan_launch: same segment outputs (seg_cnt / seg_pos / qovf / ovf) with the survivors' accumulator values (seg_val) and the
 // per-pair scale that turns them into integer sums (seg_scale), plus qslack for the merge kernel's cut.
-int mscan_launch(lance_hip_ctx *ctx, const lance_hip_index *ix_c, const float *qs, uint32_t nq, uint32_t nprobes, const uint32_t *probes,
+int mscan_launch(lance_hip_ctx *ctx, const lance_hip_index *ix, const float *qs, uint32_t nq, uint32_t nprobes, const uint32_t *probes,
                  const uint32_t *pair_starts, const uint32_t *pair_idx, const uint32_t *tbound, uint32_t *seg_cnt, uint32_t *seg_pos,
                  uint32_t *qovf, const uint32_t *allow, uint32_t **qslack_out, float **seg_val_out, float **seg_scale_out) {
-  lance_hip_index *ix = const_cast<lance_hip_index *>(ix_c);   // the constants are a cache attached to the index
-  int sd = 0, ks = 0;
-  if (!ms_shape(ix, &sd, &ks)) return LH_NOT_TAKEN;
-  LH_TRY(mscan_prepare(ctx, ix));
-  if (!ix->ms->usable) return LH_NOT_TAKEN;
-  const int d = (int)ix->d, nlist = (int)ix->nlist;
+  LH_REQUIRE(ms_shape(ix->d, ix->m) && ix->ms && ix->ms->usable, "matrix-core scan: planned for an index without its constants (d=%u, m=%u)", ix->d, ix->m);
+  const int d = (int)ix->d, nlist = (int)ix->nlist, sd = d / (int)ix->m, ks = d / 16;
   const size_t npairs = (size_t)nq * nprobes;
   // slices: at most sum over the partitions of (row slices) x (pair blocks), pair blocks <= pairs / MS3_PB + 1 per partition
   const uint64_t cap = (uint64_t)ix->ms->sum_rs + (uint64_t)ix->ms->max_rs * cdiv(npairs, MS3_PB) + 8;
@@ -1172,30 +1126,20 @@ int mscan_launch(lance_hip_ctx *ctx, const lance_hip_index *ix_c, const float *q
               h[5], (double)h[6] / h[5], (double)h[0] / h[5], (double)h[1] / h[5], (double)h[2] / h[5], (double)h[3] / h[5], (double)h[4] / h[5], h[7]);
   } else if (sd == 8 && ks == 8) hipLaunchKernelGGL((ivfpq_mscan_kernel<8, 8>), dim3(grid), dim3(1024), 0, ctx->stream, a);
   else if (sd == 4 && ks == 8) hipLaunchKernelGGL((ivfpq_mscan_kernel<4, 8>), dim3(grid), dim3(1024), 0, ctx->stream, a);
-  else if (sd == 4 && ks == 4) hipLaunchKernelGGL((ivfpq_mscan_kernel<4, 4>), dim3(grid), dim3(1024), 0, ctx->stream, a);
-  else { set_error("matrix-core scan: unsupported shape (d=%d, sd=%d)", d, sd); return LANCE_HIP_EINVAL; }
+  else hipLaunchKernelGGL((ivfpq_mscan_kernel<4, 4>), dim3(grid), dim3(1024), 0, ctx->stream, a);      // (ms_shape: d = 64, M = 16)
   LH_CHECK_HIP(hipGetLastError());
   *qslack_out = qslack; *seg_val_out = seg_val; *seg_scale_out = reinterpret_cast<float *>(prm2);
   return LANCE_HIP_OK;
 }
 
 // The bound pass of a batch the matrix-core scan serves (search_pm.hip).  pair_starts0 / pair_idx0: the nq (query, nearest partition) pairs
-// grouped by partition.  -1: not taken (the caller runs the integer pass); otherwise a status code.
-int msbound_launch(lance_hip_ctx *ctx, const lance_hip_index *ix_c, const float *qs, uint32_t nq, uint32_t keff, const uint32_t *pair_starts0,
+// grouped by partition.  Only for a plan with bound == BOUND_MATRIX (search_plan.h).
+int msbound_launch(lance_hip_ctx *ctx, const lance_hip_index *ix, const float *qs, uint32_t nq, uint32_t keff, const uint32_t *pair_starts0,
                    const uint32_t *pair_idx0, uint32_t *item_start, int4 *desc, uint32_t max_items, uint32_t *tglobal, const uint32_t *allow,
                    uint32_t nb) {
-  static const bool off = getenv("LANCE_HIP_NO_MSBOUND") != nullptr;      // A/B switch: the integer histogram pass (search_q.hip)
-  lance_hip_index *ix = const_cast<lance_hip_index *>(ix_c);
-  int sd = 0, ks = 0;
-  const bool dot = ix->metric == LANCE_HIP_DOT;
-  // u16 bins: a bin never holds more rows than the partition has (L2: larger lists keep the integer pass; dot: the kernel counts the first 65,535 rows)
-  if (off || !ms_shape(ix, &sd, &ks) || !ix->cb_mean || (!dot && ix->max_part >= 65536u)) return LH_NOT_TAKEN;
-  if (((reinterpret_cast<uintptr_t>(qs) | reinterpret_cast<uintptr_t>(ix->centroids)) & 7) != 0) return LH_NOT_TAKEN;
-  LH_TRY(mscan_prepare(ctx, ix));
-  if (!ix->ms->usable) return LH_NOT_TAKEN;
-  const int nlist = (int)ix->nlist;
+  LH_REQUIRE(ms_shape(ix->d, ix->m) && ix->cb_mean && ix->ms && ix->ms->usable, "matrix-core bound pass: planned for an index without its constants (d=%u, m=%u)", ix->d, ix->m);
+  const int nlist = (int)ix->nlist, sd = (int)(ix->d / ix->m), ks = (int)ix->d / 16;
   LH_TRY(qscan_items(ctx, pair_starts0, nlist, MSB_BQ, item_start, desc, max_items));
-  if (!((sd == 8 && ks == 8) || (sd == 4 && (ks == 8 || ks == 4)))) return LH_NOT_TAKEN;      // before the stage is counted
   ScopedTimer t(ctx, "ivfpq_msbound");      // the launch under its own name: tests assert which bound pass ran
   MsBoundArgs a;
   a.q = qs; a.centroids = ix->centroids; a.cb_mean = ix->cb_mean; a.pair_idx0 = pair_idx0; a.item_start = item_start; a.desc = desc;
@@ -1210,14 +1154,6 @@ int msbound_launch(lance_hip_ctx *ctx, const lance_hip_index *ix_c, const float 
   else hipLaunchKernelGGL((ms_bound_kernel<4, 4>), dim3(grid), dim3(1024), 0, ctx->stream, a);
   LH_CHECK_HIP(hipGetLastError());
   return LANCE_HIP_OK;
-}
-
-int mscan_prewarm(lance_hip_ctx *ctx, const lance_hip_index *ix_c) {
-  lance_hip_index *ix = const_cast<lance_hip_index *>(ix_c);
-  static const bool off = getenv("LANCE_HIP_NO_MSCAN") != nullptr;
-  if (off || !ms_shape(ix, nullptr, nullptr) || !ix->model_finite) return LANCE_HIP_OK;
-  if (ix->metric == LANCE_HIP_DOT && (!ms_dot_skew_ok(ix) || getenv("LANCE_HIP_NO_DOT_FLOW"))) return LANCE_HIP_OK;      // the index will not take the flow: no constants
-  return mscan_prepare(ctx, ix);
 }
 
 void mscan_cut_params(int *cut_shift, uint32_t *cut_slack) { *cut_shift = MS_CUT_SHIFT; *cut_slack = 2u; }

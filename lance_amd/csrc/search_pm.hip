@@ -568,21 +568,7 @@ static bool launch_pm_sd(lance_hip_ctx *ctx, const PmArgs &a, int sd, unsigned g
   return false;
 }
 
-// A/B switches, read once per process
-static bool pm_nobound() { static const bool v = getenv("LANCE_HIP_PM_NOBOUND") != nullptr; return v; }
-
-bool pm_supported(const lance_hip_index *ix, uint32_t keff, int has_range, uint32_t nq, uint32_t nprobes) {
-  const int d = (int)ix->d, m = (int)ix->m;
-  if (ix->nbits != 8 || has_range || keff > (uint32_t)SCAN_MAX_KEFF) return false;
-  if (m == 0 || d % m != 0) return false;
-  const int sd = d / m;
-  if (sd != 4 && sd != 8 && sd != 16) return false;
-  if ((reinterpret_cast<uintptr_t>(ix->codebook) & 15) || (reinterpret_cast<uintptr_t>(ix->codes) & 15)) return false;
-  if (qscan_tiled_shape(m, sd))    // M = 48 / 64 / 96: only the quantised flow exists (the exact pair table would not fit in LDS)
-    return !pm_nobound() && qscan_supported(ix, nq, nprobes);
-  if (m % 16 != 0 || m / 16 > 2) return false;
-  return true;
-}
+static_assert(PLAN_MAX_KEFF == SCAN_MAX_KEFF && PLAN_SEG_CAP == QSCAN_SEG_CAP, "search_plan.h mirrors the kernels' constants");
 
 static size_t pm_lds_base(int d, int m) {
   const int dpad = (d + 3) & ~3;
@@ -596,7 +582,7 @@ static size_t pm_lds_base(int d, int m) {
 // Quantised flow (L2 / cosine): exact bound pass over every query's nearest partition -> 4-query integer filter scan of all
 // probed partitions (search_q.hip) -> exact re-evaluation of the survivors + (dist, rowid) selection.  Queries whose bound
 // pass found fewer than keff rows have no bound: they go through the exact pair kernel (class B) and its pool.
-static int ivfpq_scan_merge_q(lance_hip_ctx *ctx, const lance_hip_index *ix, const float *qs, uint32_t nq, const uint32_t *probes,
+static int ivfpq_scan_merge_q(lance_hip_ctx *ctx, const lance_hip_index *ix, const IvfpqPlan &plan, const float *qs, uint32_t nq, const uint32_t *probes,
                               uint32_t nprobes, uint32_t keff, uint32_t k, bool do_refine, uint64_t *ids, float *dists,
                               uint64_t *cand_rid, uint32_t *cand_cnt, uint32_t *flags, const uint32_t *allow) {
   const int d = (int)ix->d, m = (int)ix->m, sd = d / m, nlist = (int)ix->nlist;
@@ -609,17 +595,7 @@ static int ivfpq_scan_merge_q(lance_hip_ctx *ctx, const lance_hip_index *ix, con
   uint32_t *item_start = ctx->scratch_t<uint32_t>("pm.item_start", (size_t)2 * nlist + 1);
   int4 *desc = ctx->scratch_t<int4>("pm.desc", max_items2);
   uint32_t *pair_starts0 = ctx->scratch_t<uint32_t>("q.pair_starts0", (size_t)nlist + 1);
-  // dot: the bound pass runs over each query's THREE nearest lists and keeps the smallest bound -- without residuals the list a query's best rows sit in
-  // is often not the one with the largest centroid score, and the nearest list's k*refine-th distance then lets hundreds of that list's rows through.
-  // C2 shape, ms per 10,000-query batch with 1 / 2 / 3 / 4 lists (gpurun r06zzf, r06zzg): unit-normalised rows 0.951 / 0.854 / 0.860 / 0.867 (overflowed
-  // segments 5,311 -> 2,852 with two), centred rows 1.150 / 0.911 / 0.900 / 0.910, SIFT-like rows as they are (largest list 82,424 of 10^6 rows) 3.94 / 2.29 /
-  // 1.88 against 3.46 on the exact pair scan.  LANCE_HIP_DOT_BOUND_LISTS: A/B
-  static const uint32_t dot_nb_env = getenv("LANCE_HIP_DOT_BOUND_LISTS") ? (uint32_t)std::max(1, atoi(getenv("LANCE_HIP_DOT_BOUND_LISTS"))) : 3u;
-  // L2 / cosine: LANCE_HIP_BOUND_LISTS = 2 .. 4 is an A/B switch (one list by default); only batches whose bound pass runs on the matrix cores take it
-  static const uint32_t l2_nb_env = getenv("LANCE_HIP_BOUND_LISTS") ? (uint32_t)std::max(1, atoi(getenv("LANCE_HIP_BOUND_LISTS"))) : 1u;
-  static const bool no_msbound_env = getenv("LANCE_HIP_NO_MSBOUND") != nullptr || getenv("LANCE_HIP_EXACT_BOUND") != nullptr;
-  const uint32_t l2_nb = (!no_msbound_env && l2_nb_env > 1 && mscan_supported(ix, nq, nprobes) && qscan_pt_mode(ix) != 2) ? l2_nb_env : 1u;
-  const uint32_t nb0 = std::min<uint32_t>(std::min<uint32_t>(ix->metric == LANCE_HIP_DOT ? dot_nb_env : l2_nb, 4u), nprobes);
+  const uint32_t nb0 = plan.bound_lists;
   const uint32_t max_items0 = (uint32_t)((size_t)nq * nb0 / 2 + nlist + 2);
   uint32_t *pair_idx0 = ctx->scratch_t<uint32_t>("q.pair_idx0", (size_t)nq * nb0);
   uint32_t *item_start0 = ctx->scratch_t<uint32_t>("q.item_start0", (size_t)nlist + 1);
@@ -629,13 +605,7 @@ static int ivfpq_scan_merge_q(lance_hip_ctx *ctx, const lance_hip_index *ix, con
   uint32_t *tglobal = ctx->scratch_t<uint32_t>("pm.tglobal", (size_t)nq * 4);
   uint32_t *seg_cnt = ctx->scratch_t<uint32_t>("q.seg_cnt", npairs);
   uint32_t *seg_pos = ctx->scratch_t<uint32_t>("q.seg_pos", npairs * QSCAN_SEG_CAP);
-  // tiled shapes (M >= 48) have no exact pair kernel: EVERY segment of a query without a bound goes through the rescan kernel and
-  // publishes ~keff rows to the pool, so the pool follows nprobes there (nprobes = 100 with refine 10 overflowed the
-  // 8192-entry pool of every such query and sent it to the query-major replay), within 1 GiB of scratch
-  uint64_t pool_max = qscan_tiled_shape(m, sd) ? 65536 : 8192;
-  while (pool_max > 8192 && (uint64_t)nq * pool_max * 8 > (1ull << 30)) pool_max /= 2;
-  int pool_cap = (int)std::min<uint64_t>(pool_max, std::max<uint64_t>(512, (uint64_t)nprobes * (keff + 28)));
-  pool_cap = (pool_cap + 255) & ~255;
+  const int pool_cap = plan.pool_cap;
   uint32_t *pool_key = ctx->scratch_t<uint32_t>("pm.pool_key", (size_t)nq * pool_cap);
   uint32_t *pool_pos = ctx->scratch_t<uint32_t>("pm.pool_pos", (size_t)nq * pool_cap);
   if (!keys || !pair_starts || !pair_idx || !item_start || !desc || !pair_starts0 || !pair_idx0 || !item_start0 || !desc0 || !item_start4 ||
@@ -647,15 +617,13 @@ static int ivfpq_scan_merge_q(lance_hip_ctx *ctx, const lance_hip_index *ix, con
   a.q = qs; a.probes = probes;
   a.centroids = ix->centroids; a.codebook = ix->codebook; a.part_offsets = ix->part_offsets; a.codes = ix->codes;
   a.d = d; a.m = m; a.nprobes = (int)nprobes; a.nlist = nlist; a.keff = (int)keff;
-  const bool dot = ix->metric == LANCE_HIP_DOT;      // (qscan_supported: only batches the matrix-core bound pass + scan serve)
+  const bool dot = ix->metric == LANCE_HIP_DOT;      // (the plan: only batches the matrix-core bound pass + scan serve)
   a.residual = dot ? 0 : 1;
   a.round_f16 = ix->dtype == LANCE_HIP_F16 ? 1 : 0;
   a.prof = nullptr;
   a.tglobal = tglobal; a.pool_key = pool_key; a.pool_pos = pool_pos; a.pool_cnt = pool_cnt; a.pool_cap = pool_cap; a.flags = flags;
   a.unbounded = 0; a.loop = 0; a.allow = allow;
-  const bool tiled = qscan_tiled_shape(m, sd);
-  static const bool exact_bound_env = getenv("LANCE_HIP_EXACT_BOUND") != nullptr;
-  const bool exact_bound = exact_bound_env && !tiled && !dot;   // the exact pair kernel has no M > 32 instantiation
+  const bool exact_bound = plan.bound == BOUND_EXACT_PAIR;
   {
     // bound pass: the nq (query, nearest partition) pairs grouped by partition
     ScopedTimer t(ctx, "pm_group");
@@ -674,20 +642,17 @@ static int ivfpq_scan_merge_q(lance_hip_ctx *ctx, const lance_hip_index *ix, con
     const size_t lds = pm_lds_base(d, m) + (size_t)PM_CAP_BOUND * 16;
     const bool ok = launch_pm_sd<METRIC_L2>(ctx, a, sd, (unsigned)(nq / 2 + nlist + 1), lds);
     LH_REQUIRE(ok, "partition-major scan: unsupported shape (m=%d, sd=%d)", m, sd);
-  } else if (!dot && qscan_pt_mode(ix) == 2) {   // per-query tables built before the bound pass and shared with the main pass (search_qt.hip)
-    ScopedTimer t(ctx, "ivfpq_scan_c0");
-    LH_TRY(qbound_pt_launch(ctx, ix, qs, nq, nprobes, keff, probes, pair_starts0, pair_idx0, item_start0, desc0, (uint32_t)(nq / 4 + nlist + 2), tglobal,
-                            allow));
   } else {
     ScopedTimer t(ctx, "ivfpq_scan_c0");
+    // per-query tables built before the bound pass and shared with the main pass (search_qt.hip)
+    if (plan.bound == BOUND_PT)
+      LH_TRY(qbound_pt_launch(ctx, ix, qs, nq, nprobes, keff, probes, pair_starts0, pair_idx0, item_start0, desc0, (uint32_t)(nq / 4 + nlist + 2), tglobal, allow));
     // a batch the matrix-core scan serves gets its bounds from the same matrix product (search_ms.hip: ms_bound_kernel) ...
-    int mb_rc = LH_NOT_TAKEN;
-    if (mscan_supported(ix, nq, nprobes))
-      mb_rc = msbound_launch(ctx, ix, qs, nq, keff, pair_starts0, pair_idx0, item_start0, desc0, (uint32_t)((size_t)nq * nb0 / 4 + nlist + 2), tglobal, allow, nb0);
-    if (mb_rc < 0) return mb_rc;          // a real failure (every LANCE_HIP_E* code is negative): never a silent fall-back
-    if (mb_rc == LH_NOT_TAKEN && dot) return LH_NOT_TAKEN;      // no integer pass for dot: the caller runs the exact pair scan (nothing but scratch was written)
+    else if (plan.bound == BOUND_MATRIX)
+      LH_TRY(msbound_launch(ctx, ix, qs, nq, keff, pair_starts0, pair_idx0, item_start0, desc0, (uint32_t)((size_t)nq * nb0 / 4 + nlist + 2), tglobal, allow, nb0));
     // ... every other one from the integer histogram, four queries per gather (search_q.hip)
-    if (mb_rc == LH_NOT_TAKEN) LH_TRY(qbound_launch(ctx, ix, qs, nq, keff, pair_starts0, pair_idx0, item_start0, desc0, (uint32_t)(nq / 4 + nlist + 2), tglobal, allow));
+    else
+      LH_TRY(qbound_launch(ctx, ix, qs, nq, keff, pair_starts0, pair_idx0, item_start0, desc0, (uint32_t)(nq / 4 + nlist + 2), tglobal, allow));
   }
   {
     // main pass grouping: class A (bounded) pairs by partition for the filter scan, class B for the exact pair kernel
@@ -701,15 +666,10 @@ static int ivfpq_scan_merge_q(lance_hip_ctx *ctx, const lance_hip_index *ix, con
   // search_ms.hip: the filter as a matrix product per partition (its own pre-pass; same segment outputs + a per-query slack for the merge cut)
   uint32_t *qslack = nullptr;
   float *seg_val = nullptr, *seg_scale = nullptr;      // rows-on-lanes kernel: the survivors' accumulator values + the per-pair scale of their sums
-  int ms_rc = LH_NOT_TAKEN;
-  if (mscan_supported(ix, nq, nprobes))
-    ms_rc = mscan_launch(ctx, ix, qs, nq, nprobes, probes, pair_starts, pair_idx, tbound, seg_cnt, seg_pos, qovf, allow, &qslack, &seg_val, &seg_scale);
-  if (ms_rc < 0) return ms_rc;
-  if (ms_rc == LH_NOT_TAKEN && dot) return LH_NOT_TAKEN;
-  if (ms_rc == LH_NOT_TAKEN) {
-    qslack = nullptr; seg_val = nullptr; seg_scale = nullptr;
-    LH_TRY(qscan_launch(ctx, ix, qs, nq, nprobes, pair_idx, item_start4, desc4, max_items4, tbound, seg_cnt, seg_pos, qovf, allow, probes));
-  }
+  if (plan.main == MAIN_MATRIX)
+    LH_TRY(mscan_launch(ctx, ix, qs, nq, nprobes, probes, pair_starts, pair_idx, tbound, seg_cnt, seg_pos, qovf, allow, &qslack, &seg_val, &seg_scale));
+  else
+    LH_TRY(qscan_launch(ctx, ix, qs, nq, nprobes, pair_idx, item_start4, desc4, max_items4, tbound, seg_cnt, seg_pos, qovf, allow, probes, plan));
   static const bool q_stats = getenv("LANCE_HIP_Q_STATS") != nullptr;
   if (q_stats) {   // diagnosis: how many rows survive the integer filter
     std::vector<uint32_t> sc(npairs), tb(nq);
@@ -719,10 +679,11 @@ static int ivfpq_scan_merge_q(lance_hip_ctx *ctx, const lance_hip_index *ix, con
     uint64_t tot = 0, ovf = 0, mx = 0, nb = 0, r0 = 0;
     for (size_t i = 0; i < npairs; ++i) { tot += std::min<uint32_t>(sc[i], QSCAN_SEG_CAP); ovf += sc[i] > (uint32_t)QSCAN_SEG_CAP; mx = std::max<uint64_t>(mx, sc[i]); if (i % nprobes == 0) r0 += sc[i]; }
     for (uint32_t i = 0; i < nq; ++i) nb += tb[i] == 0xFFFFFFFFu;
-    fprintf(stderr, "[qscan] nq=%u nprobes=%u keff=%u survivors/query %.1f (nearest partition %.1f) max segment %llu overflowed segments %llu class-B queries %llu\n",
-            nq, nprobes, keff, (double)tot / nq, (double)r0 / nq, (unsigned long long)mx, (unsigned long long)ovf, (unsigned long long)nb);
+    fprintf(stderr, "[qscan] nq=%u nprobes=%u keff=%u survivors/query %.1f (nearest partition %.1f) max segment %llu overflowed segments %llu class-B queries %llu | plan: bound %d x %u lists, main %d%s%s\n",
+            nq, nprobes, keff, (double)tot / nq, (double)r0 / nq, (unsigned long long)mx, (unsigned long long)ovf, (unsigned long long)nb,
+            (int)plan.bound, plan.bound_lists, (int)plan.main, plan.why[0] ? ": " : "", plan.why);
   }
-  if (tiled) {   // no exact pair kernel at these sizes: class-B queries are scanned by the rescan kernel (exact f32 table)
+  if (plan.class_b == CLASSB_RESCAN) {   // no exact pair kernel at these sizes: class-B queries are scanned by the rescan kernel (exact f32 table)
     ScopedTimer t(ctx, "ivfpq_scan_cb");
     LH_TRY(qscan_classb_to_rescan(ctx, tbound, nq, nprobes, seg_cnt, qovf));
   } else {
@@ -740,30 +701,27 @@ static int ivfpq_scan_merge_q(lance_hip_ctx *ctx, const lance_hip_index *ix, con
     o.out_ids = ids; o.out_dists = dists; o.cand_rid = cand_rid; o.cand_cnt = cand_cnt; o.flags = flags;
     o.part_offsets = ix->part_offsets; o.nlist = nlist;
     ScopedTimer t(ctx, "ivfpq_merge");
-    LH_TRY(qmerge_launch(ctx, ix, qs, nq, probes, nprobes, tbound, tglobal, seg_cnt, seg_pos, qovf, pool_key, pool_pos, pool_cnt, pool_cap, o, allow, qslack, seg_val, seg_scale));
+    LH_TRY(qmerge_launch(ctx, ix, qs, nq, probes, nprobes, tbound, tglobal, seg_cnt, seg_pos, qovf, pool_key, pool_pos, pool_cnt, pool_cap, o, allow, plan.main, qslack, seg_val, seg_scale));
   }
   LH_CHECK_HIP(hipGetLastError());
   return LANCE_HIP_OK;
 }
 
 // scan + merge for the whole batch; outputs as the query-major path (ids/dists or refine candidates)
-int ivfpq_scan_merge_pm(lance_hip_ctx *ctx, const lance_hip_index *ix, const float *qs, uint32_t nq, const uint32_t *probes,
+int ivfpq_scan_merge_pm(lance_hip_ctx *ctx, const lance_hip_index *ix, const IvfpqPlan &plan, const float *qs, uint32_t nq, const uint32_t *probes,
                         uint32_t nprobes, uint32_t keff, uint32_t k, bool do_refine, uint64_t *ids, float *dists,
                         uint64_t *cand_rid, uint32_t *cand_cnt, uint32_t *flags, const uint32_t *allow) {
   const int d = (int)ix->d, m = (int)ix->m, sd = d / m, nlist = (int)ix->nlist;
   const int scan_metric = ix->metric == LANCE_HIP_COSINE ? LANCE_HIP_L2 : ix->metric;
-  if (!pm_nobound() && qscan_supported(ix, nq, nprobes)) {
-    const int rc = ivfpq_scan_merge_q(ctx, ix, qs, nq, probes, nprobes, keff, k, do_refine, ids, dists, cand_rid, cand_cnt, flags, allow);
-    if (rc != LH_NOT_TAKEN) return rc;      // (dot: the matrix-core passes did not take the batch after all -- the exact pair scan below)
-  }
+  if (plan.route == ROUTE_QUANTISED)
+    return ivfpq_scan_merge_q(ctx, ix, plan, qs, nq, probes, nprobes, keff, k, do_refine, ids, dists, cand_rid, cand_cnt, flags, allow);
+  LH_REQUIRE(plan.route == ROUTE_PAIR_SCAN, "partition-major scan: called with a query-major plan");
   const size_t npairs = (size_t)nq * nprobes;
   uint32_t *pair_starts = ctx->scratch_t<uint32_t>("pm.pair_starts", (size_t)2 * nlist + 1);
   uint32_t *pair_idx = ctx->scratch_t<uint32_t>("pm.pair_idx", npairs);
   uint32_t *item_start = ctx->scratch_t<uint32_t>("pm.item_start", (size_t)2 * nlist + 1);
   uint32_t *tglobal = ctx->scratch_t<uint32_t>("pm.tglobal", (size_t)nq * 2);
-  // every (query, partition) publishes at most ~keff (+ ties) rows, usually far fewer once Tglobal is tight
-  int pool_cap = (int)std::min<uint64_t>(8192, std::max<uint64_t>(512, (uint64_t)nprobes * (keff + 28)));
-  pool_cap = (pool_cap + 255) & ~255;
+  const int pool_cap = plan.pool_cap;
   uint32_t *pool_key = ctx->scratch_t<uint32_t>("pm.pool_key", (size_t)nq * pool_cap);
   uint32_t *pool_pos = ctx->scratch_t<uint32_t>("pm.pool_pos", (size_t)nq * pool_cap);
   if (!pair_starts || !pair_idx || !item_start || !tglobal || !pool_key || !pool_pos) return LANCE_HIP_ENOMEM;
@@ -801,7 +759,7 @@ int ivfpq_scan_merge_pm(lance_hip_ctx *ctx, const lance_hip_index *ix, const flo
   {
     // pass 0 (bound): every query's nearest partition is streamed once to seed Tglobal[q]; pass 1 (main): all
     // (query, probe) pairs, nearest partition included, prune with that bound from their first row.
-    const bool nobound = pm_nobound();
+    const bool nobound = !plan.pair_bound_pass;
     for (int pass = 0; pass < 2; ++pass) {
       if (nobound && pass == 1 && nprobes == 1) break;
       ScopedTimer t(ctx, pass == 0 ? "ivfpq_scan_c0" : "ivfpq_scan_c1");
@@ -811,16 +769,7 @@ int ivfpq_scan_merge_pm(lance_hip_ctx *ctx, const lance_hip_index *ix, const flo
       // upper bound of sum ceil(c_vp / 2) over the covered virtual partitions; surplus workgroups exit at once
       const size_t cpairs = a.cls == 0 ? (size_t)nq : (a.cls == 1 ? (size_t)nq * (nprobes - 1) : (size_t)nq * nprobes);
       const unsigned grid = (unsigned)(cpairs / 2 + (a.cls == 2 ? 2 : 1) * nlist + 1);
-      bool ok = false;
-      if (scan_metric == LANCE_HIP_DOT) {
-        if (sd == 4) ok = launch_pm_mu<4, METRIC_DOT>(ctx, a, grid, lds);
-        else if (sd == 8) ok = launch_pm_mu<8, METRIC_DOT>(ctx, a, grid, lds);
-        else if (sd == 16) ok = launch_pm_mu<16, METRIC_DOT>(ctx, a, grid, lds);
-      } else {
-        if (sd == 4) ok = launch_pm_mu<4, METRIC_L2>(ctx, a, grid, lds);
-        else if (sd == 8) ok = launch_pm_mu<8, METRIC_L2>(ctx, a, grid, lds);
-        else if (sd == 16) ok = launch_pm_mu<16, METRIC_L2>(ctx, a, grid, lds);
-      }
+      const bool ok = scan_metric == LANCE_HIP_DOT ? launch_pm_sd<METRIC_DOT>(ctx, a, sd, grid, lds) : launch_pm_sd<METRIC_L2>(ctx, a, sd, grid, lds);
       LH_REQUIRE(ok, "partition-major scan: unsupported shape (m=%d, sd=%d)", m, sd);
       if (a.prof && pass == 1) {
         unsigned long long h[8];

@@ -1108,26 +1108,7 @@ __global__ LH_QM_BOUNDS(BS) void ivfpq_qmerge1g_kernel(QmergeArgs a) {
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------
-bool qscan_supported(const lance_hip_index *ix, uint32_t nq, uint32_t nprobes) {
-  static const bool off = getenv("LANCE_HIP_NO_QSCAN") != nullptr;
-  if (off || !ix->model_finite) return false;      // NaN / infinite centroids or codewords: the exact kernels decide (index.h)
-  const int scan_metric = ix->metric == LANCE_HIP_COSINE ? LANCE_HIP_L2 : ix->metric;
-  // the integer tables need entries >= 0 (squared L2); the dot metric has a quantised flow where the matrix-core scan and its bound pass
-  // serve the batch (search_ms.hip: limits and sums relative to a per-query base distance) -- every other dot batch keeps the exact pair scan
-  if (scan_metric == LANCE_HIP_DOT) { if (!mscan_dot_ready(ix, nq, nprobes)) return false; }
-  else if (scan_metric != LANCE_HIP_L2) return false;
-  {
-    const int m = (int)ix->m, sd = (int)(ix->d / ix->m);
-    if (!((m == 16 || m == 32) && (sd == 4 || sd == 8 || sd == 16)) && !qscan_tiled_shape(m, sd)) return false;
-  }
-  if ((uint64_t)nq * nprobes * Q_CAP * 4 > (2ull << 30)) return false;   // survivor segments: at most 2 GiB of scratch
-  // item residuals likewise -- where the main pass reads them: neither the per-query-table filter (search_qt.hip) nor the matrix-core
-  // scan (search_ms.hip) does.  (This check used to apply to both: a 10,000-query batch at nprobes = 50 on the C3 shape fell back to the
-  // query-major kernel, 62 ms instead of ~6: gpurun r04v.)
-  const bool needs_rq = !qscan_pt_enabled(ix) && !mscan_batch_shape(ix, nq, nprobes);
-  if (needs_rq && ((uint64_t)nq * nprobes / Q_G + ix->nlist + 1) * ix->d * 16 > (2ull << 30)) return false;
-  return true;
-}
+static_assert(PLAN_Q_G == Q_G && PLAN_SEG_CAP == Q_CAP, "search_plan.h mirrors the kernels' constants");
 
 size_t qscan_lds_bytes(int d, int m) {   // dynamic part (the quantised LUT is static LDS)
   (void)d; (void)m;
@@ -1147,13 +1128,6 @@ int qscan_group(lance_hip_ctx *ctx, const uint32_t *probes, uint32_t nq, uint32_
   return LANCE_HIP_OK;
 }
 
-// item_start / desc of the (partition, G queries) items of a grouping (used by the bound passes)
-int qscan_item_tables(lance_hip_ctx *ctx, const uint32_t *pair_starts, int nlist, int G, uint32_t *item_start, int4 *desc, uint32_t max_items) {
-  hipLaunchKernelGGL(q_item_table_kernel, dim3(1), dim3(256), 0, ctx->stream, pair_starts, nlist, G, item_start);
-  hipLaunchKernelGGL(q_item_desc_kernel, dim3((unsigned)cdiv(max_items, 256)), dim3(256), 0, ctx->stream, item_start, pair_starts, nlist, G, max_items, desc);
-  return LANCE_HIP_OK;
-}
-
 int qscan_nearest_keys(lance_hip_ctx *ctx, const uint32_t *probes, uint32_t nq, uint32_t nprobes, uint32_t *keys, uint32_t nb) {
   hipLaunchKernelGGL(q_nearest_keys_kernel, dim3((unsigned)cdiv((uint64_t)nq * nb, 256)), dim3(256), 0, ctx->stream, probes, (int)nq, (int)nprobes, (int)nb, keys);
   return LANCE_HIP_OK;
@@ -1168,9 +1142,9 @@ static bool launch_qscan_sd(lance_hip_ctx *ctx, const QscanArgs &a, int m, unsig
 
 int qscan_launch(lance_hip_ctx *ctx, const lance_hip_index *ix, const float *qs, uint32_t nq, uint32_t nprobes, const uint32_t *pair_idx,
                  const uint32_t *item_start4, const int4 *desc4, uint32_t max_items4, const uint32_t *tbound, uint32_t *seg_cnt,
-                 uint32_t *seg_pos, uint32_t *qovf, const uint32_t *allow, const uint32_t *probes) {
+                 uint32_t *seg_pos, uint32_t *qovf, const uint32_t *allow, const uint32_t *probes, const IvfpqPlan &plan) {
   const int d = (int)ix->d, m = (int)ix->m, sd = d / m;
-  const bool pt = probes != nullptr && qscan_pt_enabled(ix);   // per-query tables: no residual pre-pass, no table build in the scan
+  const bool pt = plan.main == MAIN_PT;   // per-query tables: no residual pre-pass, no table build in the scan
   f4 *rq = pt ? nullptr : reinterpret_cast<f4 *>(ctx->scratch_t<float>("qscan.rq", (size_t)max_items4 * d * 4));
   if (!pt && !rq) return LANCE_HIP_ENOMEM;
   {
@@ -1196,13 +1170,13 @@ int qscan_launch(lance_hip_ctx *ctx, const lance_hip_index *ix, const float *qs,
   bool ok = false;
 #ifdef LH_QT_PROF
   static const bool qt_prof = getenv("LANCE_HIP_QT_PROF") != nullptr;
-  if (qt_prof && qscan_tiled_shape(m, sd)) {
+  if (qt_prof && plan.main != MAIN_INTEGER) {
     a.prof = ctx->scratch_t<unsigned long long>("qt.prof", 8);
     if (a.prof) (void)lh::memset_async(a.prof, 0, 64, ctx->stream);
   }
 #endif
-  if (pt) { LH_TRY(qscan_pt_launch(ctx, ix, a, qs, nq, probes, grid)); ok = true; }
-  else if (qscan_tiled_shape(m, sd)) ok = qscan_tiled_launch(ctx, a, m, sd, grid);
+  if (pt) { LH_TRY(qscan_pt_launch(ctx, ix, a, qs, nq, probes, grid, plan.bound == BOUND_PT)); ok = true; }
+  else if (plan.main == MAIN_TILED) ok = qscan_tiled_launch(ctx, a, m, sd, grid);
   else if (sd == 4) ok = launch_qscan_sd<4>(ctx, a, m, grid, lds);
   else if (sd == 8) ok = launch_qscan_sd<8>(ctx, a, m, grid, lds);
   else if (sd == 16) ok = launch_qscan_sd<16>(ctx, a, m, grid, lds);
@@ -1279,9 +1253,7 @@ int qscan_items(lance_hip_ctx *ctx, const uint32_t *pair_starts, int nvp, int G,
 int qbound_launch(lance_hip_ctx *ctx, const lance_hip_index *ix, const float *qs, uint32_t nq, uint32_t keff, const uint32_t *pair_starts0,
                   const uint32_t *pair_idx0, uint32_t *item_start, int4 *desc, uint32_t max_items, uint32_t *tglobal, const uint32_t *allow) {
   const int d = (int)ix->d, m = (int)ix->m, sd = d / m, nlist = (int)ix->nlist;
-  hipLaunchKernelGGL(q_item_table_kernel, dim3(1), dim3(256), 0, ctx->stream, pair_starts0, nlist, Q_G, item_start);
-  hipLaunchKernelGGL(q_item_desc_kernel, dim3((unsigned)cdiv(max_items, 256)), dim3(256), 0, ctx->stream, item_start, pair_starts0, nlist, Q_G,
-                     max_items, desc);
+  LH_TRY(qscan_items(ctx, pair_starts0, nlist, Q_G, item_start, desc, max_items));
   f4 *rq = reinterpret_cast<f4 *>(ctx->scratch_t<float>("qbound.rq", (size_t)max_items * d * 4));
   if (!rq) return LANCE_HIP_ENOMEM;
   hipLaunchKernelGGL(q_residual_kernel, dim3((unsigned)cdiv(max_items, 4)), dim3(256), 0, ctx->stream, qs, pair_idx0, item_start, desc, ix->centroids, d,
@@ -1325,10 +1297,18 @@ static void launch_qmerge_mu(lance_hip_ctx *ctx, const QmergeArgs &a, unsigned n
   else hipLaunchKernelGGL((ivfpq_qmerge_kernel<SD, MU, 128, DOT>), dim3(nq), dim3(128), lds, ctx->stream, a);
 }
 
+template <int MU>
+static bool launch_qmerge_sd(lance_hip_ctx *ctx, const QmergeArgs &a, int sd, unsigned nq, int bs) {
+  if (sd == 4) launch_qmerge_mu<4, MU>(ctx, a, nq, bs);
+  else if (sd == 8) launch_qmerge_mu<8, MU>(ctx, a, nq, bs);
+  else if (sd == 16) launch_qmerge_mu<16, MU>(ctx, a, nq, bs);
+  return sd == 4 || sd == 8 || sd == 16;
+}
+
 int qmerge_launch(lance_hip_ctx *ctx, const lance_hip_index *ix, const float *qs, uint32_t nq, const uint32_t *probes, uint32_t nprobes,
                   const uint32_t *tbound, uint32_t *tglobal, const uint32_t *seg_cnt, const uint32_t *seg_pos, const uint32_t *qovf,
                   uint32_t *pool_key, uint32_t *pool_pos, uint32_t *pool_cnt, int pool_cap, const SelectOut &o, const uint32_t *allow,
-                  const uint32_t *qslack, const float *seg_val, const float *seg_scale) {
+                  PlanMain main, const uint32_t *qslack, const float *seg_val, const float *seg_scale) {
   const int d = (int)ix->d, m = (int)ix->m, sd = d / m;
   QmergeArgs a;
   a.qslack = qslack; a.seg_val = seg_val; a.seg_pv = reinterpret_cast<const uint2 *>(seg_val); a.seg_scale = reinterpret_cast<const f2 *>(seg_scale);
@@ -1362,48 +1342,24 @@ int qmerge_launch(lance_hip_ctx *ctx, const lance_hip_index *ix, const float *qs
     a.seg_sum = ctx->scratch_t<uint16_t>("q.seg_sum", (size_t)nq * nprobes * Q_CAP);
     a.ovf = ctx->scratch_t<uint32_t>("q.ovf", (size_t)nq * nprobes + 1);
     if (!a.seg_sum || !a.ovf) return LANCE_HIP_ENOMEM;
-    const bool tiled = qscan_tiled_shape(m, sd);
-    a.cut_shift = no_cut ? -1 : (tiled ? 7 : (m == 16 ? 3 : 2));
+    const bool tiled = main == MAIN_TILED || main == MAIN_PT;
+    int sh = tiled ? 7 : (m == 16 ? 3 : 2);
     a.cut_slack = tiled ? (uint32_t)(2 * m + 8) : (uint32_t)(2 * m + 4);
-    if (qslack) {   // search_ms.hip's sums: rint(dist~ * s) with |dist~ - dist| s <= qslack[q]; LIM ~ 30000 + slack -> bins of 64
-      int sh = 0; uint32_t sl = 0;
-      mscan_cut_params(&sh, &sl);
-      a.cut_shift = no_cut ? -1 : sh; a.cut_slack = sl;
-    }
+    if (main == MAIN_MATRIX) mscan_cut_params(&sh, &a.cut_slack);   // search_ms.hip's sums: rint(dist~ * s) with |dist~ - dist| s <= qslack[q]; LIM ~ 30000 + slack -> bins of 64
+    a.cut_shift = no_cut ? -1 : sh;
   }
   static const int bs = getenv("LANCE_HIP_QMERGE_BS") ? atoi(getenv("LANCE_HIP_QMERGE_BS")) : 128;
-  bool ok = true;
-  if (ix->metric == LANCE_HIP_DOT) {      // the dot flow exists for the matrix-core scan's shapes only (search_ms.hip: ms_shape)
-    if (m == 16 && sd == 4) launch_qmerge_mu<4, 1, true>(ctx, a, nq, bs);
-    else if (m == 16 && sd == 8) launch_qmerge_mu<8, 1, true>(ctx, a, nq, bs);
-    else if (m == 32 && sd == 4) launch_qmerge_mu<4, 2, true>(ctx, a, nq, bs);
-    else ok = false;
-  } else if (m == 16) {
-    if (sd == 4) launch_qmerge_mu<4, 1>(ctx, a, nq, bs);
-    else if (sd == 8) launch_qmerge_mu<8, 1>(ctx, a, nq, bs);
-    else if (sd == 16) launch_qmerge_mu<16, 1>(ctx, a, nq, bs);
-    else ok = false;
-  } else if (m == 32) {
-    if (sd == 4) launch_qmerge_mu<4, 2>(ctx, a, nq, bs);
-    else if (sd == 8) launch_qmerge_mu<8, 2>(ctx, a, nq, bs);
-    else if (sd == 16) launch_qmerge_mu<16, 2>(ctx, a, nq, bs);
-    else ok = false;
-  } else if (m == 48) {
-    if (sd == 4) launch_qmerge_mu<4, 3>(ctx, a, nq, bs);
-    else if (sd == 8) launch_qmerge_mu<8, 3>(ctx, a, nq, bs);
-    else if (sd == 16) launch_qmerge_mu<16, 3>(ctx, a, nq, bs);
-    else ok = false;
-  } else if (m == 64) {
-    if (sd == 4) launch_qmerge_mu<4, 4>(ctx, a, nq, bs);
-    else if (sd == 8) launch_qmerge_mu<8, 4>(ctx, a, nq, bs);
-    else if (sd == 16) launch_qmerge_mu<16, 4>(ctx, a, nq, bs);
-    else ok = false;
-  } else if (m == 96) {
-    if (sd == 4) launch_qmerge_mu<4, 6>(ctx, a, nq, bs);
-    else if (sd == 8) launch_qmerge_mu<8, 6>(ctx, a, nq, bs);
-    else if (sd == 16) launch_qmerge_mu<16, 6>(ctx, a, nq, bs);
-    else ok = false;
-  } else ok = false;
+  bool ok = false;
+  if (ix->metric == LANCE_HIP_DOT) {      // the dot flow exists for the matrix-core scan's shapes only (search_plan.h: ms_shape)
+    ok = ms_shape(ix->d, ix->m);      // (d, M) = (64, 16), (128, 16), (128, 32)
+    if (ok && m == 32) launch_qmerge_mu<4, 2, true>(ctx, a, nq, bs);
+    else if (ok && sd == 8) launch_qmerge_mu<8, 1, true>(ctx, a, nq, bs);
+    else if (ok) launch_qmerge_mu<4, 1, true>(ctx, a, nq, bs);
+  } else if (m == 16) ok = launch_qmerge_sd<1>(ctx, a, sd, nq, bs);
+  else if (m == 32) ok = launch_qmerge_sd<2>(ctx, a, sd, nq, bs);
+  else if (m == 48) ok = launch_qmerge_sd<3>(ctx, a, sd, nq, bs);
+  else if (m == 64) ok = launch_qmerge_sd<4>(ctx, a, sd, nq, bs);
+  else if (m == 96) ok = launch_qmerge_sd<6>(ctx, a, sd, nq, bs);
   LH_REQUIRE(ok, "quantised scan merge: unsupported shape (m=%d, sd=%d)", m, sd);
   return LANCE_HIP_OK;
 }

@@ -334,10 +334,6 @@ __global__ __launch_bounds__(256) void q_classb_to_rescan_kernel(const uint32_t 
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------
-bool qscan_tiled_shape(int m, int sd) {
-  return (m == 48 || m == 64 || m == 96) && (sd == 4 || sd == 8 || sd == 16);
-}
-
 template <int SD, int MU, int NT>
 static void launch_qscan_tiled(lance_hip_ctx *ctx, const QscanArgs &a, unsigned grid) {
   const size_t lds = (size_t)4 * Q_CAP * 4 + 8 * 4 + (size_t)4 * Q_CAP * 2;
@@ -681,22 +677,6 @@ __global__ __launch_bounds__(QT_BS) void ivfpq_qscan_tiled_pt_kernel(QscanArgs p
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------
-// 0: off; 1: tables after the bound pass (scale from T); 2: tables before the bound pass, shared by both passes
-static int qscan_pt_env() {
-  static const int mode = [] { const char *e = getenv("LANCE_HIP_QPT"); return e ? (e[0] == '2' ? 2 : (e[0] != '0' ? 1 : 0)) : 2; }();   // unset: mode 2 (r04g: C3 716 k -> 788 k q/s at nprobes 10, 348 k -> 508 k at 50)
-  return mode;
-}
-int qscan_pt_mode(const lance_hip_index *ix) { return qscan_pt_enabled(ix) ? qscan_pt_env() : 0; }
-
-bool qscan_pt_enabled(const lance_hip_index *ix) {
-  const bool on = qscan_pt_env() != 0;
-  if (!on || !ix || ix->m == 0 || ix->nbits != 8) return false;
-  const int m = (int)ix->m, sd = (int)(ix->d / ix->m);
-  if (!qscan_tiled_shape(m, sd)) return false;
-  if (ix->dtype == LANCE_HIP_F16) return false;      // the reference rounds the residual to f16 there: r is not q - cen any more
-  return ix->metric == LANCE_HIP_L2 || ix->metric == LANCE_HIP_COSINE;
-}
-
 static int qscan_pt_prepare(lance_hip_ctx *ctx, lance_hip_index *ix) {
   std::lock_guard<std::mutex> lk(ix->lazy_mu);   // the first search of any context builds the constants, the others wait for it
   if (ix->pt) return LANCE_HIP_OK;
@@ -942,7 +922,7 @@ int qbound_pt_launch(lance_hip_ctx *ctx, const lance_hip_index *ix_c, const floa
   hipLaunchKernelGGL(q_pt_prescale_kernel, dim3((unsigned)cdiv(nq, 256)), dim3(256), 0, ctx->stream, ix->pt->beta_min, ix->pt->beta_abs, ix->pt->beta_mean,
                      probes, (int)nq, (int)nprobes, sd + m, ix->cb_mean + d, kap, qn2, qmu, sq, theta, bslack);
   pt_launch_tables(ctx, ix, qs, nq, sq, tab);
-  LH_TRY(qscan_item_tables(ctx, pair_starts0, nlist, Q_G, item_start, desc, max_items));
+  LH_TRY(qscan_items(ctx, pair_starts0, nlist, Q_G, item_start, desc, max_items));
   QboundArgs a;
   a.rq = nullptr; a.pair_idx = pair_idx0; a.item_start = item_start; a.desc = desc;
   a.centroids = ix->centroids; a.codebook = ix->codebook; a.part_offsets = ix->part_offsets; a.codes = ix->codes;
@@ -959,8 +939,9 @@ int qbound_pt_launch(lance_hip_ctx *ctx, const lance_hip_index *ix_c, const floa
   return LANCE_HIP_OK;
 }
 
+// shared_tables: the plan's bound pass was BOUND_PT (qbound_pt_launch built the tables: LANCE_HIP_QPT=2); else they are built here from the bound T
 int qscan_pt_launch(lance_hip_ctx *ctx, const lance_hip_index *ix_c, const QscanArgs &a, const float *qs, uint32_t nq, const uint32_t *probes,
-                    unsigned grid) {
+                    unsigned grid, bool shared_tables) {
   lance_hip_index *ix = const_cast<lance_hip_index *>(ix_c);   // the constants are a cache attached to the index
   LH_TRY(qscan_pt_prepare(ctx, ix));
   const int d = (int)ix->d, m = (int)ix->m, sd = d / m, nprobes = a.nprobes;
@@ -971,7 +952,7 @@ int qscan_pt_launch(lance_hip_ctx *ctx, const lance_hip_index *ix_c, const Qscan
   uint16_t *tab = ctx->scratch_t<uint16_t>("pt.tab", (size_t)nq * m * 256);
   if (!qn2 || !sq || !kap || !pslack || !tab) return LANCE_HIP_ENOMEM;
   const int64_t npairs = (int64_t)nq * nprobes;
-  if (qscan_pt_mode(ix) == 2) {
+  if (shared_tables) {
     // the tables exist since the bound pass (qbound_pt_launch): only the per-pair slack with the actual T is left
     float *theta = ctx->scratch_t<float>("pt.theta", nq);
     if (!theta) return LANCE_HIP_ENOMEM;
