@@ -416,6 +416,43 @@ int lance_hip_ivfflat_search(lance_hip_ctx *ctx, const lance_hip_index *idx, con
 int lance_hip_ivfflat_search_filtered(lance_hip_ctx *ctx, const lance_hip_index *idx, const void *q, uint32_t nq, uint32_t k,
                                       uint32_t nprobes, const uint8_t *allow_by_rowid, uint64_t n_allow, uint64_t *ids, float *dists);
 
+/* ---- N6: 1-bit RaBitQ and IVF_RQ (lance-index/src/vector/bq/{builder,transform,storage}.rs, ivf.rs:281-326) ------------ */
+/* f32 columns, metric LANCE_HIP_L2 or LANCE_HIP_DOT (Cosine is refused), num_bits = 1, d a multiple of 8 up to
+ * LANCE_HIP_RQ_MAX_DIM.  rotation is the model's [d][d] f32 matrix P (row j is the j-th rotated axis), a DEVICE pointer like every
+ * other array here.  A code row is d / 8 bytes: bit j % 8 of byte j / 8 is set iff the sign bit of dot(P[j], v - c) is clear. */
+#define LANCE_HIP_RQ_MAX_DIM 2048
+/* RabitQuantizer::quantize + RQTransformer::transform (bq/builder.rs, bq/transform.rs:95-208) for rows x[n][d] already assigned:
+ * part_ids[n] (LANCE_HIP_NONE: the row gets zero codes and factors), dist_v_c[n] the distance the assignment reported
+ * (PartitionTransformer::with_distance), centroids[nlist][d].  Out: codes[n][d / 8], add[n], scale[n] (ADD_FACTORS / SCALE_FACTORS).
+ * The rotation is summed in the order of lance_linalg::distance::dot and the code / residual inner product sequentially: the
+ * reference runs a BLAS GEMM there, so codes may differ from its own where a rotated component is within rounding of zero. */
+int lance_hip_rq_encode(lance_hip_ctx *ctx, int metric, const float *x, uint64_t n, uint32_t d, const uint32_t *part_ids,
+                        const float *dist_v_c, const float *centroids, uint32_t nlist, const float *rotation, uint8_t *codes,
+                        float *add, float *scale);
+/* RabitQuantizationStorage::dist_calculator + RabitDistCalculator (bq/storage.rs:296-369, 409-445) over ONE partition's storage:
+ * codes[n][d / 8], add[n], scale[n] in storage order against nq residual queries qr[nq][d] (q - centroid) with their dist_q_c[nq].
+ * quantised != 0: distance_all (rows below n - n % 32 through the u8 table with saturating u16 sums, the rest in f32);
+ * quantised == 0: distance(id) of every row (what a prefiltered search computes).  dists[nq][n]; nq <= 65535. */
+int lance_hip_rq_distance(lance_hip_ctx *ctx, int metric, const uint8_t *codes, const float *add, const float *scale, uint64_t n,
+                          uint32_t d, const float *qr, const float *dist_q_c, uint32_t nq, const float *rotation, int quantised,
+                          float *dists);
+/* Per-partition RabitQuantizationStorage on the device (bq/storage.rs; IvfTransformer::with_rq ivf.rs:281-326): codes / add / scale
+ * are gathered into partition order (stable; rows with part id LANCE_HIP_NONE dropped); row_ids NULL -> row index.  The handle
+ * keeps its own copy of centroids and rotation; it is destroyed with lance_hip_index_destroy; every IVF_PQ / IVF_FLAT / IVF_SQ
+ * entry point, lance_hip_index_save and the maintenance entries (merge / remap / export_rows) refuse it.                       */
+int lance_hip_ivfrq_create(lance_hip_ctx *ctx, int metric, uint32_t d, const float *centroids, uint32_t nlist, const float *rotation,
+                           const uint8_t *codes, const float *add, const float *scale, const uint32_t *part_ids,
+                           const uint64_t *row_ids, uint64_t n, lance_hip_index **out);
+/* find_partitions + preprocess_query (ivf/v2.rs:316-332: residual query and dist_q_c per probed partition) + FlatIndex::search over
+ * the partition's RabitQ storage (flat/index.rs:82-126: distance_all, a max-heap of k, rows in storage order) +
+ * SortExec(dist, rowid).fetch(k); k <= 128.  Queries whose answer depends on the heap's handling of ties are replayed through it. */
+int lance_hip_ivfrq_search(lance_hip_ctx *ctx, const lance_hip_index *idx, const float *q, uint32_t nq, uint32_t k,
+                           uint32_t nprobes, uint64_t *ids, float *dists);
+/* The same under a row-id prefilter (flat/index.rs:129-165: distance(id) of every selected row -- the f32 table, never the
+ * quantised one), tested inside the scan and the replay kernel; k <= 128. */
+int lance_hip_ivfrq_search_filtered(lance_hip_ctx *ctx, const lance_hip_index *idx, const float *q, uint32_t nq, uint32_t k,
+                                    uint32_t nprobes, const uint8_t *allow_by_rowid, uint64_t n_allow, uint64_t *ids, float *dists);
+
 /* ---- N5: 8-bit scalar quantisation and IVF_SQ (lance-index/src/vector/sq.rs, sq/storage.rs, sq/builder.rs) ------------ */
 /* Columns are LANCE_HIP_F32 or LANCE_HIP_F16 (an int8 column is refused: the reference's SQ builder takes float arrays only; f64
  * columns are not in this library).  1 <= d <= LANCE_HIP_SQ_MAX_DIM; only num_bits = 8 exists (sq.rs `// TODO: support SQ4`).

@@ -111,6 +111,20 @@ extern "C" {
         ids: *mut u64, dists: *mut f32) -> i32;
     pub fn lance_hip_ivfsq_search_filtered(ctx: *mut LanceHipCtx, idx: *const LanceHipIndex, q: *const c_void, nq: u32, k: u32,
         nprobes: u32, allow_by_rowid: *const u8, n_allow: u64, ids: *mut u64, dists: *mut f32) -> i32;
+    // 1-bit RaBitQ (bq/builder.rs, bq/transform.rs:95-208) and the IVF_RQ sub-index (FlatIndex over RabitQuantizationStorage,
+    // bq/storage.rs:296-369, 409-445); f32 columns, L2 / dot, d a multiple of 8; rotation = the model's [d][d] matrix, a device pointer
+    pub fn lance_hip_rq_encode(ctx: *mut LanceHipCtx, metric: i32, x: *const f32, n: u64, d: u32, part_ids: *const u32,
+        dist_v_c: *const f32, centroids: *const f32, nlist: u32, rotation: *const f32, codes: *mut u8, add: *mut f32,
+        scale: *mut f32) -> i32;
+    pub fn lance_hip_rq_distance(ctx: *mut LanceHipCtx, metric: i32, codes: *const u8, add: *const f32, scale: *const f32, n: u64,
+        d: u32, qr: *const f32, dist_q_c: *const f32, nq: u32, rotation: *const f32, quantised: i32, dists: *mut f32) -> i32;
+    pub fn lance_hip_ivfrq_create(ctx: *mut LanceHipCtx, metric: i32, d: u32, centroids: *const f32, nlist: u32, rotation: *const f32,
+        codes: *const u8, add: *const f32, scale: *const f32, part_ids: *const u32, row_ids: *const u64, n: u64,
+        out: *mut *mut LanceHipIndex) -> i32;
+    pub fn lance_hip_ivfrq_search(ctx: *mut LanceHipCtx, idx: *const LanceHipIndex, q: *const f32, nq: u32, k: u32, nprobes: u32,
+        ids: *mut u64, dists: *mut f32) -> i32;
+    pub fn lance_hip_ivfrq_search_filtered(ctx: *mut LanceHipCtx, idx: *const LanceHipIndex, q: *const f32, nq: u32, k: u32,
+        nprobes: u32, allow_by_rowid: *const u8, n_allow: u64, ids: *mut u64, dists: *mut f32) -> i32;
     // index maintenance (optimize_indices: ivf.rs:355-560, builder.rs:685-935; remap: builder.rs:256-359): every call returns a new
     // handle and leaves its sources untouched; new_ids[i] == u64::MAX (LANCE_HIP_ROW_DELETED) drops the row
     pub fn lance_hip_index_merge(ctx: *mut LanceHipCtx, srcs: *const *const LanceHipIndex, n_srcs: u32,

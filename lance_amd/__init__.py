@@ -9,18 +9,18 @@ a GPU.
 from . import _lib
 from ._lib import LanceHipError
 
-__all__ = ["_lib", "LanceHipError", "Engine", "DeviceIndex", "KMeans", "IvfPqParams", "IvfPqIndex", "IvfSqIndex", "DeviceSqIndex", "create_index",
+__all__ = ["_lib", "LanceHipError", "Engine", "DeviceIndex", "KMeans", "IvfPqParams", "IvfPqIndex", "IvfSqIndex", "DeviceSqIndex", "IvfRqIndex", "DeviceRqIndex", "create_index",
            "flat_knn", "multivector_distance", "multivector_flat_knn", "train_ivf_centroids", "train_pq_codebook", "train_sq_bounds", "default_engine", "load_index",
            "validate_vector_index", "merge_indices", "IndicesBuilder", "IvfModel", "PqModel"]
 
 
 def __getattr__(name):
     # torch-dependent modules are imported lazily so that `import lance_amd` stays cheap
-    if name in ("Engine", "DeviceIndex", "DeviceSqIndex"):
+    if name in ("Engine", "DeviceIndex", "DeviceSqIndex", "DeviceRqIndex"):
         from . import engine
         return getattr(engine, name)
     if name in ("KMeans", "IvfPqParams", "IvfPqIndex", "create_index", "flat_knn", "multivector_distance", "multivector_flat_knn",
-                "train_ivf_centroids", "IvfSqIndex", "train_sq_bounds",
+                "train_ivf_centroids", "IvfSqIndex", "IvfRqIndex", "train_sq_bounds",
                 "train_pq_codebook", "default_engine", "load_index", "validate_vector_index", "merge_indices"):
         from . import vector
         return getattr(vector, name)

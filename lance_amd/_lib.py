@@ -15,6 +15,7 @@ L2, COSINE, DOT = 0, 1, 2
 F32, F16, I8 = 0, 1, 2
 NONE = 0xFFFFFFFF
 SQ_MAX_DIM = 16384                   # LANCE_HIP_SQ_MAX_DIM (include/lance_hip.h)
+RQ_MAX_DIM = 2048                    # LANCE_HIP_RQ_MAX_DIM (include/lance_hip.h)
 MULTIVEC_MAX_QUERY_VECTORS = 256     # LANCE_HIP_MULTIVEC_MAX_QUERY_VECTORS (include/lance_hip.h)
 U64_MAX = 0xFFFFFFFFFFFFFFFF
 ROW_DELETED = U64_MAX               # LANCE_HIP_ROW_DELETED (include/lance_hip.h)
@@ -36,6 +37,7 @@ SYMBOLS = [
     "lance_hip_search_stats", "lance_hip_ivfpq_search_filtered", "lance_hip_ivfpq_search_filtered_range",
     "lance_hip_flat_topk", "lance_hip_multivec_distance", "lance_hip_flat_multivec_topk", "lance_hip_ivfflat_create", "lance_hip_ivfflat_search", "lance_hip_ivfflat_search_filtered",
     "lance_hip_sq_bounds", "lance_hip_sq_encode", "lance_hip_sq_distance", "lance_hip_ivfsq_create", "lance_hip_ivfsq_search", "lance_hip_ivfsq_search_filtered",
+    "lance_hip_rq_encode", "lance_hip_rq_distance", "lance_hip_ivfrq_create", "lance_hip_ivfrq_search", "lance_hip_ivfrq_search_filtered",
     "lance_hip_index_file_open", "lance_hip_index_file_get", "lance_hip_index_file_close", "lance_hip_index_file_write",
     "lance_hip_index_load", "lance_hip_index_load_lists", "lance_hip_index_save", "lance_hip_file_read_column",
     "lance_hip_timing_enable", "lance_hip_timing_query", "lance_hip_ubench", "lance_hip_merge_topk",
@@ -149,6 +151,11 @@ def load():
         "lance_hip_ivfsq_create": (i32, [vp, i32, i32, u32, vp, u32, vp, vp, vp, u64, C.POINTER(f64), C.POINTER(vp)]),
         "lance_hip_ivfsq_search": (i32, [vp, vp, vp, u32, u32, u32, vp, vp]),
         "lance_hip_ivfsq_search_filtered": (i32, [vp, vp, vp, u32, u32, u32, vp, u64, vp, vp]),
+        "lance_hip_rq_encode": (i32, [vp, i32, vp, u64, u32, vp, vp, vp, u32, vp, vp, vp, vp]),
+        "lance_hip_rq_distance": (i32, [vp, i32, vp, vp, vp, u64, u32, vp, vp, u32, vp, i32, vp]),
+        "lance_hip_ivfrq_create": (i32, [vp, i32, u32, vp, u32, vp, vp, vp, vp, vp, vp, u64, C.POINTER(vp)]),
+        "lance_hip_ivfrq_search": (i32, [vp, vp, vp, u32, u32, u32, vp, vp]),
+        "lance_hip_ivfrq_search_filtered": (i32, [vp, vp, vp, u32, u32, u32, vp, u64, vp, vp]),
         "lance_hip_index_file_open": (i32, [C.c_char_p, C.POINTER(vp)]),
         "lance_hip_index_file_get": (i32, [vp, C.POINTER(IndexFileView)]),
         "lance_hip_index_file_close": (None, [vp]),

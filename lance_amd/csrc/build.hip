@@ -301,6 +301,7 @@ lance_hip_index::~lance_hip_index() {
   if (vectors) (void)hipFree(vectors);
   if (flat_items) (void)hipFree(flat_items);
   if (raw_u8) (void)hipFree(raw_u8);
+  if (rq_rot_t) (void)hipFree(rq_rot_t);
 }
 
 // tail of lance_hip_ivfpq_encode: the optional loss and the synchronisation

@@ -80,6 +80,17 @@ struct lance_hip_index {
   double sq_lo = 0.0, sq_hi = 0.0;   // the quantiser's bounds (ScalarQuantizer::bounds)
   uint32_t sq_nlist = 0, sq_ld = 0;
   const uint32_t *sq_xx = nullptr;   // alias into `codes`
+  // IVF_RQ (rq.hip; bq/builder.rs, bq/transform.rs, bq/storage.rs): `codes` holds the 1-bit RaBitQ codes [n][rq_cb] (rq_cb = d / 8 bytes,
+  // bit j of a row in byte j / 8, bit j % 8; row-major, rows grouped by partition) followed, in the same allocation and 16-byte
+  // aligned, by the per-row factors rq_add [n] and rq_scale [n].  rq_rot_t is the rotation TRANSPOSED ([i][j] = P[j][i]): lane j of a
+  // rotating kernel reads consecutive words.  Like an SQ handle it keeps m = 0, vectors = NULL and the generic nlist = 0 (its own
+  // count is rq_nlist), so every IVF_PQ / IVF_FLAT entry point refuses it; IVF_SQ entries and the index file / maintenance entries
+  // refuse it by the flag.
+  bool rq = false;
+  uint32_t rq_nlist = 0, rq_cb = 0;
+  float *rq_rot_t = nullptr;          // [d][d] device
+  const float *rq_add = nullptr;      // aliases into `codes`
+  const float *rq_scale = nullptr;
   uint32_t max_part = 0;
   uint32_t code_bytes() const { return nbits == 4 ? m / 2 : m; }   // bytes of PQ code per row
   ~lance_hip_index();

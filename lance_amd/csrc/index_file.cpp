@@ -704,6 +704,7 @@ extern "C" int lance_hip_index_load_lists(lance_hip_ctx *ctx, const char *index_
 extern "C" int lance_hip_index_save(lance_hip_ctx *ctx, const lance_hip_index *idx, const char *index_dir, int has_loss, double loss) {
   LH_REQUIRE(ctx && idx && index_dir, "index_save: NULL argument");
   LH_REQUIRE(!idx->sq, "index_save: IVF_SQ index files are not supported (IVF_PQ and IVF_FLAT are)");
+  LH_REQUIRE(!idx->rq, "index_save: IVF_RQ index files are not supported (IVF_PQ and IVF_FLAT are)");
   LH_CHECK_HIP(hipSetDevice(ctx->device));
   lance_hip_index_file_view v{};
   const bool pq = idx->m != 0;

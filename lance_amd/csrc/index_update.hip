@@ -143,6 +143,7 @@ static uint8_t *iu_payload(lance_hip_index *ix) { return iu_kind(ix) == IU_FLAT 
 
 static int iu_check_handle(const lance_hip_ctx *ctx, const lance_hip_index *ix, const char *what) {
   LH_REQUIRE(ix, "%s: NULL index", what);
+  LH_REQUIRE(!ix->rq, "%s: IVF_RQ indices are not maintained (the reference's RabitQ storage has no append_batch): rebuild the index", what);
   LH_REQUIRE(!ix->ephemeral && ix->part_offsets && ix->part_offsets_h.size() == (size_t)iu_lists(ix) + 1 && ix->centroids,
              "%s: the handle holds no index storage", what);
   LH_REQUIRE(ix->device == ctx->device, "%s: context and index live on different devices", what);

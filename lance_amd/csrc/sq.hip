@@ -452,6 +452,19 @@ static int sq_encode_launch(lance_hip_ctx *ctx, int dtype, const void *x, uint64
 
 }  // namespace lh
 
+// kernels.h: the merge step for another FlatIndex sub-index scan that filled the same per-pair lists (rq.hip)
+int lh::sq_merge_pairs(lance_hip_ctx *ctx, const PairLists &pl, uint32_t nq, uint64_t *ids, float *dists, const char *timer) {
+  SqArgs a = {};
+  a.row_ids = pl.row_ids; a.nprobes = pl.nprobes; a.k = pl.k; a.pkey = pl.pkey; a.ppos = pl.ppos; a.pcnt = pl.pcnt; a.pamb = pl.pamb;
+  a.flags = pl.flags; a.n_replay = pl.n_replay;
+  {
+    ScopedTimer t(ctx, timer);
+    hipLaunchKernelGGL(sq_merge_kernel, dim3(nq), dim3(256), (size_t)SQ_BUF * 16 + 16, ctx->stream, a, ids, dists);
+  }
+  LH_CHECK_HIP(hipGetLastError());
+  return LANCE_HIP_OK;
+}
+
 using namespace lh;
 
 extern "C" int lance_hip_sq_bounds(lance_hip_ctx *ctx, int dtype, const void *x, uint64_t count, double *bounds_host) {

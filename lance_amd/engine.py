@@ -128,6 +128,33 @@ def _sq_column(a):
     return _vec(a)
 
 
+def _rq_f32(a, what):
+    """an array for the RaBitQ entry points -> contiguous float32 cuda tensor; other element types are refused"""
+    name = _dtype_name(a)
+    if name not in ("float32", "float64"):      # (float64 host arrays are narrowed, as everywhere in this package)
+        raise NotImplementedError(f"IVF_RQ: {what} must be float32, got {name} (float16 and int8 columns are not supported)")
+    return _vec(a)[0]
+
+
+def _rq_check(metric, x, cent, rot):
+    if metric == "cosine":
+        raise NotImplementedError("IVF_RQ: metric cosine is not supported (which distance type the reference's loaded storage carries into "
+                                  "q_factor is not established); use l2 or dot")
+    if metric not in ("l2", "dot"):
+        raise ValueError(f"IVF_RQ: metric {metric} not supported (l2 and dot are)")
+    if x.dim() != 2:
+        raise ValueError(f"rows must be [n][d], got shape {tuple(x.shape)}")
+    d = x.shape[1]
+    if d % 8 != 0 or d == 0:
+        raise ValueError(f"IVF_RQ: dimension {d} is not a multiple of 8 (one bit per dimension, packed into bytes)")
+    if d > _lib.RQ_MAX_DIM:
+        raise ValueError(f"IVF_RQ: dimension {d} not supported (up to {_lib.RQ_MAX_DIM})")
+    if cent is not None and (cent.dim() != 2 or cent.shape[1] != d):
+        raise ValueError(f"centroids must be [nlist][{d}], got shape {tuple(cent.shape)}")
+    if tuple(rot.shape) != (d, d):
+        raise ValueError(f"rq_rotation must be [{d}][{d}], got shape {tuple(rot.shape)}")
+
+
 def _on_engine_device(fn):
     """Every tensor a method allocates or moves must live on the GPU the context was created on (two Engines in one process
     may sit on different GPUs): run the method with that device current."""
@@ -495,6 +522,45 @@ class Engine:
         check(self.lib.lance_hip_sq_distance(self.h, dt, METRICS[metric], _ptr(codes), n, d, _ptr(q), q.shape[0], b, _ptr(dists)))
         return dists
 
+    # ---- 1-bit RaBitQ (lance-index/src/vector/bq) ------------------------------------------
+    def rq_encode(self, x, part_ids, dist_v_c, centroids, rotation, metric="l2"):
+        """RabitQuantizer::quantize + RQTransformer::transform: float32 rows x [n][d] with their partition ids and the distances the
+        assignment reported (Engine.assign's two results), centroids [nlist][d], rotation P [d][d] -> (codes uint8 [n][d / 8],
+        add float32 [n], scale float32 [n]).  Rows without a partition (id -1) get zeros."""
+        x, cent, rot = _rq_f32(x, "x"), _rq_f32(centroids, "centroids"), _rq_f32(rotation, "rotation")
+        _rq_check(metric, x, cent, rot)
+        n, d = x.shape
+        part = to_device(part_ids, torch.int32)
+        dvc = to_device(dist_v_c, torch.float32)
+        if part.numel() != n or dvc.numel() != n:
+            raise ValueError(f"part_ids and dist_v_c must hold one entry per row ({n}), got {part.numel()} and {dvc.numel()}")
+        codes = torch.empty((n, d // 8), dtype=torch.uint8, device=x.device)
+        add = torch.empty(n, dtype=torch.float32, device=x.device)
+        scale = torch.empty(n, dtype=torch.float32, device=x.device)
+        torch.cuda.synchronize()
+        check(self.lib.lance_hip_rq_encode(self.h, METRICS[metric], _ptr(x), n, d, _ptr(part), _ptr(dvc), _ptr(cent), cent.shape[0], _ptr(rot),
+                                           _ptr(codes), _ptr(add), _ptr(scale)))
+        return codes, add, scale
+
+    def rq_distance(self, codes, add, scale, qr, dist_q_c, rotation, metric="l2", quantised=True):
+        """RabitDistCalculator over ONE partition's storage (codes [n][d / 8], add [n], scale [n], in storage order) against residual
+        queries qr [nq][d] (q - centroid) with their dist_q_c [nq]: quantised=True is distance_all (rows below n - n % 32 through the
+        u8 table, the rest in f32), False is distance(id) of every row (a prefiltered search) -> [nq][n] float32"""
+        rot = _rq_f32(rotation, "rotation")
+        d = rot.shape[0]
+        qr = _rq_f32(qr, "qr").reshape(-1, d)
+        _rq_check(metric, qr, None, rot)
+        codes = to_device(codes, torch.uint8)
+        add, scale, dqc = to_device(add, torch.float32), to_device(scale, torch.float32), to_device(dist_q_c, torch.float32)
+        n = codes.shape[0]
+        if codes.dim() != 2 or codes.shape[1] != d // 8 or add.numel() != n or scale.numel() != n or dqc.numel() != qr.shape[0]:
+            raise ValueError(f"codes must be [n][{d // 8}] with add / scale [n] and dist_q_c [nq]")
+        dists = torch.empty((qr.shape[0], n), dtype=torch.float32, device=qr.device)
+        torch.cuda.synchronize()
+        check(self.lib.lance_hip_rq_distance(self.h, METRICS[metric], _ptr(codes), _ptr(add), _ptr(scale), n, d, _ptr(qr), _ptr(dqc), qr.shape[0],
+                                             _ptr(rot), int(bool(quantised)), _ptr(dists)))
+        return dists
+
     def search_stats(self):
         """queries of the last search replayed by the exact (heap-emulating) kernel"""
         n = C.c_uint32(0)
@@ -677,6 +743,71 @@ class DeviceFlatIndex:
         except Exception:
             pass
 
+
+
+class DeviceRqIndex:
+    """Handle of a device-resident IVF_RQ index (FlatIndex sub-index over the 1-bit RaBitQ codes and factors of each partition)."""
+
+    def __init__(self, engine, handle, metric, centroids, rotation):
+        self.engine = engine
+        self.h = handle
+        self.metric = metric
+        self.centroids = centroids
+        self.rotation = rotation
+        self.data_dtype = torch.float32
+
+    @classmethod
+    def create(cls, engine, metric, centroids, rotation, codes, add, scale, part_ids, row_ids=None):
+        """centroids [nlist][d] and rotation [d][d] float32; codes [n][d / 8] uint8, add / scale [n] float32 (Engine.rq_encode of the
+        rows); part_ids [n] (-1 = dropped)"""
+        cent, rot = _rq_f32(centroids, "centroids"), _rq_f32(rotation, "rotation")
+        _rq_check(metric, cent, cent, rot)
+        d = cent.shape[1]
+        codes = to_device(codes, torch.uint8)
+        add, scale = to_device(add, torch.float32), to_device(scale, torch.float32)
+        part = to_device(part_ids, torch.int32)
+        rid = None if row_ids is None else to_device(row_ids, torch.int64)
+        n = codes.shape[0]
+        if codes.dim() != 2 or codes.shape[1] != d // 8 or add.numel() != n or scale.numel() != n or part.numel() != n:
+            raise ValueError(f"codes must be [n][{d // 8}] with add / scale / part_ids [n]")
+        h = C.c_void_p()
+        torch.cuda.synchronize()
+        check(engine.lib.lance_hip_ivfrq_create(engine.h, METRICS[metric], d, _ptr(cent), cent.shape[0], _ptr(rot), _ptr(codes), _ptr(add),
+                                                _ptr(scale), _ptr(part), _ptr(rid), n, C.byref(h)))
+        return cls(engine, h, metric, cent, rot)
+
+    def save(self, index_dir, loss=None):
+        raise NotImplementedError("IVF_RQ index files are not supported (IVF_PQ and IVF_FLAT are)")
+
+    def search(self, q, k, nprobes, allow=None):
+        """allow: boolean array indexed by row id (a prefilter), tested inside the scan kernels (lance_hip_ivfrq_search_filtered): every
+        selected row then takes the f32 distance, as the reference's prefiltered FlatIndex::search does"""
+        d = self.centroids.shape[1]
+        q = _rq_f32(q, "queries").reshape(-1, d)
+        nq = q.shape[0]
+        ids = torch.empty((nq, k), dtype=torch.int64, device=q.device)
+        dists = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+        if allow is not None:
+            a = allow if isinstance(allow, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(allow, dtype=bool))
+            a = a.to(torch.uint8).to(_dev()).contiguous()
+            torch.cuda.synchronize()
+            check(self.engine.lib.lance_hip_ivfrq_search_filtered(self.engine.h, self.h, _ptr(q), nq, k, nprobes, _ptr(a), a.numel(),
+                                                                  _ptr(ids), _ptr(dists)))
+            return ids, dists
+        torch.cuda.synchronize()
+        check(self.engine.lib.lance_hip_ivfrq_search(self.engine.h, self.h, _ptr(q), nq, k, nprobes, _ptr(ids), _ptr(dists)))
+        return ids, dists
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.engine.lib.lance_hip_index_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class DeviceSqIndex:
@@ -1011,4 +1142,5 @@ class DeviceIndex:
 
 _wrap_methods(DeviceFlatIndex, skip=("close",))
 _wrap_methods(DeviceSqIndex, skip=("close", "save"))
+_wrap_methods(DeviceRqIndex, skip=("close", "save"))
 _wrap_methods(DeviceIndex, skip=("close",))

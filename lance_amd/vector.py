@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from ._lib import EINVAL, METRICS, NONE, ROW_DELETED, LanceHipError
-from .engine import DeviceFlatIndex, DeviceIndex, DeviceSqIndex, Engine, _dtype_name, check_multivector, to_device
+from .engine import DeviceFlatIndex, DeviceIndex, DeviceRqIndex, DeviceSqIndex, Engine, _dtype_name, check_multivector, to_device
 
 _engine = None
 
@@ -228,6 +228,8 @@ def merge_indices(indices, raw=None):
     if not indices:
         raise ValueError("merge_indices: no index given")
     kinds = {type(ix) for ix in indices}
+    if any(k.__name__ == "IvfRqIndex" for k in kinds):
+        raise NotImplementedError("IVF_RQ: merge_indices is not supported (the reference's RabitQ storage has no append_batch): rebuild the index")
     if len(kinds) != 1 or not isinstance(indices[0], _Maintenance):
         raise ValueError(f"merge_indices: the indices must be of one kind, got {sorted(k.__name__ for k in kinds)}")
     try:
@@ -530,6 +532,66 @@ class IvfSqIndex(_Maintenance):
         raise NotImplementedError("IVF_SQ index files are not supported (IVF_PQ and IVF_FLAT are)")
 
 
+class IvfRqIndex:
+    """IVF_RQ: IVF partitions over 1-bit RaBitQ codes (lance-index/src/vector/bq): d / 8 code bytes and two f32 factors per row, the
+    residual rotated by a matrix that is part of the model.  Resident in HBM; no index files, refine, distance ranges or maintenance
+    (the reference's RabitQ storage has no append_batch either)."""
+
+    def __init__(self, ix, params, stats, part_ids):
+        self._ix = ix
+        self.params = params
+        self.stats = stats
+        self.part_ids = part_ids
+
+    @property
+    def centroids(self):
+        return self._ix.centroids.cpu().numpy()
+
+    @property
+    def rotation(self):
+        """the rotation P [d][d] float32 stored with the index (rotated = P @ residual)"""
+        return self._ix.rotation.cpu().numpy()
+
+    def search_device(self, q, k, nprobes):
+        return self._ix.search(q, k, nprobes)
+
+    def nearest(self, q, k=10, nprobes=1, prefilter=None, refine_factor=None, distance_range=None):
+        """prefilter: boolean array over row ids; the mask is tested inside the scan kernels, and every selected row takes the f32
+        distance (the reference's prefiltered FlatIndex::search never uses the quantised table)"""
+        if refine_factor is not None:
+            raise NotImplementedError("IVF_RQ: refine_factor (re-ranking on the raw vectors) is not supported by this engine")
+        if distance_range is not None:
+            raise NotImplementedError("IVF_RQ: distance_range is not supported by this engine")
+        ids, dists = self._ix.search(q, k, nprobes) if prefilter is None else self._ix.search(q, k, nprobes, allow=prefilter)
+        return ids.cpu().numpy().view(np.uint64), dists.cpu().numpy()
+
+    def _unmaintained(self, what):
+        raise NotImplementedError(f"IVF_RQ: {what} is not supported (the reference's RabitQ storage has no append_batch): rebuild the index")
+
+    def append(self, *a, **kw):
+        self._unmaintained("append")
+
+    def remap(self, *a, **kw):
+        self._unmaintained("remap")
+
+    def delete(self, *a, **kw):
+        self._unmaintained("delete")
+
+    def save(self, index_dir):
+        raise NotImplementedError("IVF_RQ index files are not supported (IVF_PQ and IVF_FLAT are)")
+
+    def close(self):
+        self._ix.close()
+
+
+def rq_rotation_matrix(d, seed):
+    """The default rotation of an IVF_RQ index: Q of the QR decomposition of a seeded Gaussian matrix, computed in float64 on the
+    host and cast to float32.  (The reference draws its own random orthogonal matrix; its RNG stream is not reproduced -- the matrix
+    is part of the model and is stored with the index, as the reference stores its own.)"""
+    g = np.random.default_rng(seed).standard_normal((d, d))
+    return np.ascontiguousarray(np.linalg.qr(g)[0].astype(np.float32))
+
+
 def train_sq_bounds(x, params: IvfPqParams, engine=None):
     """load_or_build_quantizer for the scalar quantiser (rust/lance/src/index/vector/builder.rs:399-466, sq.rs:152-180): sample
     sample_rate * 2^num_bits rows, normalise (cosine), drop non-finite rows, fold the rest into fresh bounds.  There is no residual
@@ -678,16 +740,31 @@ def _transform_rows(eng, itype, metric, x, cent, codebook=None, bounds=None, tim
     return part, codes
 
 
-def create_index(x, index_type="IVF_PQ", metric="l2", num_partitions=256, num_sub_vectors=16, num_bits=8, max_iters=50,
-                 sample_rate=256, ivf_centroids=None, pq_codebook=None, seed=42, keep_raw=True, engine=None):
-    """Dataset.create_index(column, "IVF_PQ", ...) for a vector matrix resident (or copied) in HBM."""
+def create_index(x, index_type="IVF_PQ", metric="l2", num_partitions=256, num_sub_vectors=16, num_bits=None, max_iters=50,
+                 sample_rate=256, ivf_centroids=None, pq_codebook=None, seed=42, keep_raw=True, engine=None, rq_rotation=None):
+    """Dataset.create_index(column, "IVF_PQ", ...) for a vector matrix resident (or copied) in HBM.
+    num_bits: None = the index type's default (8 for IVF_PQ / IVF_SQ, 1 for IVF_RQ, as in the reference's build parameters).
+    rq_rotation: IVF_RQ only (ignored otherwise) -- the [d][d] float32 rotation of the model; None: rq_rotation_matrix(d, seed)."""
     # ---- argument rules of Dataset.create_index (python/python/lance/dataset.py:2708-2960), checked before any device work
     if not isinstance(metric, str):
         raise ValueError(f"Metric {metric} not supported.")
     metric_n = _normalize_metric_type(metric)
     itype = str(index_type).upper()
-    if itype not in ("IVF_PQ", "IVF_FLAT", "IVF_SQ"):
-        raise NotImplementedError(f"index_type {index_type}: IVF_PQ, IVF_FLAT and IVF_SQ are on this engine's hot path")
+    if itype not in ("IVF_PQ", "IVF_FLAT", "IVF_SQ", "IVF_RQ"):
+        raise NotImplementedError(f"index_type {index_type}: IVF_PQ, IVF_FLAT, IVF_SQ and IVF_RQ are on this engine's hot path")
+    if num_bits is None:
+        num_bits = 1 if itype == "IVF_RQ" else 8
+    if itype == "IVF_RQ":
+        # RabitQuantizer (lance-index/src/vector/bq/builder.rs): one bit per dimension here, f32 columns, L2 and dot
+        if num_bits != 1:
+            raise ValueError(f"RabitQuantization: num_bits {num_bits} not supported (only 1 is)")
+        if len(tuple(x.shape)) == 2 and (x.shape[1] % 8 != 0 or x.shape[1] == 0):
+            raise ValueError(f"IVF_RQ: dimension {x.shape[1]} is not a multiple of 8 (one bit per dimension, packed into bytes)")
+        if _dtype_name(x) not in ("float32", "float64"):
+            raise NotImplementedError(f"IVF_RQ: unsupported data type: {_dtype_name(x)} (float32 columns are supported; float16 and int8 are not)")
+        if metric_n == "cosine":
+            raise NotImplementedError("IVF_RQ: metric cosine is not supported (which distance type the reference's loaded storage carries into "
+                                      "q_factor is not established); use l2 or dot")
     if itype == "IVF_SQ":
         # ScalarQuantizer (lance-index/src/vector/sq.rs): 8 bits only (`// TODO: support SQ4`), float columns only
         if num_bits != 8:
@@ -763,6 +840,25 @@ def create_index(x, index_type="IVF_PQ", metric="l2", num_partitions=256, num_su
         fx = timed("build_partitions", lambda: DeviceFlatIndex.create(eng, params.metric, cent, xs, part))
         out = IvfFlatIndex(fx, params, stats, part)
         out._x = xs if keep_raw else None     # the stored rows (borrowed): needed to re-partition under a prefilter
+        out._rows_offered = n
+        return out
+    if itype == "IVF_RQ":
+        rot = to_device(np.asarray(rq_rotation_matrix(d, seed) if rq_rotation is None else
+                                   (rq_rotation.detach().cpu().numpy() if isinstance(rq_rotation, torch.Tensor) else rq_rotation), np.float32))
+        if tuple(rot.shape) != (d, d):
+            raise ValueError(f"rq_rotation must be [{d}][{d}], got shape {tuple(rot.shape)}")
+
+        x = x.to(torch.float32)
+
+        def transform():
+            # KeepFiniteVectors, then PartitionTransformer::with_distance(true), then RQTransformer (ivf.rs:281-326)
+            part, dvc = eng.assign(x, cent, params.metric)
+            part = torch.where(torch.isfinite(x).all(dim=1), part, torch.full_like(part, -1))
+            return part, dvc
+        part, dvc = timed("transform", transform)
+        codes, add, scale = timed("encode", lambda: eng.rq_encode(x, part, dvc, cent, rot, params.metric))
+        rx = timed("build_partitions", lambda: DeviceRqIndex.create(eng, params.metric, cent, rot, codes, add, scale, part))
+        out = IvfRqIndex(rx, params, stats, part)
         out._rows_offered = n
         return out
     if itype == "IVF_SQ":

@@ -1,0 +1,173 @@
+"""The DEVICE code of lance_amd/csrc/rq.hip run on the CPU, lane by lane (tests/c/simt_emu: a thread per lane, a barrier for
+__syncthreads), under AddressSanitizer + UBSan, against tests/rq_spec.py bit for bit: the encoder, the query preparation, the three
+distance branches (packed rows through the u8 table, the f32 remainder, the f32 fold under a prefilter) and the search -- per-pair
+selection, the merge kernel shared with IVF_SQ, the replay decision and the heap replay.  The kernels' text is cut out of the sources at
+test time, so what runs here is what the GPU compiles.  This checks the logic and the memory safety of the kernels without a device;
+the arithmetic of the device's own instructions is what tests/test_zz_gpu_rq.py checks."""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import rq_spec as R
+from test_sq_kernels_cpu import function_text
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "lance_amd", "csrc")
+EMU = os.path.join(ROOT, "tests", "c", "simt_emu")
+f32 = np.float32
+
+
+def block_text(src, head):
+    """the brace-matched definition that starts with the line `head` (a struct or a __global__ kernel)"""
+    start = src.index(head)
+    depth, i = 0, src.index("{", start)
+    while True:
+        depth += {"{": 1, "}": -1}.get(src[i], 0)
+        i += 1
+        if depth == 0:
+            return src[start:i] + (";\n" if head.startswith("struct") else "\n")
+
+
+def device_code():
+    read = lambda name: open(os.path.join(CSRC, name)).read()
+    exact, common, sq, rq = read("exact.cuh"), read("search_common.cuh"), read("sq.hip"), read("rq.hip")
+    parts = [function_text(exact, n) for n in ("order_key", "key_to_float")]
+    parts += [function_text(common, n) for n in ("row_allowed", "bitonic_sort_kr", "heap_sift_up", "heap_push", "heap_pop")]
+    # the merge kernel IVF_RQ shares with IVF_SQ, with the constants and the argument block it uses
+    parts += [re.search(r"^constexpr int SQ_MAX_K = \d+;\n", sq, flags=re.M).group(0), re.search(r"^constexpr int SQ_BUF = \d+;", sq, flags=re.M).group(0) + "\n"]
+    parts += [block_text(sq, "struct SqArgs {"), block_text(sq, "__global__ __launch_bounds__(256) void sq_merge_kernel(")]
+    body = rq[rq.index("constexpr uint32_t RQ_MAX_DIM"):rq.index("// ---- host side")]
+    body = body.replace("LANCE_HIP_RQ_MAX_DIM", "2048")
+    code = "".join(parts) + body
+    code = code.replace("extern __shared__ __attribute__((aligned(16))) char smem[];", "")
+    assert "__global__" in code and "smem" in code
+    return code
+
+
+@pytest.fixture(scope="module")
+def emulator(tmp_path_factory):
+    work = tmp_path_factory.mktemp("rq_emu")
+    (work / "rq_device_code.inc").write_text(device_code())
+    exe = str(work / "rq_kernels")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-pthread",
+           "-I", str(work), "-I", EMU, os.path.join(EMU, "rq_kernels_main.cpp"), "-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    if r.returncode != 0 and "sanitize" in r.stderr:
+        pytest.skip("g++ without sanitizer runtimes")
+    assert r.returncode == 0, r.stderr[-3000:]
+    return exe, work
+
+
+def run_case(emulator, oracle, x, q, cent, P, metric, k, nprobes, row_ids, prefilter=None):
+    exe, work = emulator
+    x, q, cent, P = (np.ascontiguousarray(a, f32) for a in (x, q, cent, P))
+    n, d = x.shape
+    nq, nlist = q.shape[0], cent.shape[0]
+    nprobes = min(nprobes, nlist)
+    part, dvc = R.prepare_rows(oracle, x, cent, metric)
+    offs, perm = oracle.partition_layout(part, nlist)
+    probes, pd = oracle.find_partitions(q, cent, nprobes, metric)
+    every, every_d = oracle.find_partitions(q, cent, nlist, metric)
+    dqc_all = np.empty((nq, nlist), f32)
+    np.put_along_axis(dqc_all, every.astype(np.int64), every_d, axis=1)
+    bits = np.zeros(len(perm) // 32 + 4, np.uint32)
+    if prefilter is not None:
+        stored = row_ids[perm]
+        ok = stored < prefilter.size
+        ok[ok] = prefilter[stored[ok]]
+        for i in np.nonzero(ok)[0]:
+            bits[i >> 5] |= np.uint32(1 << (i & 31))
+    inp, outp = str(work / "in.bin"), str(work / "out.bin")
+    with open(inp, "wb") as fh:
+        np.array([n, d, nlist, nq, nprobes, k, int(metric == "dot"), int(prefilter is not None)], np.uint32).tofile(fh)
+        x.tofile(fh); q.tofile(fh); cent.tofile(fh); P.tofile(fh)
+        part.astype(np.uint32).tofile(fh); dvc.astype(f32).tofile(fh)
+        np.array([len(perm)], np.uint32).tofile(fh); perm.astype(np.uint32).tofile(fh); offs.astype(np.uint32).tofile(fh)
+        row_ids.astype(np.uint64).tofile(fh); probes.astype(np.uint32).tofile(fh); pd.astype(f32).tofile(fh); dqc_all.tofile(fh)
+        if prefilter is not None:
+            bits.tofile(fh)
+    r = subprocess.run([exe, inp, outp], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout[-1000:] + r.stderr[-4000:]
+    raw = np.fromfile(outp, np.uint8)
+    pos = 0
+
+    def take(count, dt):
+        nonlocal pos
+        a = raw[pos:pos + count * np.dtype(dt).itemsize].view(dt)
+        pos += count * np.dtype(dt).itemsize
+        return a
+    cb = d // 8
+    codes, add, scale = take(n * cb, np.uint8).reshape(n, cb), take(n, f32), take(n, f32)
+    want_codes, want_add, want_scale = R.encode(x, part, dvc, cent, P, metric)
+    assert (codes == want_codes).all()
+    assert (add.view(np.uint32) == want_add.view(np.uint32)).all() and (scale.view(np.uint32) == want_scale.view(np.uint32)).all()
+    for p in range(nlist):
+        rows = perm[int(offs[p]):int(offs[p + 1])]
+        if len(rows) == 0:
+            continue
+        for quantised in (True, False):
+            got = take(nq * len(rows), f32).reshape(nq, len(rows))
+            want = R.distances(want_codes[rows], want_add[rows], want_scale[rows], q - cent[p], dqc_all[:, p], P, metric, quantised)
+            assert (got.view(np.uint32) == want.view(np.uint32)).all(), (p, quantised)
+    ids, dists = take(nq * k, np.uint64).reshape(nq, k), take(nq * k, f32).reshape(nq, k)
+    flags = take(nq + 1, np.uint32)
+    fast_ids = take(nq * k, np.uint64).reshape(nq, k)
+    assert pos == raw.size
+    oi, od = R.search(oracle, want_codes, want_add, want_scale, part, cent, P, q, k, nprobes, metric, row_ids=row_ids, prefilter=prefilter)
+    assert (ids == oi).all() and (dists.view(np.uint32) == od.view(np.uint32)).all()
+    kept = flags[:nq] == 0
+    assert (fast_ids[kept] == oi[kept]).all()
+    assert flags[nq] == (~kept).sum()
+    return int(flags[nq])
+
+
+def test_device_code_is_found():
+    code = device_code()
+    for name in ("rq_transpose_kernel", "rq_encode_kernel", "rq_prepare", "rq_row_distance", "rq_distance_kernel", "rq_scan_kernel", "rq_exact_kernel",
+                 "rq_gather_kernel", "sq_merge_kernel", "heap_pop", "bitonic_sort_kr", "order_key"):
+        assert name in code, name
+    assert "hipLaunchKernelGGL" not in code and "LH_REQUIRE" not in code, "host code must stay out"
+
+
+def queries(x, cent, nq, seed):
+    rng = np.random.default_rng(seed)
+    return np.ascontiguousarray((x[rng.integers(0, len(x), nq)] + rng.standard_normal((nq, x.shape[1])) * 0.2).astype(f32))
+
+
+@pytest.mark.parametrize("metric,d,rot,k,nprobes", [("l2", 128, "qr", 10, 3), ("dot", 8, "signed_perm", 128, 5), ("l2", 24, "identity", 1, 1)])
+def test_three_branches(emulator, oracle, metric, d, rot, k, nprobes):
+    """partitions of 64, 33, 31 and 0 rows and one of 258 (n % 32 = 0, 1, 31, 2; more than one 256-row chunk): packed rows, remainder
+    rows and -- under the prefilter -- the f32 fold; d = 128 reads rows as 16-byte words, d = 8 / 24 byte by byte (d = 24 also takes
+    the dot's tail).  The mask is half as long as the largest row id: about half the rows are selected, the ids of the others lie
+    past its end (not selected, and never read).  (Each run starts a thread per lane: two runs per shape.)"""
+    x, cent = R.sized_partitions([64, 33, 31, 0, 258], d, seed=d)
+    q = queries(x, cent, 2, seed=1)
+    P = R.rotations(d, seed=3)[rot]
+    rid = R.permuted_ids(len(x), 2)
+    run_case(emulator, oracle, x, q, cent, P, metric, k, nprobes, rid)
+    run_case(emulator, oracle, x, q, cent, P, metric, k, 5, rid, prefilter=np.ones(int(rid.max()) // 2, bool))
+
+
+def test_row_addresses(emulator, oracle):
+    """Lance row addresses (fragment << 32 | offset, tests/rowid_fixtures.py): the merge and the replay carry all 64 bits, and a mask
+    far shorter than every id selects nothing"""
+    import rowid_fixtures as F
+    x, cent = R.sized_partitions([40, 65], 16, seed=9)
+    q = queries(x, cent, 2, seed=3)
+    rid = F.row_addresses(len(x), 5)
+    P = R.rotations(16, seed=2)["qr"]
+    run_case(emulator, oracle, x, q, cent, P, "l2", 10, 2, rid)
+    run_case(emulator, oracle, x, q, cent, P, "l2", 10, 2, rid, prefilter=np.ones(1000, bool))
+
+
+def test_ties_are_replayed(emulator, oracle):
+    """a block of identical rows: more rows tie at a partition's k-th distance than fit, the heap decides which stay"""
+    x, cent = R.sized_partitions([40, 300], 16, seed=4, dup_block=200)
+    q = queries(x, cent, 2, seed=2)
+    rid = np.random.default_rng(6).permutation(len(x)).astype(np.uint64) * np.uint64(5) + np.uint64(1)
+    P = R.rotations(16, seed=1)["qr"]
+    assert run_case(emulator, oracle, x, q, cent, P, "l2", 10, 2, rid) > 0
+    assert run_case(emulator, oracle, x, q, cent, P, "l2", 128, 2, rid, prefilter=np.arange(int(rid.max()) + 1) % 3 != 0) > 0
