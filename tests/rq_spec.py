@@ -1,4 +1,4 @@
-"""Shared by tests/test_rq_spec.py (CPU), tests/test_rq_kernels_cpu.py (CPU) and tests/test_zz_gpu_rq.py (GPU): the CPU specification
+"""Shared by tests/test_rq_spec.py (CPU), tests/test_rq_kernels_cpu.py (CPU), tests/test_zz_gpu_rq.py and tests/test_zz_gpu_rq_scan.py (GPU): the CPU specification
 of the 1-bit RaBitQ quantiser and of the IVF_RQ search, in numpy, composed with the oracle's functions for the IVF side.
 
 The specification (lance-index bq/builder.rs, bq/transform.rs, bq/storage.rs:130-156, 249-369, 409-445; ivf.rs:281-326;
@@ -67,9 +67,10 @@ def seq_sum(a, start=0.0):
 
 
 def rotate(P, r, block=256):
-    """[n][D] = dot(P[j], r_i), in row blocks (the broadcast product is n D d floats)"""
+    """[n][D] = dot(P[j], r_i), in row blocks (the broadcast product is n D d floats: at most 2^26 of them at a time)"""
     r = np.asarray(r, f32).reshape(-1, P.shape[1])
     out = np.empty((r.shape[0], P.shape[0]), f32)
+    block = max(1, min(block, (1 << 26) // (P.shape[0] * P.shape[1])))
     for i in range(0, r.shape[0], block):
         out[i:i + block] = dot16(P[None, :, :], r[i:i + block, None, :])
     return out
@@ -299,3 +300,180 @@ def sized_partitions(sizes, d, seed, dup_block=0):
         rows.append(r)
     x = np.concatenate(rows).astype(f32)
     return np.ascontiguousarray(x[rng.permutation(len(x))]), cent
+
+
+# ---- one partition whose storage order is chosen for one query -------------------------------------------------------------------
+# The scan kernel (rq.hip: rq_scan_kernel) reads a partition in chunks of CHUNK rows and sorts / truncates its candidates to k once more
+# than CHUNK of them have piled up: with every row a candidate the first truncation follows storage position 2 CHUNK - 1, and from
+# then on a row enters only with a key <= the k-th key of that truncation.  The orders below put rows where that threshold, and the
+# tie it may have cut, decide the answer.
+CHUNK = 256
+FIRST_CUT = 2 * CHUNK
+TIE = 40                               # copies in the tie block of tie_then_closer / tie_then_displaced
+ORDERS = {                             # order -> (rows of the partition, the k it is defined for)
+    "descending": (832, (2, 10, 128)),
+    "ascending": (832, (2, 10, 128)),
+    "staircase": (832, (2, 10, 128)),
+    "tie_then_closer": (813, (2, 10)),
+    "tie_then_displaced": (813, (2, 10)),
+    "tie_across_chunk": (813, (2, 10)),
+    "tie_wide": (813, (128,)),
+    "tie_across_remainder": (813, (2, 10)),
+}
+
+
+def kth_is_tied(keys, k):
+    """are more rows at the k-th smallest key than fit into k?  (the heap, not the order by position, then decides which stay)"""
+    s = np.sort(np.asarray(keys))
+    return len(s) > k and s[k - 1] == s[k]
+
+
+class _Redraw(Exception):
+    pass
+
+
+def ordered_partition(oracle, order, metric, k, d=64, prefiltered=False, seed=0, small=40):
+    """Partition 0 of two (explicit centroids 4 e_0, 4 e_1; partition 1 holds `small` rows, so that nprobes = 2 has something to
+    merge): ORDERS[order][0] rows stored in `order` for the design query q, by the keys of the branch the search will use --
+    Query.distance_all without a prefilter, Query.distance with an all-selected one.  A row's assignment, code and factors do not
+    depend on where it is stored; its distance does only through the packed / remainder split, so the last N % 32 rows (the ones
+    farthest by the remainder branch) are fixed first and only the rows before them are ordered.  Every property an order is for
+    is asserted here, on the keys recomputed from the final layout.  A draw in which two generated rows share a key, or in which
+    the heap of tie_then_closer happens to keep the k first rows by (key, position), is drawn again: the fixture returned has neither.
+    -> dict: x [N + small][d] (input order = storage order), cent [2][d], P, q [d], keys u32 [N] (order_key of the design query's
+    distance to partition 0's rows in storage order), cut_tie (more rows tie at the k-th key than fit into k), N"""
+    for draw in range(16):
+        try:
+            return _ordered_partition(oracle, order, metric, k, d, prefiltered, seed, small, draw)
+        except _Redraw:
+            pass
+    raise AssertionError("no usable draw")
+
+
+def _ordered_partition(oracle, order, metric, k, d, prefiltered, seed, small, draw):
+    N = ORDERS[order][0]
+    assert k in ORDERS[order][1] and 2 <= k and d >= 2
+    cent = np.zeros((2, d), f32)
+    cent[0, 0] = cent[1, 1] = 4.0
+    P = rotation(d, seed + 5)
+    rem = N % BATCH
+    head_n = N - rem
+    rng = np.random.default_rng([seed, k, int(prefiltered), list(ORDERS).index(order), int(metric == "dot"), draw])
+    gauss = lambda n: rng.standard_normal((n, d)).astype(f32) * f32(0.25)
+    rows, other, q = (cent[0] + gauss(N)).astype(f32), (cent[1] + gauss(small)).astype(f32), (cent[0] + gauss(1)[0] + gauss(1)[0]).astype(f32)
+    pr, pd = oracle.find_partitions(q[None], cent, 2, metric)
+    assert pr[0, 0] == 0, "the design query's nearest partition is partition 0"
+    calc = Query(q - cent[0], pd[0, 0], P, metric)
+    part, codes, add, scale = build(oracle, rows, cent, P, metric)
+    assert (part == 0).all()
+    if prefiltered:
+        kh = kt = order_key(calc.distance(codes, add, scale))
+    else:
+        kh = order_key(calc.finish(calc.raw_packed(codes), add, scale))
+        kt = order_key(calc.finish(calc.raw_f32(codes, 0.0), add, scale))
+    by_tail = np.argsort(kt, kind="stable")
+    tail = by_tail[head_n:]                                # the remainder rows: the farthest by the branch they will take
+    asc = by_tail[:head_n][np.argsort(kh[by_tail[:head_n]], kind="stable")]      # the rows before them, nearest first
+    if len(np.unique(np.concatenate([kh[asc], kt[tail]]))) != N:
+        raise _Redraw("two generated rows share a key")
+
+    def tie_block(j, copies, into_tail=0):
+        """the row at rank j becomes `copies` rows (the farthest rows are overwritten; `into_tail` of them in the remainder)"""
+        src = asc[j]
+        dst = np.concatenate([asc[head_n - (copies - 1 - into_tail):], tail[:into_tail]])
+        rows[dst] = rows[src]
+        rest = asc[j + 1:head_n - (copies - 1 - into_tail)]
+        return np.concatenate([[src], dst[:copies - 1 - into_tail]]), rest[rng.permutation(len(rest))]
+
+    if order == "descending":
+        assert rem == 0
+        head = asc[::-1]
+    elif order == "ascending":
+        assert rem == 0
+        head = asc
+    elif order == "staircase":
+        assert rem == 0
+        head = np.concatenate([asc[:k - 1], asc[k - 1:][::-1]])
+    elif order == "tie_then_closer":
+        j = k // 2
+        tie, rest = tie_block(j, TIE)
+        near = asc[:j]
+        head = np.concatenate([rest[:100], tie, rest[100:600 - TIE], near, rest[600 - TIE:]])
+    elif order == "tie_then_displaced":
+        j = k // 2                                             # nearer rows ahead of the first truncation; k more come after it
+        tie, rest = tie_block(j + k, TIE)
+        near, early = asc[:k], asc[k:k + j]
+        head = np.concatenate([rest[:100], tie, early, rest[100:600 - TIE - j], near, rest[600 - TIE - j:]])
+    elif order == "tie_across_chunk":
+        tie, rest = tie_block(k // 2, 13)
+        rest = np.concatenate([asc[:k // 2], rest])
+        rest = rest[rng.permutation(len(rest))]
+        head = np.concatenate([rest[:CHUNK - 6], tie, rest[CHUNK - 6:]])
+    elif order == "tie_wide":
+        tie, rest = tie_block(k // 2, 300)
+        rest = np.concatenate([asc[:k // 2], rest])
+        rest = rest[rng.permutation(len(rest))]
+        head = np.concatenate([rest[:100], tie, rest[100:]])
+    elif order == "tie_across_remainder":
+        assert rem == 13
+        tie, rest = tie_block(k // 2, 14, into_tail=7)
+        rest = np.concatenate([asc[:k // 2], rest])
+        rest = rest[rng.permutation(len(rest))]
+        head = np.concatenate([rest, tie])
+    else:
+        raise ValueError(order)
+    layout = np.concatenate([head, tail]).astype(np.int64)
+    assert len(layout) == N and len(np.unique(layout)) == N
+    x = np.ascontiguousarray(np.concatenate([rows[layout], other]).astype(f32))
+
+    # ---- the final layout, from scratch -------------------------------------------------------------------------------------------
+    part, codes, add, scale = build(oracle, x, cent, P, metric)
+    assert (part[:N] == 0).all() and (part[N:] == 1).all()
+    dist = calc.distance(codes[:N], add[:N], scale[:N]) if prefiltered else calc.distance_all(codes[:N], add[:N], scale[:N])
+    keys = order_key(dist)
+    where = np.empty(N, np.int64)
+    where[layout] = np.arange(N)                               # storage position of every generated row
+    kth = lambda upto: np.sort(keys[:upto])[k - 1]             # what a truncation after `upto` rows leaves as the threshold
+    assert N > FIRST_CUT + CHUNK, "the scan passes two chunks after its first truncation"
+    if order == "descending":
+        assert len(np.unique(keys)) == N
+        for p in range(FIRST_CUT, N):
+            assert keys[p] < keys[:p].min()                    # every later row enters, at rank 0
+    elif order == "ascending":
+        assert (keys[FIRST_CUT:] > kth(FIRST_CUT)).all()       # nothing enters after the first truncation
+    elif order == "staircase":
+        assert len(np.unique(keys)) == N
+        for p in range(FIRST_CUT, N):
+            s = np.sort(keys[:p])
+            assert s[k - 2] < keys[p] < s[k - 1]               # every later row is exactly the new k-th: the threshold falls step by step
+    else:
+        tk = keys[where[tie[0]]]
+        tied = np.nonzero(keys == tk)[0]
+    if order in ("tie_then_closer", "tie_then_displaced"):
+        assert len(tied) == TIE and (tied == where[tie]).all() and tied.max() < CHUNK
+        assert where[near].min() >= FIRST_CUT and (keys[where[near]] < tk).all()
+        first = np.sort(keys[:FIRST_CUT])
+        assert first[k - 1] == tk and first[k] == tk           # the first truncation cuts the tie
+        final = np.sort(keys)
+        if order == "tie_then_closer":
+            assert (keys < tk).sum() == k // 2 and final[k - 1] == tk and final[k] == tk
+            pos = np.arange(N, dtype=np.uint64)
+            heap = set(oracle.heap_topk(dist, pos, k)[0].tolist())
+            by_position = set(np.lexsort((pos, keys))[:k].tolist())
+            assert len(heap) == k
+            if heap == by_position:
+                raise _Redraw("the heap happens to keep the first copies by position")
+        else:
+            assert (keys < tk).sum() >= k and final[k - 1] < tk and final[k - 1] != final[k]
+    elif order == "tie_across_chunk":
+        assert (tied == np.arange(CHUNK - 6, CHUNK + 7)).all() and kth_is_tied(keys, k) and np.sort(keys)[k - 1] == tk
+    elif order == "tie_wide":
+        assert (tied == np.arange(100, 400)).all() and kth_is_tied(keys, k) and np.sort(keys)[k - 1] == tk
+    elif order == "tie_across_remainder":
+        copies = np.arange(head_n - 7, head_n + 7)
+        assert (x[copies] == x[copies[0]]).all()
+        if prefiltered:
+            assert (tied == copies).all() and kth_is_tied(keys, k) and np.sort(keys)[k - 1] == tk
+        else:
+            assert (tied == copies[:7]).all() and len(np.unique(keys[copies[7:]])) == 1      # two branches: two keys
+    return {"x": x, "cent": cent, "P": P, "q": q, "keys": keys, "cut_tie": bool(kth_is_tied(keys, k)), "N": N}

@@ -171,3 +171,32 @@ def test_ties_are_replayed(emulator, oracle):
     P = R.rotations(16, seed=1)["qr"]
     assert run_case(emulator, oracle, x, q, cent, P, "l2", 10, 2, rid) > 0
     assert run_case(emulator, oracle, x, q, cent, P, "l2", 128, 2, rid, prefilter=np.arange(int(rid.max()) + 1) % 3 != 0) > 0
+
+
+# ---- past two chunks: the mid-scan threshold and the ties it cuts (rq_spec.ordered_partition) ---------------------------------------
+@pytest.mark.parametrize("order,k,prefiltered", [("staircase", 10, False), ("tie_then_closer", 10, False), ("tie_wide", 128, True),
+                                                 ("tie_across_remainder", 10, False), ("tie_across_remainder", 10, True)])
+def test_scan_past_two_chunks(emulator, oracle, order, k, prefiltered):
+    """a partition of ~800 rows (four 256-row chunks) stored in an order chosen for the first query: after its first truncation the
+    scan admits rows by its threshold alone.  staircase: every later row is exactly the new k-th (a threshold one rank too tight loses
+    them); tie_then_closer: a tie cut at the first truncation is still the k-th key at the end; tie_wide: 300 copies over two chunks at
+    k = 128; tie_across_remainder: copies on both sides of the packed / remainder boundary, one key under a prefilter, two without"""
+    f = R.ordered_partition(oracle, order, "l2", k, prefiltered=prefiltered)
+    x, cent = f["x"], f["cent"]
+    q = np.ascontiguousarray(np.stack([f["q"], queries(x, cent, 1, seed=5)[0]]))
+    rid = R.permuted_ids(len(x), 4)
+    mask = np.ones(int(rid.max()) + 1, bool) if prefiltered else None
+    replays = run_case(emulator, oracle, x, q, cent, f["P"], "l2", k, 2, rid, prefilter=mask)
+    if f["cut_tie"]:
+        assert replays > 0
+    assert f["cut_tie"] or order in ("staircase", "tie_across_remainder")
+
+
+def test_d136(emulator, oracle):
+    """d = 136: eight full 16-blocks and a tail of 8 in every rotation dot, 17 code bytes per row (read byte by byte, rows not 16-byte
+    aligned), 34 tables; one query is a centroid (zero residual in that partition: qmin == qmax there, not in the others)"""
+    d = 136
+    x, cent = R.sized_partitions([33, 0, 97], d, seed=d)
+    q = queries(x, cent, 2, seed=7)
+    q[1] = cent[2]
+    run_case(emulator, oracle, x, q, cent, R.rotations(d, seed=6)["qr"], "l2", 10, 3, R.permuted_ids(len(x), 8))

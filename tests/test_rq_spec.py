@@ -116,6 +116,42 @@ def test_zero_residual_and_signed_zero_bits():
     assert sd[0] == 0.0 and np.signbit(sd[0])                 # the reference negates unwrap_or_default()
 
 
+# ---- the ordered partitions of the scan tests (rq_spec.ordered_partition asserts what each order is for) -------------------------
+ORDERED = [(order, k) for order, (_, ks) in R.ORDERS.items() for k in ks]
+
+
+def chunked_scan(keys, k, tight=0):
+    """the selection rq_scan_kernel makes over one partition, every row a candidate: candidates pile up chunk by chunk, are sorted by
+    (key, position) and cut to k once more than CHUNK are held, and from then on a row enters only with key <= the k-th key kept.
+    tight = 1 takes the (k - 1)-th key as that threshold: the fault a scan test must notice.  -> positions kept"""
+    held, thr = [], None
+    for base in range(0, len(keys), R.CHUNK):
+        held += [(int(keys[p]), p) for p in range(base, min(base + R.CHUNK, len(keys))) if thr is None or keys[p] <= thr]
+        if len(held) > R.CHUNK:
+            held = sorted(held)[:k]
+            thr = held[k - 1 - tight][0]
+    return [p for _, p in sorted(held)[:k]]
+
+
+@pytest.mark.parametrize("prefiltered", [False, True])
+@pytest.mark.parametrize("metric", ["l2", "dot"])
+@pytest.mark.parametrize("order,k", ORDERED)
+def test_ordered_partition(oracle, order, k, metric, prefiltered):
+    f = R.ordered_partition(oracle, order, metric, k, prefiltered=prefiltered)
+    keys, N = f["keys"], f["N"]
+    assert f["x"].shape == (N + 40, 64) and N == R.ORDERS[order][0] and N > R.FIRST_CUT + R.CHUNK
+    want = list(np.lexsort((np.arange(N), keys))[:k])
+    assert chunked_scan(keys, k) == want
+    if order == "staircase":
+        assert chunked_scan(keys, k, tight=1) != want          # a threshold one rank too tight loses the rows of the last chunk
+    if order in ("tie_then_closer", "tie_across_chunk", "tie_wide") or (order == "tie_across_remainder" and prefiltered):
+        assert f["cut_tie"]
+    if order in ("descending", "ascending", "staircase", "tie_then_displaced"):
+        assert not f["cut_tie"]
+    again = R.ordered_partition(oracle, order, metric, k, prefiltered=prefiltered)
+    assert (again["x"].view(np.uint32) == f["x"].view(np.uint32)).all() and (again["q"] == f["q"]).all()      # seeded: every caller gets the same
+
+
 RECALL_AT_10 = 0.2867
 
 
