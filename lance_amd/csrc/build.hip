@@ -285,6 +285,7 @@ lance_hip_index::~lance_hip_index() {
   }
   if (cq) {
     if (cq->cpl) (void)hipFree(cq->cpl);
+    if (cq->chi) (void)hipFree(cq->chi);
     if (cq->maxbits) (void)hipFree(cq->maxbits);
     delete cq;
   }

@@ -50,8 +50,12 @@ struct lance_hip_index {
   } *ms = nullptr;
   // find_partitions over thousands of lists (xform_fused.hip MODE 2): the centroids' bf16 planes [nlist ^ 64][2 d + 16] and max |c|^2, built by the
   // first such search (they were rebuilt by every call: 65,536 x 128 centroids are 35 MB of planes, ~0.25 of the batch's 1.2 ms sweep stage)
+  // Fewer lists than that route takes (coarse_fused_kernel, mfma_assign.hip): ma_prep_kernel's planes chi / clo [nlist][d] and |c|^2 [nlist ^ 64] in
+  // ONE allocation (chi), and the same maxima words -- an index has one shape or the other, so cpl or chi is set, never both
   struct CqConst {
     uint16_t *cpl = nullptr;
+    uint16_t *chi = nullptr, *clo = nullptr;   // clo and cn alias into chi's allocation
+    float *cn = nullptr;
     uint32_t *maxbits = nullptr;  // [4] words, [0] = max |c|^2 as float bits
   } *cq = nullptr;
   std::mutex lazy_mu;             // guards the creation of `pt` / `ms` / `cq` (several contexts / host threads may search one index)

@@ -176,8 +176,19 @@ int flat_topk_small(lance_hip_ctx *ctx, int metric, int dtype, const void *x, co
                     uint32_t nq, uint32_t k, uint64_t *ids, float *dists, bool *done);
 // mfma_assign.hip: the coarse quantiser at query time on the matrix cores (surrogate matrix + exact re-check of the candidates)
 bool coarse_mfma_supported(int metric, int d, uint32_t nq, uint32_t nlist, uint32_t nprobes, bool lanes32, const float *q, const float *cent);
+// fewer lists than the per-group route takes: sweep + select in one kernel (coarse_fused_kernel), which needs no [nq][nlist] matrix.  Its centroid
+// constants (ma_prep_kernel's planes, |c|^2 over nlist ^ 64 floats, maxima) are built per call or once per index (index.h CqConst)
+struct CoarseFusedConst {
+  const uint16_t *chi, *clo;   // [nlist][d] bf16 planes
+  const float *cn;             // [coarse_fused_cn_elems(nlist)]
+  const uint32_t *maxbits;     // [4] words, [0] = max |c|^2 as float bits
+};
+bool coarse_fused_shape(int d, uint32_t nlist);
+size_t coarse_fused_cn_elems(uint32_t nlist);
+int coarse_fused_planes(lance_hip_ctx *ctx, const float *cent, uint32_t nlist, int d, uint16_t *chi, uint16_t *clo, float *cn, uint32_t *maxbits /* zeroed */);
 int find_partitions_mfma(lance_hip_ctx *ctx, int metric, const float *q, uint32_t nq, int d, const float *cent, uint32_t nlist, uint32_t nprobes,
-                         float *matrix, uint32_t *part_ids, float *dists, const uint16_t *cpl_ready = nullptr, const uint32_t *maxbits_ready = nullptr);
+                         float *matrix, uint32_t *part_ids, float *dists, const uint16_t *cpl_ready = nullptr, const uint32_t *maxbits_ready = nullptr,
+                         const CoarseFusedConst *fused_ready = nullptr);
 int launch_normalize(lance_hip_ctx *ctx, const float *x, int64_t n, int d, float *out, bool f16);   // f16: half-precision arithmetic on f32 containers
 // the same, and the normalised rows once more as a binary16 plane x 2^14 (stride dp = d rounded up to 32) + the squared-norm bound per row
 int launch_normalize_planes(lance_hip_ctx *ctx, const float *x, int64_t n, int d, float *out, bool f16, uint16_t *plane16, int dp, float *n2);

@@ -937,6 +937,9 @@ int launch_assign_mfma(lance_hip_ctx *ctx, const PairwiseArgs &p, int d, int met
 //   bits; the margin is widened by 1/16): it is its group's key holder and that key is <= thr, or the group's SECOND key is <= thr --
 //   cand = { key holders of groups with key <= thr }  +  { all 16 members of groups whose second key is <= thr } (one query in seven has one).
 // Exact distances, sort and emission are unchanged; the exact-path fall-back writes its distances into the (otherwise untouched) matrix row.
+//
+// Up to 960 lists (C2: 256) neither kernel above runs: coarse_fused_kernel (below) sweeps and selects in one launch and keeps the surrogates in
+// LDS.  The matrix route is left with 961 .. 1023 lists, rows longer than 128 elements and LANCE_HIP_NO_COARSE_FUSED=1.
 constexpr int CS_CAP = 128;     // candidates per query (two per lane in the final sort)
 constexpr int CS_CAP_G = 512;   // ... with per-group keys: a group with two members in reach brings all sixteen (trained centroids of structureless data:
                                 // one query in a few thousand has ~100 centroids inside the margin, and its exact-path fall-back against 65,536
@@ -1187,6 +1190,287 @@ __global__ __launch_bounds__(256) void coarse_select_kernel(float *__restrict__ 
   }
 }
 
+// ---- fewer than ~1000 lists: sweep and select in ONE kernel, the surrogates never leave LDS ---------------------------------------
+// A 512-lane workgroup owns CF_ROWS = 32 queries (10,000 queries: 313 workgroups, two per CU fit).  Phase 1 stages their rows ONCE: as f32 (the
+// operand of the exact re-check) and split into bf16 hi / lo planes, all in LDS.  Phase 2: wave w sweeps the 32-centroid blocks w, w + 8, ..: per
+// k-step the A fragments (centroids) come straight from the prepared planes (<= 512 KB: they sit in L2), the B fragments (queries) from LDS, and the
+// same three MFMAs per block as ma_top3_kernel run.  The surrogates go to the LDS array sur[32][nlist ^ 64 + 4] (row stride = 4 mod 32 words: the
+// 16-byte writes of eight consecutive rows cover the 32 banks once); padding centroids are written as +inf.  After one barrier wave w selects for
+// rows w, w + 8, ..:
+//   T0   = the nprobes-th smallest of the 256 values "four smallest of every lane", taken by nprobes rounds of wave-wide minimum extraction
+//          (the lane that holds the minimum -- the lowest one on a tie -- pops it): these are distinct elements of the row, so at least nprobes
+//          distinct centroids have s <= T0.  The same T0 as coarse_select_kernel's network over the same 256 values, at ~20 instructions a probe;
+//   cand = { c < nlist : s(c) <= T0 + 2E },  2E = 2 * 2^-13 (|q|^2 + max|c|^2) (+ 2^-22 under dot) as in ma_top3_kernel (|q|^2 summed in another
+//          order, which only moves the margin by an ulp): every centroid of the reference's answer is in it (see the block comment above
+//          coarse_select_kernel: the argument only needs T0 to bound the nprobes-th smallest surrogate from above and E to dominate
+//          |s + const_q - dist_ref|);
+//   the candidates' distances come from cs_group_distance (dist_exact_rt's value), sixteen candidates' loads in flight at a time; the keys
+//   (order_key(dist) << 32) | centroid are unique, so a candidate's rank is the number of smaller keys -- the order the sorting network gave --
+//   and the ranks below nprobes are emitted.
+// A row whose surrogates hold a NaN, whose 2E is not finite or is <= 2 * 2^-100, or that has more than CS_CAP or fewer than nprobes candidates is
+// answered by the same wave from exact distances to ALL centroids (reference order), written over the row's LDS array; it counts itself in
+// n_exact_rows.  Rows beyond nq are staged as zeros and never selected or written.
+constexpr int CF_ROWS = 32;
+constexpr int CF_WAVES = 8;
+constexpr uint32_t CF_MAX_LISTS = 960;       // d = 128: 16.5 KB of f32 rows + 17 KB of bf16 planes (later the candidate lists) + 32 x 964 x 4 B = 120.5 KB of
+                                             // surrogates = 154 KB of the CU's 160 KB; 1024 lists would need 162 KB
+
+static size_t coarse_fused_lds(int d, uint32_t nlist) {
+  const size_t n64 = (size_t)cdiv(nlist, MA_CT) * MA_CT;
+  const size_t planes = (size_t)2 * CF_ROWS * (d + 8) * 2, cands = (size_t)CF_WAVES * CS_CAP * 12;
+  return (size_t)CF_ROWS * (d + 4) * 4 + std::max(planes, cands) + (size_t)CF_ROWS * (n64 + 4) * 4;
+}
+
+template <int CTRL, int ROW_MASK, bool SUM>
+__device__ __forceinline__ float cf_dpp_step(float v) {      // min / sum with the DPP source lane; lanes outside ROW_MASK or without a source keep v
+  const float ident = SUM ? 0.0f : v;
+  const float o = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, ident), __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xF, false));
+  return SUM ? v + o : fminf(v, o);
+}
+template <bool SUM>
+__device__ __forceinline__ float cf_wave_reduce(float v) {      // the minimum / a sum of the 64 lanes, on every lane (min: no NaNs among the operands)
+  v = cf_dpp_step<0xB1, 0xF, SUM>(v);       // quad_perm [1, 0, 3, 2]
+  v = cf_dpp_step<0x4E, 0xF, SUM>(v);       // quad_perm [2, 3, 0, 1]
+  v = cf_dpp_step<0x141, 0xF, SUM>(v);      // row_half_mirror
+  v = cf_dpp_step<0x140, 0xF, SUM>(v);      // row_mirror: every lane holds the result of its 16-lane row
+  v = cf_dpp_step<0x142, 0xA, SUM>(v);      // row_bcast:15 into rows 1 and 3
+  v = cf_dpp_step<0x143, 0xC, SUM>(v);      // row_bcast:31 into rows 2 and 3: lane 63 holds the wave's
+  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
+}
+
+template <int KS, int METRIC>
+__global__ __launch_bounds__(64 * CF_WAVES, 4) void coarse_fused_kernel(const float *__restrict__ q, int nq, const uint16_t *__restrict__ chi,
+                                                                       const uint16_t *__restrict__ clo, const float *__restrict__ cn /* [nlist ^ 64] */,
+                                                                       const uint32_t *__restrict__ maxbits, const float *__restrict__ cent, int nlist,
+                                                                       int nprobes, uint32_t *__restrict__ part_ids, float *__restrict__ dists,
+                                                                       uint32_t *__restrict__ n_exact_rows) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int D = KS * 16;
+  constexpr int XS = D + 4;          // f32 row stride of the staged queries
+  constexpr int CS = D + 8;          // bf16 row stride of a query plane (16-byte skew: conflict-free ds_read_b128)
+  constexpr size_t PLANES = (size_t)2 * CF_ROWS * CS * 2, CANDS = (size_t)CF_WAVES * CS_CAP * 12;
+  const int n64 = (nlist + MA_CT - 1) / MA_CT * MA_CT;
+  const int SP = n64 + 4;            // f32 row stride of the surrogates
+  float *xs = reinterpret_cast<float *>(smem);                                            // [CF_ROWS][XS]
+  uint16_t *xh = reinterpret_cast<uint16_t *>(xs + CF_ROWS * XS), *xl = xh + CF_ROWS * CS;      // [CF_ROWS][CS] each (phases 1 and 2)
+  unsigned long long *ck_all = reinterpret_cast<unsigned long long *>(xh);                // [CF_WAVES][CS_CAP] (key << 32) | centroid  (phase 3, same bytes)
+  uint32_t *cl_all = reinterpret_cast<uint32_t *>(ck_all + CF_WAVES * CS_CAP);            // [CF_WAVES][CS_CAP] candidate centroids
+  float *sur = reinterpret_cast<float *>(smem + (size_t)CF_ROWS * XS * 4 + (PLANES > CANDS ? PLANES : CANDS));      // [CF_ROWS][SP]
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, grp = lane >> 4;
+  const int j = lane & 31, g = lane >> 5;
+  const int64_t row0 = (int64_t)blockIdx.x * CF_ROWS;
+
+  // phase 1: eight consecutive elements per lane: f32 row + bf16 hi / lo planes
+  if ((int)threadIdx.x < CF_ROWS * (D / 8)) {
+    const int r = (int)threadIdx.x / (D / 8), c8 = (int)threadIdx.x - r * (D / 8);
+    f4 a = {0.0f, 0.0f, 0.0f, 0.0f}, b = a;
+    if (row0 + r < nq) { a = load4(q + (row0 + r) * D + 8 * c8); b = load4(q + (row0 + r) * D + 8 * c8 + 4); }
+    *reinterpret_cast<f4 *>(&xs[r * XS + 8 * c8]) = a;
+    *reinterpret_cast<f4 *>(&xs[r * XS + 8 * c8 + 4]) = b;
+    const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    bf16x8 h, l;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const uint32_t hb = bf16_rne_bits(v[e]);
+      const uint32_t lb = bf16_rne_bits(v[e] - bf16_bits_to_float(hb));
+      h[e] = (short)hb; l[e] = (short)lb;
+    }
+    *reinterpret_cast<bf16x8 *>(xh + r * CS + 8 * c8) = h;
+    *reinterpret_cast<bf16x8 *>(xl + r * CS + 8 * c8) = l;
+  }
+  __syncthreads();
+
+  // phase 2: this wave's 32-centroid blocks.  D[centroid i][row j]: lane (j, g) holds centroids i = (v & 3) + 8 (v >> 2) + 4 g of the block
+  const int nblocks = n64 / 32;
+  for (int blk = wave; blk < nblocks; blk += CF_WAVES) {
+    const int c0 = blk * 32;
+    const int ca = min(c0 + j, nlist - 1);      // (a padding centroid: any real one, overwritten with +inf below)
+    const uint16_t *ha = chi + (int64_t)ca * D + g * 8, *la = clo + (int64_t)ca * D + g * 8;
+    const uint16_t *bh = xh + j * CS + g * 8, *bl = xl + j * CS + g * 8;
+    bf16x8 ah[KS], al[KS];
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+      ah[s] = *reinterpret_cast<const bf16x8 *>(ha + s * 16);
+      al[s] = *reinterpret_cast<const bf16x8 *>(la + s * 16);
+    }
+    f32x16 acc;
+#pragma unroll
+    for (int v = 0; v < 16; ++v) acc[v] = 0.0f;
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+      const bf16x8 qh = *reinterpret_cast<const bf16x8 *>(bh + s * 16);
+      const bf16x8 ql = *reinterpret_cast<const bf16x8 *>(bl + s * 16);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[s], qh, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[s], ql, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[s], qh, acc, 0, 0, 0);
+    }
+    float *srow = sur + (size_t)j * SP;
+#pragma unroll
+    for (int vq = 0; vq < 4; ++vq) {
+      const int ib = c0 + 8 * vq + 4 * g;
+      const f4 cn4 = *reinterpret_cast<const f4 *>(cn + ib);
+      float o[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float dot = acc[vq * 4 + e];
+        float v = METRIC == METRIC_DOT ? -dot : __builtin_fmaf(-2.0f, dot, cn4[e]);
+        if (ib + e >= nlist) v = INFINITY;
+        o[e] = v;
+      }
+      *reinterpret_cast<f4 *>(srow + ib) = f4{o[0], o[1], o[2], o[3]};
+    }
+  }
+  __syncthreads();      // the surrogates are complete; the bf16 planes are dead: their bytes hold the candidate lists from here on
+
+  // phase 3: one row at a time per wave
+  unsigned long long *ck = ck_all + wave * CS_CAP;
+  uint32_t *cl = cl_all + wave * CS_CAP;
+  const float cmax2 = __uint_as_float(maxbits[0]);
+  for (int r = wave; r < CF_ROWS; r += CF_WAVES) {
+    const int64_t qi = row0 + r;
+    if (qi >= nq) break;                      // (wave-uniform; no workgroup-level barrier below)
+    float *row = sur + (size_t)r * SP;
+    const float *wrow = xs + r * XS;
+    float xn2 = 0.0f;
+    for (int e = lane; e < D; e += 64) xn2 += wrow[e] * wrow[e];
+    xn2 = cf_wave_reduce<true>(xn2);
+    // 2E, E = 2^-13 (|q|^2 + max|c|^2) (+ 2^-22 under dot: see ma_common.cuh)
+    const float E2 = 2.0f * 0.0001220703125f * (xn2 + cmax2) + (METRIC == METRIC_DOT ? 4.7683716e-7f : 0.0f);
+    bool bad = !(E2 < INFINITY) || !(E2 > 7.888609052210118e-31f);      // (2 * 2^-100 scale: products in the denormal range -> exact path)
+    float m0 = INFINITY, m1 = INFINITY, m2 = INFINITY, m3 = INFINITY;   // the four smallest values of the lane (a NaN never enters)
+    for (int base = 0; base < n64; base += 256) {
+      float v4[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) { const int i = base + 64 * u + lane; v4[u] = i < n64 ? row[i] : INFINITY; }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const float v = v4[u];
+        bad |= v != v;
+        if (v < m3) {
+          if (v < m2) {
+            m3 = m2;
+            if (v < m1) {
+              m2 = m1;
+              if (v < m0) { m1 = m0; m0 = v; } else m1 = v;
+            } else m2 = v;
+          } else m3 = v;
+        }
+      }
+    }
+    bad = __any(bad);
+    uint32_t cnt = 0;
+    if (!bad) {
+      float t0 = INFINITY;
+      for (int pr = 0; pr < nprobes; ++pr) {
+        t0 = cf_wave_reduce<false>(m0);
+        if (!(t0 < INFINITY)) break;          // fewer than nprobes finite values: the threshold is +inf
+        const unsigned long long holders = __ballot(m0 == t0);
+        if (lane == __ffsll((long long)holders) - 1) { m0 = m1; m1 = m2; m2 = m3; m3 = INFINITY; }
+      }
+      const float thr = t0 + E2;
+      for (int base = 0; base < nlist; base += 256) {
+        float v4[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { const int i = base + 64 * u + lane; v4[u] = i < nlist ? row[i] : INFINITY; }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int i = base + 64 * u + lane;
+          const bool take = i < nlist && v4[u] <= thr;
+          const unsigned long long mask = __ballot(take);
+          if (take) {
+            const uint32_t pos = cnt + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
+            if (pos < (uint32_t)CS_CAP) cl[pos] = (uint32_t)i;
+          }
+          cnt += (uint32_t)__popcll(mask);
+        }
+      }
+      if (cnt > (uint32_t)CS_CAP || cnt < (uint32_t)nprobes) bad = true;
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (bad) {
+      // exact distances to every centroid, written over the row; then the nprobes smallest (key, index) one after the other
+      if (lane == 0 && n_exact_rows) atomicAdd(n_exact_rows, 1u);
+      for (int c0 = 0; c0 < nlist; c0 += 4) {
+        const int c = c0 + grp;
+        float v = 0.0f;
+        if (c < nlist) v = cs_group_distance<METRIC>(wrow, cent + (int64_t)c * D, D, lane);
+        else (void)cs_group_distance<METRIC>(wrow, cent, D, lane);          // keep the shuffles wave-uniform
+        if (c < nlist && (lane & 15) == 0) row[c] = v;
+      }
+      __builtin_amdgcn_wave_barrier();
+      __threadfence_block();
+      unsigned long long last = 0ull;
+      bool have_last = false;
+      for (int pr = 0; pr < nprobes; ++pr) {
+        unsigned long long best = ~0ull;
+        for (int i = lane; i < nlist; i += 64) {
+          const unsigned long long kk = ((unsigned long long)order_key(row[i]) << 32) | (uint32_t)i;
+          if ((!have_last || kk > last) && kk < best) best = kk;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { const unsigned long long ob = __shfl_xor(best, o, 64); best = ob < best ? ob : best; }
+        if (lane == 0) {
+          part_ids[qi * nprobes + pr] = (uint32_t)best;
+          if (dists) dists[qi * nprobes + pr] = key_to_float((uint32_t)(best >> 32));
+        }
+        last = best; have_last = true;
+      }
+      continue;
+    }
+    // exact distances of the candidates: sixteen per round (four per 16-lane group), their loads in flight together
+    for (uint32_t c0 = 0; c0 < cnt; c0 += 16) {
+      uint32_t cc[4];
+      float dv[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) { const uint32_t ci = c0 + 4 * u + (uint32_t)grp; cc[u] = ci < cnt ? cl[ci] : cl[0]; }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) dv[u] = cs_group_distance<METRIC>(wrow, cent + (int64_t)cc[u] * D, D, lane);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const uint32_t ci = c0 + 4 * u + (uint32_t)grp;
+        if (ci < cnt && (lane & 15) == 0) ck[ci] = ((unsigned long long)order_key(dv[u]) << 32) | cc[u];
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+    // rank = number of smaller keys (unique: the centroid is part of the key); lane holds candidates lane and lane + 64
+    const unsigned long long k0 = (uint32_t)lane < cnt ? ck[lane] : ~0ull, k1 = 64u + (uint32_t)lane < cnt ? ck[64 + lane] : ~0ull;
+    uint32_t rank0 = 0, rank1 = 0;
+    for (uint32_t i = 0; i < cnt; i += 4) {      // four LDS reads in flight (all lanes read the same address: a broadcast)
+      unsigned long long o[4];
+#pragma unroll
+      for (uint32_t u = 0; u < 4; ++u) o[u] = i + u < cnt ? ck[i + u] : ~0ull;      // (~0 is below no key)
+#pragma unroll
+      for (uint32_t u = 0; u < 4; ++u) {
+        rank0 += o[u] < k0 ? 1u : 0u;
+        rank1 += o[u] < k1 ? 1u : 0u;
+      }
+    }
+    if ((uint32_t)lane < cnt && rank0 < (uint32_t)nprobes) {
+      part_ids[qi * nprobes + rank0] = (uint32_t)k0;
+      if (dists) dists[qi * nprobes + rank0] = key_to_float((uint32_t)(k0 >> 32));
+    }
+    if (64u + (uint32_t)lane < cnt && rank1 < (uint32_t)nprobes) {
+      part_ids[qi * nprobes + rank1] = (uint32_t)k1;
+      if (dists) dists[qi * nprobes + rank1] = key_to_float((uint32_t)(k1 >> 32));
+    }
+    __builtin_amdgcn_wave_barrier();          // the next row reuses cl / ck
+  }
+}
+
+template <int KS>
+static void coarse_launch_fused(lance_hip_ctx *ctx, int metric, const float *q, uint32_t nq, const uint16_t *chi, const uint16_t *clo, const float *cn,
+                                const uint32_t *maxbits, const float *cent, uint32_t nlist, uint32_t nprobes, uint32_t *part_ids, float *dists,
+                                uint32_t *n_exact_rows) {
+  const size_t lds = coarse_fused_lds(KS * 16, nlist);
+  const dim3 grid((unsigned)cdiv(nq, CF_ROWS));
+  if (metric == METRIC_DOT)
+    hipLaunchKernelGGL((coarse_fused_kernel<KS, METRIC_DOT>), grid, dim3(64 * CF_WAVES), lds, ctx->stream, q, (int)nq, chi, clo, cn, maxbits, cent, (int)nlist,
+                       (int)nprobes, part_ids, dists, n_exact_rows);
+  else
+    hipLaunchKernelGGL((coarse_fused_kernel<KS, METRIC_L2>), grid, dim3(64 * CF_WAVES), lds, ctx->stream, q, (int)nq, chi, clo, cn, maxbits, cent, (int)nlist,
+                       (int)nprobes, part_ids, dists, n_exact_rows);
+}
+
 bool coarse_mfma_supported(int metric, int d, uint32_t nq, uint32_t nlist, uint32_t nprobes, bool lanes32, const float *q, const float *cent) {
   static const char *env = getenv("LANCE_HIP_MFMA_COARSE");      // "0": off, "1": on for every shape the kernels take
   static const bool off = env && env[0] == '0', force = env && env[0] == '1';
@@ -1228,8 +1512,68 @@ bool coarse_groups_shape(int d, uint32_t nlist) {
   return !ma && d <= 128 && d % 16 == 0 && coarse_groups_from() > 0 && nlist >= (uint32_t)std::max(coarse_groups_from(), 256);
 }
 
+// Below the per-group route's first list count: the fused kernel.  LANCE_HIP_NO_COARSE_FUSED=1 (read once): the two-kernel route, for A/B runs.
+bool coarse_fused_shape(int d, uint32_t nlist) {
+  static const bool off = getenv("LANCE_HIP_NO_COARSE_FUSED") != nullptr && getenv("LANCE_HIP_NO_COARSE_FUSED")[0] == '1';
+  return !off && d >= 16 && d <= 128 && d % 16 == 0 && nlist >= 32 && nlist <= CF_MAX_LISTS && !coarse_groups_shape(d, nlist) &&
+         coarse_fused_lds(d, nlist) <= (size_t)160 * 1024;
+}
+size_t coarse_fused_cn_elems(uint32_t nlist) { return (size_t)cdiv(nlist, MA_CT) * MA_CT; }
+int coarse_fused_planes(lance_hip_ctx *ctx, const float *cent, uint32_t nlist, int d, uint16_t *chi, uint16_t *clo, float *cn, uint32_t *maxbits) {
+  hipLaunchKernelGGL(ma_prep_kernel, dim3(nlist), dim3(64), 0, ctx->stream, cent, (int)nlist, d, d, nullptr, chi, clo, cn, maxbits, nullptr);
+  LH_CHECK_HIP(hipGetLastError());
+  return LANCE_HIP_OK;
+}
+
+static int find_partitions_fused(lance_hip_ctx *ctx, int metric, const float *q, uint32_t nq, int d, const float *cent, uint32_t nlist, uint32_t nprobes,
+                                 uint32_t *part_ids, float *dists, const CoarseFusedConst *ready) {
+  uint32_t *maxbits = ctx->scratch_t<uint32_t>("cq.maxbits", 4);   // [0] max |c|^2 (per-call prep only), [2] rows answered by the exact path
+  if (!maxbits) return LANCE_HIP_ENOMEM;
+  static const bool stats = getenv("LANCE_HIP_COARSE_STATS") != nullptr;
+  const uint16_t *chi, *clo;
+  const float *cn;
+  const uint32_t *mb;
+  ScopedTimer t(ctx, "select_probes");
+  ctx->count_stage("coarse_fused");
+  if (ready) {      // constants of the index: nothing to prepare; the exact-path counter is only cleared when somebody reads it
+    chi = ready->chi; clo = ready->clo; cn = ready->cn; mb = ready->maxbits;
+    if (stats) LH_CHECK_HIP(lh::memset_async(maxbits, 0, 16, ctx->stream));
+  } else {
+    uint16_t *h = ctx->scratch_t<uint16_t>("cq.chi", (size_t)nlist * d), *l = ctx->scratch_t<uint16_t>("cq.clo", (size_t)nlist * d);
+    float *n = ctx->scratch_t<float>("cq.cn", coarse_fused_cn_elems(nlist));
+    if (!h || !l || !n) return LANCE_HIP_ENOMEM;
+    ctx->count_stage("coarse_fused_prep");      // (tests: an index with cached constants never comes here)
+    LH_CHECK_HIP(lh::memset_async(maxbits, 0, 16, ctx->stream));
+    LH_TRY(coarse_fused_planes(ctx, cent, nlist, d, h, l, n, maxbits));
+    chi = h; clo = l; cn = n; mb = maxbits;
+  }
+  switch (d / 16) {
+    case 1: coarse_launch_fused<1>(ctx, metric, q, nq, chi, clo, cn, mb, cent, nlist, nprobes, part_ids, dists, maxbits + 2); break;
+    case 2: coarse_launch_fused<2>(ctx, metric, q, nq, chi, clo, cn, mb, cent, nlist, nprobes, part_ids, dists, maxbits + 2); break;
+    case 3: coarse_launch_fused<3>(ctx, metric, q, nq, chi, clo, cn, mb, cent, nlist, nprobes, part_ids, dists, maxbits + 2); break;
+    case 4: coarse_launch_fused<4>(ctx, metric, q, nq, chi, clo, cn, mb, cent, nlist, nprobes, part_ids, dists, maxbits + 2); break;
+    case 5: coarse_launch_fused<5>(ctx, metric, q, nq, chi, clo, cn, mb, cent, nlist, nprobes, part_ids, dists, maxbits + 2); break;
+    case 6: coarse_launch_fused<6>(ctx, metric, q, nq, chi, clo, cn, mb, cent, nlist, nprobes, part_ids, dists, maxbits + 2); break;
+    case 7: coarse_launch_fused<7>(ctx, metric, q, nq, chi, clo, cn, mb, cent, nlist, nprobes, part_ids, dists, maxbits + 2); break;
+    case 8: coarse_launch_fused<8>(ctx, metric, q, nq, chi, clo, cn, mb, cent, nlist, nprobes, part_ids, dists, maxbits + 2); break;
+    default: return LANCE_HIP_EINVAL;
+  }
+  LH_CHECK_HIP(hipGetLastError());
+  if (stats && !ctx->capturing) {
+    uint32_t h[4];
+    LH_CHECK_HIP(hipMemcpyAsync(h, maxbits, 16, hipMemcpyDeviceToHost, ctx->stream));
+    LH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    fprintf(stderr, "[coarse] nq=%u nlist=%u nprobes=%u fused=1: %u queries took the exact path\n", nq, nlist, nprobes, h[2]);
+  }
+  return LANCE_HIP_OK;
+}
+
+// matrix: NULL on calls the fused kernel serves (coarse_fused_shape); fused_ready: the index's constants for it, or NULL (per-call prep)
 int find_partitions_mfma(lance_hip_ctx *ctx, int metric, const float *q, uint32_t nq, int d, const float *cent, uint32_t nlist, uint32_t nprobes,
-                         float *matrix, uint32_t *part_ids, float *dists, const uint16_t *cpl_ready, const uint32_t *maxbits_ready) {
+                         float *matrix, uint32_t *part_ids, float *dists, const uint16_t *cpl_ready, const uint32_t *maxbits_ready,
+                         const CoarseFusedConst *fused_ready) {
+  if (coarse_fused_shape(d, nlist)) return find_partitions_fused(ctx, metric, q, nq, d, cent, nlist, nprobes, part_ids, dists, fused_ready);
+  LH_REQUIRE(matrix, "find_partitions: no matrix scratch for a shape the fused kernel does not serve");
   const bool wide = d > 128;
   const int dp = wide ? (d + MW_KC - 1) / MW_KC * MW_KC : d;
   const size_t kd = (size_t)nlist * dp;

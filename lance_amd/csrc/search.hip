@@ -1036,19 +1036,29 @@ static bool raw_compact_enabled() {
   static const bool off = getenv("LANCE_HIP_NO_RAW_COMPACT") != nullptr;      // A/B switch: always refine from the caller's column
   return !off;
 }
-// find_partitions over thousands of lists: the centroids' bf16 planes as constants of the index (index.h CqConst).  Built by the first
-// uncaptured search of such an index or by lance_hip_index_prewarm; no memory for them, or a capture in progress: the call builds its own.
+// find_partitions on the matrix cores: the centroids' bf16 planes as constants of the index (index.h CqConst) -- the per-group route's planes over
+// thousands of lists, the fused kernel's below that.  Built by the first uncaptured search of such an index or by lance_hip_index_prewarm; no memory
+// for them, or a capture in progress: the call builds its own.
 int coarse_planes_prepare(lance_hip_ctx *ctx, const lance_hip_index *ix_c, int scan_metric) {
   lance_hip_index *ix = const_cast<lance_hip_index *>(ix_c);
   std::lock_guard<std::mutex> lk(ix->lazy_mu);
   if (ix->cq || ctx->capturing) return LANCE_HIP_OK;
+  const bool fused = coarse_fused_shape((int)ix->d, ix->nlist);
   auto *cq = new lance_hip_index::CqConst();
-  bool ok = hipMalloc(reinterpret_cast<void **>(&cq->cpl), xform_coarse_planes_elems(ix->nlist, (int)ix->d) * 2) == hipSuccess;
+  const size_t kd = (size_t)ix->nlist * ix->d;
+  bool ok;
+  if (fused) {
+    ok = hipMalloc(reinterpret_cast<void **>(&cq->chi), kd * 2 * 2 + coarse_fused_cn_elems(ix->nlist) * 4) == hipSuccess;
+    if (ok) { cq->clo = cq->chi + kd; cq->cn = reinterpret_cast<float *>(cq->clo + kd); }      // (d % 16 == 0: the offsets are multiples of 32 bytes)
+  } else {
+    ok = hipMalloc(reinterpret_cast<void **>(&cq->cpl), xform_coarse_planes_elems(ix->nlist, (int)ix->d) * 2) == hipSuccess;
+  }
   ok = ok && hipMalloc(reinterpret_cast<void **>(&cq->maxbits), 16) == hipSuccess;
-  auto drop = [&]() { if (cq->cpl) (void)hipFree(cq->cpl); if (cq->maxbits) (void)hipFree(cq->maxbits); delete cq; };
+  auto drop = [&]() { if (cq->cpl) (void)hipFree(cq->cpl); if (cq->chi) (void)hipFree(cq->chi); if (cq->maxbits) (void)hipFree(cq->maxbits); delete cq; };
   if (!ok) { (void)hipGetLastError(); drop(); return LANCE_HIP_OK; }
   if (lh::memset_async(cq->maxbits, 0, 16, ctx->stream) != hipSuccess ||
-      xform_coarse_planes(ctx, scan_metric, ix->centroids, ix->nlist, (int)ix->d, cq->cpl, cq->maxbits) != LANCE_HIP_OK ||
+      (fused ? coarse_fused_planes(ctx, ix->centroids, ix->nlist, (int)ix->d, cq->chi, cq->clo, cq->cn, cq->maxbits)
+             : xform_coarse_planes(ctx, scan_metric, ix->centroids, ix->nlist, (int)ix->d, cq->cpl, cq->maxbits)) != LANCE_HIP_OK ||
       hipStreamSynchronize(ctx->stream) != hipSuccess) {      // (other contexts search the same index: published complete)
     drop();
     set_error("find_partitions: building the centroid planes of the index failed");
@@ -1544,19 +1554,25 @@ static int ivfpq_search_enqueue_impl(lance_hip_ctx *ctx, const lance_hip_index *
   if (q_stats && plan.route != ROUTE_QUANTISED) fprintf(stderr, "[plan] nq=%u nprobes=%u keff=%u route %d: %s\n", nq, nprobes, keff, (int)plan.route, plan.why);
   if (qn) LH_TRY(launch_normalize(ctx, q, (int64_t)nq, d, qn, ix->dtype == LANCE_HIP_F16));   // an f16 key is normalised in f16 arithmetic
   // coarse quantiser: all distances, then per-query partial sort
-  float *matrix = ctx->scratch_t<float>("search.matrix", (size_t)nq * nlist);
-  uint32_t *probes = ctx->scratch_t<uint32_t>("search.probes", (size_t)nq * nprobes);
-  if (!matrix || !probes) return LANCE_HIP_ENOMEM;
   const bool coarse_l32 = ix->dtype == LANCE_HIP_F16 && scan_metric == LANCE_HIP_DOT && d > 16;
-  if (coarse_mfma_supported(scan_metric, d, nq, (uint32_t)nlist, nprobes, coarse_l32, qs, ix->centroids)) {
-    // kmeans.rs:1134-1158 on the matrix cores: bf16x3 surrogate matrix, exact re-check of the nprobes + few candidates
+  const bool coarse_mfma = coarse_mfma_supported(scan_metric, d, nq, (uint32_t)nlist, nprobes, coarse_l32, qs, ix->centroids);
+  const bool coarse_fused = coarse_mfma && coarse_fused_shape(d, (uint32_t)nlist);      // keeps its surrogates in LDS: no [nq][nlist] matrix
+  float *matrix = coarse_fused ? nullptr : ctx->scratch_t<float>("search.matrix", (size_t)nq * nlist);
+  uint32_t *probes = ctx->scratch_t<uint32_t>("search.probes", (size_t)nq * nprobes);
+  if ((!matrix && !coarse_fused) || !probes) return LANCE_HIP_ENOMEM;
+  if (coarse_mfma) {
+    // kmeans.rs:1134-1158 on the matrix cores: bf16x3 surrogates, exact re-check of the nprobes + few candidates
     const uint16_t *cpl = nullptr;
     const uint32_t *cmb = nullptr;
-    if (coarse_groups_shape(d, (uint32_t)nlist)) {      // thousands of lists: the centroids' bf16 planes are constants of the index
+    CoarseFusedConst cf{};
+    bool have_cf = false;
+    if (coarse_fused || coarse_groups_shape(d, (uint32_t)nlist)) {      // the centroids' bf16 planes are constants of the index
       LH_TRY(coarse_planes_prepare(ctx, ix, scan_metric));
-      if (ix->cq) { cpl = ix->cq->cpl; cmb = ix->cq->maxbits; }
+      if (ix->cq && coarse_fused) { cf = CoarseFusedConst{ix->cq->chi, ix->cq->clo, ix->cq->cn, ix->cq->maxbits}; have_cf = true; }
+      else if (ix->cq) { cpl = ix->cq->cpl; cmb = ix->cq->maxbits; }
     }
-    LH_TRY(find_partitions_mfma(ctx, scan_metric, qs, nq, d, ix->centroids, (uint32_t)nlist, nprobes, matrix, probes, nullptr, cpl, cmb));
+    LH_TRY(find_partitions_mfma(ctx, scan_metric, qs, nq, d, ix->centroids, (uint32_t)nlist, nprobes, matrix, probes, nullptr, cpl, cmb,
+                                have_cf ? &cf : nullptr));
   } else {
     PairwiseArgs pa;
     pa.x = qs; pa.n = nq; pa.ldx = d; pa.cent = ix->centroids; pa.k = nlist; pa.matrix = matrix;
@@ -1668,10 +1684,12 @@ int find_partitions_f32(lance_hip_ctx *ctx, int metric, const float *qf, uint32_
   if (nprobes > nlist) nprobes = nlist;
   LH_REQUIRE(nlist <= 8192 || nprobes <= 2048, "find_partitions: nprobes=%u > 2048 with more than 8192 partitions is not supported", nprobes);
   if (nq == 0 || nprobes == 0) return LANCE_HIP_OK;
-  float *matrix = ctx->scratch_t<float>("search.matrix", (size_t)nq * nlist);
-  if (!matrix) return LANCE_HIP_ENOMEM;
   const int km = metric == LANCE_HIP_COSINE ? LANCE_HIP_L2 : metric;
-  if (coarse_mfma_supported(km, (int)d, nq, nlist, nprobes, lanes32, qf, cf)) {
+  const bool mfma = coarse_mfma_supported(km, (int)d, nq, nlist, nprobes, lanes32, qf, cf);
+  const bool fused = mfma && coarse_fused_shape((int)d, nlist);      // keeps its surrogates in LDS: no [nq][nlist] matrix
+  float *matrix = fused ? nullptr : ctx->scratch_t<float>("search.matrix", (size_t)nq * nlist);
+  if (!matrix && !fused) return LANCE_HIP_ENOMEM;
+  if (mfma) {
     LH_TRY(find_partitions_mfma(ctx, km, qf, nq, (int)d, cf, nlist, nprobes, matrix, part_ids, dists));
   } else {
     PairwiseArgs pa;
@@ -1715,7 +1733,7 @@ int lance_hip_index_prewarm(lance_hip_ctx *ctx, lance_hip_index *idx) {
   LH_REQUIRE(ctx && idx, "index_prewarm: NULL argument");
   LH_CHECK_HIP(hipSetDevice(ctx->device));
   if (idx->m > 0 && !plan_index_ms_refusal(plan_index(idx, nullptr), plan_switches_from_env())) LH_TRY(mscan_prepare(ctx, idx));   // the search's own rule
-  if (coarse_groups_shape((int)idx->d, idx->nlist) && (reinterpret_cast<uintptr_t>(idx->centroids) & 15) == 0)
+  if ((coarse_groups_shape((int)idx->d, idx->nlist) || coarse_fused_shape((int)idx->d, idx->nlist)) && (reinterpret_cast<uintptr_t>(idx->centroids) & 15) == 0)
     LH_TRY(coarse_planes_prepare(ctx, idx, idx->metric == LANCE_HIP_COSINE ? LANCE_HIP_L2 : idx->metric));
   (void)raw_compact_prepare(ctx, idx);      // nullptr = the column stays f32 (not integer-valued, or not an f32 L2 / dot index): not an error
   LH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
