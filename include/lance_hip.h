@@ -254,7 +254,10 @@ int lance_hip_index_from_storage(lance_hip_ctx *ctx, int dtype, int metric, uint
                                  const uint64_t *row_ids, uint64_t n, lance_hip_index **out);
 void lance_hip_index_destroy(lance_hip_index *idx);
 /* Optional raw vectors for refine (scanner.rs:2884-2904 `take` + flat_knn): x[n_raw][d],
- * indexed by row id (row id r -> x[r]); borrowed, must outlive the index and must not
+ * indexed by row id (row id r -> x[r]); the element type is the handle's dtype (IVF_PQ,
+ * IVF_SQ: the column's; IVF_RQ: f32).  IVF_SQ and IVF_RQ handles take them too (for
+ * lance_hip_ivfsq_search_refine / lance_hip_ivfrq_search_refine); for a cosine IVF_SQ index
+ * they are the ORIGINAL rows, not the normalised ones.  Borrowed, must outlive the index and must not
  * change while attached: the engine may keep a lossless compact copy of it (an f32 column
  * whose every element is an integer in [0, 255] is read as bytes by the refine kernel) and
  * captured searches hold its address.  After changing the contents call set_raw again
@@ -452,6 +455,23 @@ int lance_hip_ivfrq_search(lance_hip_ctx *ctx, const lance_hip_index *idx, const
  * quantised one), tested inside the scan and the replay kernel; k <= 128. */
 int lance_hip_ivfrq_search_filtered(lance_hip_ctx *ctx, const lance_hip_index *idx, const float *q, uint32_t nq, uint32_t k,
                                     uint32_t nprobes, const uint8_t *allow_by_rowid, uint64_t n_allow, uint64_t *ids, float *dists);
+
+/* ---- re-ranking for IVF_SQ and IVF_RQ (scanner.rs:2884-2904: the ANN node is asked for k * refine_factor rows, knn.rs:642, the rows
+ * are taken by row id and re-scored by flat_knn in the index's metric with the original query) ------------------------------------
+ * keff = k * refine_factor, 1 <= keff <= LANCE_HIP_SQRQ_MAX_CANDIDATES; refine_factor = 0 is refused (scanner.rs:2869).  First the
+ * search of that index type with k = keff: a heap of keff per probed partition, the (dist, rowid) merge with fetch keff, the same
+ * arithmetic branches, prefilter branch (allow_by_rowid != NULL) and tie replay as lance_hip_ivf{sq,rq}_search[_filtered] -- through
+ * the same kernels up to keff = 128, through their wide-capacity counterparts beyond.  Then the keff row ids are scored against the
+ * raw vectors (lance_hip_index_set_raw; without them: LANCE_HIP_EINVAL) with the ORIGINAL query -- for a cosine IVF_SQ index not the
+ * normalised copy the quantiser sees, for an f16 index widened --, ordered by (exact dist, rowid), and the first k are returned;
+ * missing slots are id ~0 and distance +inf.  A stored row id >= n_raw is an error (LANCE_HIP_EINVAL), never ranked.           */
+#define LANCE_HIP_SQRQ_MAX_CANDIDATES 768
+int lance_hip_ivfsq_search_refine(lance_hip_ctx *ctx, const lance_hip_index *idx, const void *q, uint32_t nq, uint32_t k,
+                                  uint32_t nprobes, uint32_t refine_factor, const uint8_t *allow_by_rowid /* NULL = none */,
+                                  uint64_t n_allow, uint64_t *ids, float *dists);
+int lance_hip_ivfrq_search_refine(lance_hip_ctx *ctx, const lance_hip_index *idx, const float *q, uint32_t nq, uint32_t k,
+                                  uint32_t nprobes, uint32_t refine_factor, const uint8_t *allow_by_rowid /* NULL = none */,
+                                  uint64_t n_allow, uint64_t *ids, float *dists);
 
 /* ---- N5: 8-bit scalar quantisation and IVF_SQ (lance-index/src/vector/sq.rs, sq/storage.rs, sq/builder.rs) ------------ */
 /* Columns are LANCE_HIP_F32 or LANCE_HIP_F16 (an int8 column is refused: the reference's SQ builder takes float arrays only; f64

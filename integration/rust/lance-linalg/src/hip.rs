@@ -125,6 +125,12 @@ extern "C" {
         ids: *mut u64, dists: *mut f32) -> i32;
     pub fn lance_hip_ivfrq_search_filtered(ctx: *mut LanceHipCtx, idx: *const LanceHipIndex, q: *const f32, nq: u32, k: u32,
         nprobes: u32, allow_by_rowid: *const u8, n_allow: u64, ids: *mut u64, dists: *mut f32) -> i32;
+    // re-ranking for IVF_SQ / IVF_RQ (scanner.rs:2884-2904): k * refine_factor <= 768 candidates by the quantised distance, re-scored against
+    // the raw vectors (lance_hip_index_set_raw) with the original query; allow_by_rowid NULL = no prefilter
+    pub fn lance_hip_ivfsq_search_refine(ctx: *mut LanceHipCtx, idx: *const LanceHipIndex, q: *const c_void, nq: u32, k: u32,
+        nprobes: u32, refine_factor: u32, allow_by_rowid: *const u8, n_allow: u64, ids: *mut u64, dists: *mut f32) -> i32;
+    pub fn lance_hip_ivfrq_search_refine(ctx: *mut LanceHipCtx, idx: *const LanceHipIndex, q: *const f32, nq: u32, k: u32,
+        nprobes: u32, refine_factor: u32, allow_by_rowid: *const u8, n_allow: u64, ids: *mut u64, dists: *mut f32) -> i32;
     // index maintenance (optimize_indices: ivf.rs:355-560, builder.rs:685-935; remap: builder.rs:256-359): every call returns a new
     // handle and leaves its sources untouched; new_ids[i] == u64::MAX (LANCE_HIP_ROW_DELETED) drops the row
     pub fn lance_hip_index_merge(ctx: *mut LanceHipCtx, srcs: *const *const LanceHipIndex, n_srcs: u32,

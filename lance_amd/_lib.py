@@ -37,6 +37,7 @@ SYMBOLS = [
     "lance_hip_search_stats", "lance_hip_ivfpq_search_filtered", "lance_hip_ivfpq_search_filtered_range",
     "lance_hip_flat_topk", "lance_hip_multivec_distance", "lance_hip_flat_multivec_topk", "lance_hip_ivfflat_create", "lance_hip_ivfflat_search", "lance_hip_ivfflat_search_filtered",
     "lance_hip_sq_bounds", "lance_hip_sq_encode", "lance_hip_sq_distance", "lance_hip_ivfsq_create", "lance_hip_ivfsq_search", "lance_hip_ivfsq_search_filtered",
+    "lance_hip_ivfsq_search_refine", "lance_hip_ivfrq_search_refine",
     "lance_hip_rq_encode", "lance_hip_rq_distance", "lance_hip_ivfrq_create", "lance_hip_ivfrq_search", "lance_hip_ivfrq_search_filtered",
     "lance_hip_index_file_open", "lance_hip_index_file_get", "lance_hip_index_file_close", "lance_hip_index_file_write",
     "lance_hip_index_load", "lance_hip_index_load_lists", "lance_hip_index_save", "lance_hip_file_read_column",
@@ -156,6 +157,8 @@ def load():
         "lance_hip_ivfrq_create": (i32, [vp, i32, u32, vp, u32, vp, vp, vp, vp, vp, vp, u64, C.POINTER(vp)]),
         "lance_hip_ivfrq_search": (i32, [vp, vp, vp, u32, u32, u32, vp, vp]),
         "lance_hip_ivfrq_search_filtered": (i32, [vp, vp, vp, u32, u32, u32, vp, u64, vp, vp]),
+        "lance_hip_ivfsq_search_refine": (i32, [vp, vp, vp, u32, u32, u32, u32, vp, u64, vp, vp]),
+        "lance_hip_ivfrq_search_refine": (i32, [vp, vp, vp, u32, u32, u32, u32, vp, u64, vp, vp]),
         "lance_hip_index_file_open": (i32, [C.c_char_p, C.POINTER(vp)]),
         "lance_hip_index_file_get": (i32, [vp, C.POINTER(IndexFileView)]),
         "lance_hip_index_file_close": (None, [vp]),

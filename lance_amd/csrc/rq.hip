@@ -30,6 +30,7 @@
 #include "index.h"
 #include "kernels.h"
 #include "search_common.cuh"
+#include "wide_cand.cuh"
 
 #pragma clang fp contract(off)
 
@@ -500,6 +501,83 @@ static int rq_transposed(lance_hip_ctx *ctx, const float *rotation, uint32_t d, 
 static size_t rq_scan_lds(uint32_t d) { return (size_t)20 * d + (size_t)RQ_BUF * 16 + sizeof(RqQuery) + sizeof(RqCtl); }
 static size_t rq_exact_lds(uint32_t d) { return (size_t)24 * d + RQ_MAX_K * 12 + (RQ_MAX_K + 4) * 8 + 64 * 4 + sizeof(RqQuery) + 16; }
 
+// ---- wide candidates (wide_cand.cuh): device code ---------------------------------------------------------------------------------
+// keff = k * refine_factor above RQ_MAX_K: the scan / replay of IVF_RQ at the wide capacity, with the narrow kernels' preparation and
+// row distance (the same three branches)
+struct RqWideArgs {
+  const uint8_t *codes;          // [n][cb] partition-ordered
+  const float *add, *scale;      // [n]
+  const float *pdists;           // [nq][nprobes] dist_q_c of every pair
+  const float *q;                // [nq][d]
+  const float *cent;             // [nlist][d]
+  const float *pt;               // [d][d] rotation, transposed
+  int d, dot;
+  float sqrt_d;
+  WideLists w;
+};
+
+// dynamic LDS: table 16 d | etab 4 d | u64 entries [w.cap] | RqQuery | WideCtl.  During the preparation the first 4 d bytes of the
+// entries hold the rotated query (4 d <= 8 w.cap: d <= RQ_MAX_DIM = 2048, w.cap >= 1024).
+__global__ __launch_bounds__(256) void rq_wide_scan_kernel(RqWideArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int d = a.d, cb = d / 8;
+  float *table = reinterpret_cast<float *>(smem);
+  uint8_t *etab = reinterpret_cast<uint8_t *>(smem + 16 * (size_t)d);
+  uint64_t *e = reinterpret_cast<uint64_t *>(smem + 20 * (size_t)d);
+  RqQuery *h = reinterpret_cast<RqQuery *>(e + a.w.cap);
+  WideCtl *ctl = reinterpret_cast<WideCtl *>(h + 1);
+  const int pair = blockIdx.x;
+  const int qi = pair / a.w.nprobes;
+  const uint32_t part = a.w.probes[pair];
+  const uint32_t r0 = a.w.part_offsets[part], r1 = a.w.part_offsets[part + 1];
+  if (threadIdx.x == 0) { ctl->cnt = 0; ctl->thr = 0xFFFFFFFFu; ctl->amb_key = 0; ctl->amb = 0; }
+  if (r1 > r0) {     // (uniform) an empty partition needs no tables
+    rq_prepare<256>(a.q + (int64_t)qi * d, a.cent + (int64_t)part * d, a.pt, d, a.pdists[pair], a.dot, a.w.allow == nullptr, table, etab,
+                    reinterpret_cast<float *>(e), h);
+  } else {
+    __syncthreads();
+  }
+  const uint32_t np = r0 + ((r1 - r0) - (r1 - r0) % RQ_BATCH);      // first row of the f32 remainder
+  wide_scan_pair(a.w, pair, r0, r1, e, ctl, [&](uint32_t row) {
+    const int mode = a.w.allow ? RQ_FILTERED : (row < np ? RQ_PACKED : RQ_REMAINDER);
+    return order_key(rq_row_distance(a.codes + (int64_t)row * cb, cb, mode, table, etab, h, a.sqrt_d, a.add[row], a.scale[row]));
+  });
+}
+
+struct RqWideDist {
+  const RqWideArgs &a;
+  int qi;
+  float *table;
+  uint8_t *etab;
+  float *rqv;
+  RqQuery *h;
+  __device__ __forceinline__ void partition(int pi, uint32_t part) {
+    rq_prepare<64>(a.q + (int64_t)qi * a.d, a.cent + (int64_t)part * a.d, a.pt, a.d, a.pdists[(int64_t)qi * a.w.nprobes + pi], a.dot,
+                   a.w.allow == nullptr, table, etab, rqv, h);
+  }
+  __device__ __forceinline__ uint32_t key(uint32_t off, int row, int np) const {
+    const int cb = a.d / 8;
+    const int mode = a.w.allow ? RQ_FILTERED : (row < np - np % RQ_BATCH ? RQ_PACKED : RQ_REMAINDER);
+    const int64_t r = (int64_t)off + row;
+    return order_key(rq_row_distance(a.codes + r * cb, cb, mode, table, etab, h, a.sqrt_d, a.add[r], a.scale[r]));
+  }
+};
+
+// dynamic LDS: table 16 d | etab 4 d | rotated query 4 d | RqQuery (24 bytes) | wide_replay_bytes(w.k): at d = 2048 and k = 768 that is
+// 49152 + 24 + 15664 = 64840 of the 65536 bytes
+__global__ __launch_bounds__(64) void rq_wide_exact_kernel(RqWideArgs a, uint64_t *__restrict__ out_ids, float *__restrict__ out_dists) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int qi = blockIdx.x;
+  if (!a.w.flags[qi]) return;
+  const size_t d = (size_t)a.d;
+  RqWideDist dist = {a, qi, reinterpret_cast<float *>(smem), reinterpret_cast<uint8_t *>(smem + 16 * d), reinterpret_cast<float *>(smem + 20 * d),
+                     reinterpret_cast<RqQuery *>(smem + 24 * d)};
+  wide_replay_query(a.w, qi, smem + 24 * d + sizeof(RqQuery), dist, out_ids, out_dists);
+}
+// ---- wide candidates: host side ---------------------------------------------------------------------------------------------------
+static_assert(sizeof(RqQuery) % 8 == 0, "the replay area that follows RqQuery holds 64-bit row ids");
+static_assert(WIDE_MAX_K == LANCE_HIP_SQRQ_MAX_CANDIDATES, "the wide kernels' capacity is the public limit");
+
 }  // namespace lh
 
 using namespace lh;
@@ -603,9 +681,16 @@ extern "C" int lance_hip_ivfrq_create(lance_hip_ctx *ctx, int metric, uint32_t d
   return LANCE_HIP_OK;
 }
 
+// refine_factor == 0: the k best by the RQ estimate.  Otherwise (lance_hip_ivfrq_search_refine, which has checked the arguments) the
+// keff = k * refine_factor best are candidates [nq][keff] in the scratch arena -- through the kernels above up to RQ_MAX_K, through the
+// wide ones (wide_cand.cuh) beyond --, re-scored against the raw vectors (launch_refine: flat_knn's arithmetic)
 static int ivfrq_search_impl(lance_hip_ctx *ctx, const lance_hip_index *idx, const float *q, uint32_t nq, uint32_t k, uint32_t nprobes,
-                             const uint32_t *allow, uint64_t *ids, float *dists) {
-  LH_REQUIRE(k > 0 && k <= (uint32_t)RQ_MAX_K, "ivfrq_search: k=%u not supported (1..%d)", k, RQ_MAX_K);
+                             const uint32_t *allow, uint64_t *ids, float *dists, uint32_t refine_factor = 0) {
+  const bool refine = refine_factor != 0;
+  if (!refine) LH_REQUIRE(k > 0 && k <= (uint32_t)RQ_MAX_K, "ivfrq_search: k=%u not supported (1..%d)", k, RQ_MAX_K);
+  const uint32_t kout = k;
+  if (refine) k *= refine_factor;      // keff: every list below is strided by it, the outputs by kout
+  const bool wide = k > (uint32_t)RQ_MAX_K;
   if (nq == 0) return LANCE_HIP_OK;
   if (nprobes > idx->rq_nlist) nprobes = idx->rq_nlist;
   LH_REQUIRE(nprobes > 0, "ivfrq_search: nprobes must be > 0");
@@ -628,13 +713,47 @@ static int ivfrq_search_impl(lance_hip_ctx *ctx, const lance_hip_index *idx, con
   a.pcnt = ctx->scratch_t<uint32_t>("ivfrq.pcnt", pairs);
   a.pamb = ctx->scratch_t<uint32_t>("ivfrq.pamb", pairs);
   if (!a.pkey || !a.ppos || !a.pcnt || !a.pamb) return LANCE_HIP_ENOMEM;
+  uint64_t *cand = nullptr;
+  float *cand_d = nullptr;
+  uint32_t *cand_cnt = nullptr, *rflags = nullptr;
+  if (refine) {
+    cand = ctx->scratch_t<uint64_t>("ivfrq.cand", (size_t)nq * k);
+    cand_d = ctx->scratch_t<float>("ivfrq.cand_d", (size_t)nq * k);
+    cand_cnt = ctx->scratch_t<uint32_t>("ivfrq.cand_cnt", (size_t)nq);
+    rflags = ctx->scratch_t<uint32_t>("ivfrq.rflags", (size_t)nq);
+    if (!cand || !cand_d || !cand_cnt || !rflags) return LANCE_HIP_ENOMEM;
+    LH_CHECK_HIP(lh::memset_async(rflags, 0, (size_t)nq * 4, ctx->stream));
+  }
   LH_CHECK_HIP(lh::memset_async(flags, 0, ((size_t)nq + 1) * 4, ctx->stream));
   ctx->last_replay_counter = flags + nq;
+  RqWideArgs wa = {};
+  size_t wide_scan_lds = 0;
+  if (wide) {
+    wa.codes = a.codes; wa.add = a.add; wa.scale = a.scale; wa.cent = a.cent; wa.pt = a.pt; wa.d = a.d; wa.dot = a.dot; wa.sqrt_d = a.sqrt_d;
+    wa.w.row_ids = a.row_ids; wa.w.part_offsets = a.part_offsets; wa.w.allow = allow; wa.w.nprobes = a.nprobes; wa.w.k = a.k;
+    wa.w.cap = wide_scan_cap((size_t)20 * d + sizeof(RqQuery) + sizeof(WideCtl));
+    wa.w.pkey = a.pkey; wa.w.ppos = a.ppos; wa.w.pcnt = a.pcnt; wa.w.pamb = a.pamb; wa.w.n_replay = flags + nq;
+    wide_scan_lds = (size_t)20 * d + (size_t)wa.w.cap * 8 + sizeof(RqQuery) + sizeof(WideCtl);
+  }
   for (uint32_t q0 = 0; q0 < nq; q0 += qch) {
     const uint32_t nqc = std::min(qch, nq - q0);
     a.probes = probes + (size_t)q0 * nprobes; a.pdists = pd + (size_t)q0 * nprobes; a.q = q + (size_t)q0 * d; a.flags = flags + q0;
-    uint64_t *oid = ids + (size_t)q0 * k;
-    float *od = dists + (size_t)q0 * k;
+    uint64_t *oid = (refine ? cand : ids) + (size_t)q0 * k;
+    float *od = (refine ? cand_d : dists) + (size_t)q0 * k;
+    if (wide) {
+      wa.pdists = a.pdists; wa.q = a.q; wa.w.probes = a.probes; wa.w.flags = a.flags;
+      {
+        ScopedTimer t(ctx, "ivfrq_wide_scan");
+        hipLaunchKernelGGL(rq_wide_scan_kernel, dim3(nqc * nprobes), dim3(256), wide_scan_lds, ctx->stream, wa);
+      }
+      LH_TRY(wide_merge_lists(ctx, wa.w, nqc, oid, od, "ivfrq_wide_merge"));
+      {
+        ScopedTimer t(ctx, "ivfrq_wide_exact");
+        hipLaunchKernelGGL(rq_wide_exact_kernel, dim3(nqc), dim3(64), (size_t)24 * d + sizeof(RqQuery) + wide_replay_bytes((int)k), ctx->stream, wa,
+                           oid, od);
+      }
+      continue;
+    }
     {
       ScopedTimer t(ctx, "ivfrq_scan");
       hipLaunchKernelGGL(rq_scan_kernel, dim3(nqc * nprobes), dim3(256), rq_scan_lds(d), ctx->stream, a);
@@ -649,6 +768,11 @@ static int ivfrq_search_impl(lance_hip_ctx *ctx, const lance_hip_index *idx, con
     }
   }
   LH_CHECK_HIP(hipGetLastError());
+  if (refine) {
+    LH_TRY(launch_cand_count(ctx, cand, nq, k, cand_cnt));
+    LH_TRY(launch_refine(ctx, idx, q, nq, (int)d, cand, cand_cnt, k, kout, ids, dists, rflags, nullptr));
+    return check_flags(ctx, rflags, nq);      // synchronises; a stored row id beyond the raw vectors is an error, not a rank
+  }
   LH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
   return LANCE_HIP_OK;
 }
@@ -678,4 +802,22 @@ extern "C" int lance_hip_ivfrq_search_filtered(lance_hip_ctx *ctx, const lance_h
   const uint32_t *bits = nullptr;
   LH_TRY(build_allow_bits(ctx, idx->row_ids, idx->n, allow_by_rowid, n_allow, &bits));
   return ivfrq_search_impl(ctx, idx, q, nq, k, nprobes, bits, ids, dists);
+}
+
+// keff = k * refine_factor candidates by the RQ estimate, re-scored against the raw vectors (lance_hip_index_set_raw)
+extern "C" int lance_hip_ivfrq_search_refine(lance_hip_ctx *ctx, const lance_hip_index *idx, const float *q, uint32_t nq, uint32_t k,
+                                             uint32_t nprobes, uint32_t refine_factor, const uint8_t *allow_by_rowid, uint64_t n_allow,
+                                             uint64_t *ids, float *dists) {
+  lh::CtxLock _ctx_lock(ctx);
+  LH_TRY(ivfrq_check(ctx, idx, q, nq, ids, dists));
+  LH_REQUIRE(refine_factor >= 1, "ivfrq_search_refine: refine_factor can not be zero");
+  LH_REQUIRE(k >= 1 && (uint64_t)k * refine_factor <= (uint64_t)LANCE_HIP_SQRQ_MAX_CANDIDATES,
+             "ivfrq_search_refine: k * refine_factor = %llu not supported (1..%d, LANCE_HIP_SQRQ_MAX_CANDIDATES)",
+             (unsigned long long)k * refine_factor, LANCE_HIP_SQRQ_MAX_CANDIDATES);
+  LH_REQUIRE(idx->raw != nullptr, "ivfrq_search_refine: refine_factor needs raw vectors (lance_hip_index_set_raw)");
+  LH_REQUIRE(allow_by_rowid || n_allow == 0, "ivfrq_search_refine: NULL filter");
+  LH_CHECK_HIP(hipSetDevice(ctx->device));
+  const uint32_t *bits = nullptr;
+  if (allow_by_rowid) LH_TRY(build_allow_bits(ctx, idx->row_ids, idx->n, allow_by_rowid, n_allow, &bits));
+  return ivfrq_search_impl(ctx, idx, q, nq, k, nprobes, bits, ids, dists, refine_factor);
 }

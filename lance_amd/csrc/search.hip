@@ -1294,8 +1294,14 @@ __global__ __launch_bounds__(256) void cand_count_kernel(const uint64_t *__restr
 
 // refine of cand_rid [nq][keff] (cand_cnt [nq] valid entries each): exact distances in the index's metric against the raw column, then
 // (dist, rowid) order, fetch k; cand_exact (optional): every candidate's exact distance in the list's order
-static int launch_refine(lance_hip_ctx *ctx, const lance_hip_index *ix, const float *q, uint32_t nq, int d, const uint64_t *cand_rid, const uint32_t *cand_cnt,
-                         uint32_t keff, uint32_t k, uint64_t *ids, float *dists, uint32_t *flags, float *cand_exact) {
+int launch_cand_count(lance_hip_ctx *ctx, const uint64_t *ids, uint32_t nq, uint32_t keff, uint32_t *cnt) {
+  hipLaunchKernelGGL(cand_count_kernel, dim3((unsigned)cdiv(nq, 256)), dim3(256), 0, ctx->stream, ids, nq, keff, cnt);
+  LH_CHECK_HIP(hipGetLastError());
+  return LANCE_HIP_OK;
+}
+
+int launch_refine(lance_hip_ctx *ctx, const lance_hip_index *ix, const float *q, uint32_t nq, int d, const uint64_t *cand_rid, const uint32_t *cand_cnt,
+                  uint32_t keff, uint32_t k, uint64_t *ids, float *dists, uint32_t *flags, float *cand_exact) {
   {
     const int P = next_pow2(std::max((int)keff, 64));
     ScopedTimer t(ctx, "refine");
@@ -1704,7 +1710,7 @@ int find_partitions_f32(lance_hip_ctx *ctx, int metric, const float *qf, uint32_
   return LANCE_HIP_OK;
 }
 
-static int check_flags(lance_hip_ctx *ctx, const uint32_t *flags, uint32_t nq) {
+int check_flags(lance_hip_ctx *ctx, const uint32_t *flags, uint32_t nq) {
   std::vector<uint32_t> fh(nq);
   LH_CHECK_HIP(hipMemcpyAsync(fh.data(), flags, (size_t)nq * 4, hipMemcpyDeviceToHost, ctx->stream));
   LH_CHECK_HIP(hipStreamSynchronize(ctx->stream));

@@ -32,6 +32,7 @@
 #include "index.h"
 #include "kernels.h"
 #include "search_common.cuh"
+#include "wide_cand.cuh"
 
 #pragma clang fp contract(off)
 
@@ -465,6 +466,78 @@ int lh::sq_merge_pairs(lance_hip_ctx *ctx, const PairLists &pl, uint32_t nq, uin
   return LANCE_HIP_OK;
 }
 
+// ---- wide candidates (wide_cand.cuh): device code ---------------------------------------------------------------------------------
+// keff = k * refine_factor above SQ_MAX_K: the scan / replay of IVF_SQ at the wide capacity, with the narrow kernels' row distance
+namespace lh {
+
+struct SqWideArgs {
+  const uint8_t *codes;          // [n][ld] partition-ordered, zero-padded rows
+  const uint32_t *xx;            // [n] sum of squared codes
+  const uint8_t *qcodes;         // [nq][ld]
+  const uint32_t *qq;            // [nq] sum of squared query codes
+  int ld, dot;
+  float r2;                      // ((end - start) as f32)^2
+  WideLists w;
+};
+
+// dynamic LDS: [ld] query codes | [w.cap] u64 entries | WideCtl
+__global__ __launch_bounds__(256) void sq_wide_scan_kernel(SqWideArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  uint4 *qs = reinterpret_cast<uint4 *>(smem);
+  uint64_t *e = reinterpret_cast<uint64_t *>(smem + a.ld);
+  WideCtl *ctl = reinterpret_cast<WideCtl *>(e + a.w.cap);
+  const int pair = blockIdx.x;
+  const int qi = pair / a.w.nprobes;
+  const uint32_t part = a.w.probes[pair];
+  const uint32_t r0 = a.w.part_offsets[part], r1 = a.w.part_offsets[part + 1];
+  const int nv = a.ld / 16;
+  for (int i = threadIdx.x; i < nv; i += 256) qs[i] = reinterpret_cast<const uint4 *>(a.qcodes + (int64_t)qi * a.ld)[i];
+  if (threadIdx.x == 0) { ctl->cnt = 0; ctl->thr = 0xFFFFFFFFu; ctl->amb_key = 0; ctl->amb = 0; }
+  __syncthreads();
+  const uint32_t qq = a.qq[qi];
+  wide_scan_pair(a.w, pair, r0, r1, e, ctl, [&](uint32_t row) {
+    const uint32_t xq = sq_row_xq(reinterpret_cast<const uint4 *>(a.codes + (int64_t)row * a.ld), qs, nv);
+    return order_key(sq_finish(a.dot, sq_sum(a.dot, xq, a.xx[row], qq), a.r2));
+  });
+}
+
+struct SqWideDist {
+  const SqWideArgs &a;
+  const uint4 *qs;
+  uint32_t qq;
+  __device__ __forceinline__ void partition(int, uint32_t) {}
+  __device__ __forceinline__ uint32_t key(uint32_t off, int row, int) const {
+    const uint32_t xq = sq_row_xq(reinterpret_cast<const uint4 *>(a.codes + (int64_t)(off + row) * a.ld), qs, a.ld / 16);
+    return order_key(sq_finish(a.dot, sq_sum(a.dot, xq, a.xx[off + row], qq), a.r2));
+  }
+};
+
+// dynamic LDS: [ld] query codes | wide_replay_bytes(w.k)
+__global__ __launch_bounds__(64) void sq_wide_exact_kernel(SqWideArgs a, uint64_t *__restrict__ out_ids, float *__restrict__ out_dists) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int qi = blockIdx.x;
+  if (!a.w.flags[qi]) return;
+  uint4 *qs = reinterpret_cast<uint4 *>(smem);
+  const int nv = a.ld / 16;
+  for (int i = threadIdx.x; i < nv; i += 64) qs[i] = reinterpret_cast<const uint4 *>(a.qcodes + (int64_t)qi * a.ld)[i];
+  __syncthreads();
+  SqWideDist dist = {a, qs, a.qq[qi]};
+  wide_replay_query(a.w, qi, smem + a.ld, dist, out_ids, out_dists);
+}
+// ---- wide candidates: host side ---------------------------------------------------------------------------------------------------
+
+// kernels.h: the wide merge step (IVF_SQ and IVF_RQ)
+int wide_merge_lists(lance_hip_ctx *ctx, const WideLists &w, uint32_t nq, uint64_t *ids, float *dists, const char *timer) {
+  {
+    ScopedTimer t(ctx, timer);
+    hipLaunchKernelGGL((wide_merge_kernel<WIDE_MERGE_BUF>), dim3(nq), dim3(256), (size_t)WIDE_MERGE_BUF * 16 + 16, ctx->stream, w, ids, dists);
+  }
+  LH_CHECK_HIP(hipGetLastError());
+  return LANCE_HIP_OK;
+}
+
+}  // namespace lh
+
 using namespace lh;
 
 extern "C" int lance_hip_sq_bounds(lance_hip_ctx *ctx, int dtype, const void *x, uint64_t count, double *bounds_host) {
@@ -595,9 +668,16 @@ extern "C" int lance_hip_ivfsq_create(lance_hip_ctx *ctx, int dtype, int metric,
   return LANCE_HIP_OK;
 }
 
+// refine_factor == 0: the k best by the SQ distance.  Otherwise (lance_hip_ivfsq_search_refine, which has checked the arguments) the
+// keff = k * refine_factor best are candidates [nq][keff] in the scratch arena -- through the kernels above up to SQ_MAX_K, through the
+// wide ones (wide_cand.cuh) beyond --, re-scored against the raw vectors with the ORIGINAL query (launch_refine: flat_knn's arithmetic)
 static int ivfsq_search_impl(lance_hip_ctx *ctx, const lance_hip_index *idx, const void *q, uint32_t nq, uint32_t k, uint32_t nprobes,
-                             const uint32_t *allow, uint64_t *ids, float *dists) {
-  LH_REQUIRE(k > 0 && k <= (uint32_t)SQ_MAX_K, "ivfsq_search: k=%u not supported (1..%d)", k, SQ_MAX_K);
+                             const uint32_t *allow, uint64_t *ids, float *dists, uint32_t refine_factor = 0) {
+  const bool refine = refine_factor != 0;
+  if (!refine) LH_REQUIRE(k > 0 && k <= (uint32_t)SQ_MAX_K, "ivfsq_search: k=%u not supported (1..%d)", k, SQ_MAX_K);
+  const uint32_t kout = k;
+  if (refine) k *= refine_factor;      // keff: every list below is strided by it, the outputs by kout
+  const bool wide = k > (uint32_t)SQ_MAX_K;
   if (nq == 0) return LANCE_HIP_OK;
   if (nprobes > idx->sq_nlist) nprobes = idx->sq_nlist;
   LH_REQUIRE(nprobes > 0, "ivfsq_search: nprobes must be > 0");
@@ -605,6 +685,7 @@ static int ivfsq_search_impl(lance_hip_ctx *ctx, const lance_hip_index *idx, con
   const uint32_t ld = idx->sq_ld;
   const float *qf;
   LH_TRY(as_f32(ctx, idx->dtype, q, (size_t)nq * d, "f16.q", &qf));
+  const float *q_orig = qf;            // what the refine scores with: a cosine index's key is normalised below, the original is not
   uint32_t *probes = ctx->scratch_t<uint32_t>("ivfsq.probes", (size_t)nq * nprobes);
   float *pd = ctx->scratch_t<float>("ivfsq.pdists", (size_t)nq * nprobes);
   uint32_t *flags = ctx->scratch_t<uint32_t>("ivfsq.flags", (size_t)nq + 1);
@@ -641,14 +722,47 @@ static int ivfsq_search_impl(lance_hip_ctx *ctx, const lance_hip_index *idx, con
   const size_t scan_lds = (size_t)ld + SQ_BUF * 8 + sizeof(SqCtl);
   const size_t merge_lds = (size_t)SQ_BUF * 16 + 16;
   const size_t exact_lds = (size_t)ld + SQ_MAX_K * 12 + (SQ_MAX_K + 4) * 8 + 64 * 4 + 16;
+  uint64_t *cand = nullptr;
+  float *cand_d = nullptr;
+  uint32_t *cand_cnt = nullptr, *rflags = nullptr;
+  if (refine) {
+    cand = ctx->scratch_t<uint64_t>("ivfsq.cand", (size_t)nq * k);
+    cand_d = ctx->scratch_t<float>("ivfsq.cand_d", (size_t)nq * k);
+    cand_cnt = ctx->scratch_t<uint32_t>("ivfsq.cand_cnt", (size_t)nq);
+    rflags = ctx->scratch_t<uint32_t>("ivfsq.rflags", (size_t)nq);
+    if (!cand || !cand_d || !cand_cnt || !rflags) return LANCE_HIP_ENOMEM;
+    LH_CHECK_HIP(lh::memset_async(rflags, 0, (size_t)nq * 4, ctx->stream));
+  }
   LH_CHECK_HIP(lh::memset_async(flags, 0, ((size_t)nq + 1) * 4, ctx->stream));
   a.n_replay = flags + nq;
   ctx->last_replay_counter = a.n_replay;
+  SqWideArgs wa = {};
+  size_t wide_scan_lds = 0;
+  if (wide) {
+    wa.codes = a.codes; wa.xx = a.xx; wa.ld = a.ld; wa.dot = a.dot; wa.r2 = a.r2;
+    wa.w.row_ids = a.row_ids; wa.w.part_offsets = a.part_offsets; wa.w.allow = allow; wa.w.nprobes = a.nprobes; wa.w.k = a.k;
+    wa.w.cap = wide_scan_cap((size_t)ld + sizeof(WideCtl));
+    wa.w.pkey = a.pkey; wa.w.ppos = a.ppos; wa.w.pcnt = a.pcnt; wa.w.pamb = a.pamb; wa.w.n_replay = a.n_replay;
+    wide_scan_lds = (size_t)ld + (size_t)wa.w.cap * 8 + sizeof(WideCtl);
+  }
   for (uint32_t q0 = 0; q0 < nq; q0 += qch) {
     const uint32_t nqc = std::min(qch, nq - q0);
     a.probes = probes + (size_t)q0 * nprobes; a.qcodes = qc + (size_t)q0 * ld; a.qq = qq + q0; a.flags = flags + q0;
-    uint64_t *oid = ids + (size_t)q0 * k;
-    float *od = dists + (size_t)q0 * k;
+    uint64_t *oid = (refine ? cand : ids) + (size_t)q0 * k;
+    float *od = (refine ? cand_d : dists) + (size_t)q0 * k;
+    if (wide) {
+      wa.qcodes = a.qcodes; wa.qq = a.qq; wa.w.probes = a.probes; wa.w.flags = a.flags;
+      {
+        ScopedTimer t(ctx, "ivfsq_wide_scan");
+        hipLaunchKernelGGL(sq_wide_scan_kernel, dim3(nqc * nprobes), dim3(256), wide_scan_lds, ctx->stream, wa);
+      }
+      LH_TRY(wide_merge_lists(ctx, wa.w, nqc, oid, od, "ivfsq_wide_merge"));
+      {
+        ScopedTimer t(ctx, "ivfsq_wide_exact");
+        hipLaunchKernelGGL(sq_wide_exact_kernel, dim3(nqc), dim3(64), (size_t)ld + wide_replay_bytes((int)k), ctx->stream, wa, oid, od);
+      }
+      continue;
+    }
     {
       ScopedTimer t(ctx, "ivfsq_scan");
       hipLaunchKernelGGL(sq_scan_kernel, dim3(nqc * nprobes), dim3(256), scan_lds, ctx->stream, a);
@@ -663,6 +777,11 @@ static int ivfsq_search_impl(lance_hip_ctx *ctx, const lance_hip_index *idx, con
     }
   }
   LH_CHECK_HIP(hipGetLastError());
+  if (refine) {
+    LH_TRY(launch_cand_count(ctx, cand, nq, k, cand_cnt));
+    LH_TRY(launch_refine(ctx, idx, q_orig, nq, d, cand, cand_cnt, k, kout, ids, dists, rflags, nullptr));
+    return check_flags(ctx, rflags, nq);      // synchronises; a stored row id beyond the raw vectors is an error, not a rank
+  }
   LH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
   return LANCE_HIP_OK;
 }
@@ -692,4 +811,22 @@ extern "C" int lance_hip_ivfsq_search_filtered(lance_hip_ctx *ctx, const lance_h
   const uint32_t *bits = nullptr;
   LH_TRY(build_allow_bits(ctx, idx->row_ids, idx->n, allow_by_rowid, n_allow, &bits));
   return ivfsq_search_impl(ctx, idx, q, nq, k, nprobes, bits, ids, dists);
+}
+
+// keff = k * refine_factor candidates by the SQ distance, re-scored against the raw vectors (lance_hip_index_set_raw) with the original query
+extern "C" int lance_hip_ivfsq_search_refine(lance_hip_ctx *ctx, const lance_hip_index *idx, const void *q, uint32_t nq, uint32_t k,
+                                             uint32_t nprobes, uint32_t refine_factor, const uint8_t *allow_by_rowid, uint64_t n_allow,
+                                             uint64_t *ids, float *dists) {
+  lh::CtxLock _ctx_lock(ctx);
+  LH_TRY(ivfsq_check(ctx, idx, q, nq, ids, dists));
+  LH_REQUIRE(refine_factor >= 1, "ivfsq_search_refine: refine_factor can not be zero");
+  LH_REQUIRE(k >= 1 && (uint64_t)k * refine_factor <= (uint64_t)LANCE_HIP_SQRQ_MAX_CANDIDATES,
+             "ivfsq_search_refine: k * refine_factor = %llu not supported (1..%d, LANCE_HIP_SQRQ_MAX_CANDIDATES)",
+             (unsigned long long)k * refine_factor, LANCE_HIP_SQRQ_MAX_CANDIDATES);
+  LH_REQUIRE(idx->raw != nullptr, "ivfsq_search_refine: refine_factor needs raw vectors (lance_hip_index_set_raw)");
+  LH_REQUIRE(allow_by_rowid || n_allow == 0, "ivfsq_search_refine: NULL filter");
+  LH_CHECK_HIP(hipSetDevice(ctx->device));
+  const uint32_t *bits = nullptr;
+  if (allow_by_rowid) LH_TRY(build_allow_bits(ctx, idx->row_ids, idx->n, allow_by_rowid, n_allow, &bits));
+  return ivfsq_search_impl(ctx, idx, q, nq, k, nprobes, bits, ids, dists, refine_factor);
 }

@@ -745,6 +745,21 @@ class DeviceFlatIndex:
 
 
 
+def _raw_column(raw, dtype):
+    t = raw if isinstance(raw, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(raw))
+    t = t.to(dtype).to(_dev()).contiguous()
+    if t.dim() != 2:
+        raise ValueError(f"raw vectors must be [rows][d], got shape {tuple(t.shape)}")
+    return t
+
+
+def _allow_bytes(allow):
+    if allow is None:
+        return None
+    a = allow if isinstance(allow, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(allow, dtype=bool))
+    return a.to(torch.uint8).to(_dev()).contiguous()
+
+
 class DeviceRqIndex:
     """Handle of a device-resident IVF_RQ index (FlatIndex sub-index over the 1-bit RaBitQ codes and factors of each partition)."""
 
@@ -755,6 +770,7 @@ class DeviceRqIndex:
         self.centroids = centroids
         self.rotation = rotation
         self.data_dtype = torch.float32
+        self._raw = None
 
     @classmethod
     def create(cls, engine, metric, centroids, rotation, codes, add, scale, part_ids, row_ids=None):
@@ -779,14 +795,27 @@ class DeviceRqIndex:
     def save(self, index_dir, loss=None):
         raise NotImplementedError("IVF_RQ index files are not supported (IVF_PQ and IVF_FLAT are)")
 
-    def search(self, q, k, nprobes, allow=None):
+    def set_raw(self, raw):
+        """the column for refine_factor searches, indexed by row id (float32; borrowed by the handle, kept alive here)"""
+        self._raw = _raw_column(raw, self.data_dtype)
+        check(self.engine.lib.lance_hip_index_set_raw(self.h, _ptr(self._raw), self._raw.shape[0]))
+
+    def search(self, q, k, nprobes, allow=None, refine_factor=0):
         """allow: boolean array indexed by row id (a prefilter), tested inside the scan kernels (lance_hip_ivfrq_search_filtered): every
-        selected row then takes the f32 distance, as the reference's prefiltered FlatIndex::search does"""
+        selected row then takes the f32 distance, as the reference's prefiltered FlatIndex::search does.
+        refine_factor > 0: the k * refine_factor best by the RQ estimate are re-scored against the raw vectors (set_raw) and the k
+        best by the exact distance are returned (lance_hip_ivfrq_search_refine)"""
         d = self.centroids.shape[1]
         q = _rq_f32(q, "queries").reshape(-1, d)
         nq = q.shape[0]
         ids = torch.empty((nq, k), dtype=torch.int64, device=q.device)
         dists = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+        if refine_factor:
+            a = _allow_bytes(allow)
+            torch.cuda.synchronize()
+            check(self.engine.lib.lance_hip_ivfrq_search_refine(self.engine.h, self.h, _ptr(q), nq, k, nprobes, refine_factor, _ptr(a),
+                                                                0 if a is None else a.numel(), _ptr(ids), _ptr(dists)))
+            return ids, dists
         if allow is not None:
             a = allow if isinstance(allow, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(allow, dtype=bool))
             a = a.to(torch.uint8).to(_dev()).contiguous()
@@ -820,6 +849,7 @@ class DeviceSqIndex:
         self.centroids = centroids
         self.data_dtype = data_dtype
         self.bounds = bounds
+        self._raw = None
 
     @classmethod
     def create(cls, engine, metric, centroids, codes, part_ids, bounds, row_ids=None):
@@ -856,14 +886,28 @@ class DeviceSqIndex:
     def save(self, index_dir, loss=None):
         raise NotImplementedError("IVF_SQ index files are not supported (IVF_PQ and IVF_FLAT are)")
 
-    def search(self, q, k, nprobes, allow=None):
-        """allow: boolean array indexed by row id (a prefilter), tested inside the scan kernels (lance_hip_ivfsq_search_filtered)"""
+    def set_raw(self, raw):
+        """the column for refine_factor searches, indexed by row id, in the column's element type (borrowed by the handle, kept
+        alive here).  For a cosine index: the ORIGINAL rows, not the normalised ones the codes were made from"""
+        self._raw = _raw_column(raw, self.data_dtype)
+        check(self.engine.lib.lance_hip_index_set_raw(self.h, _ptr(self._raw), self._raw.shape[0]))
+
+    def search(self, q, k, nprobes, allow=None, refine_factor=0):
+        """allow: boolean array indexed by row id (a prefilter), tested inside the scan kernels (lance_hip_ivfsq_search_filtered).
+        refine_factor > 0: the k * refine_factor best by the SQ distance are re-scored against the raw vectors (set_raw) with the
+        query as given and the k best by the exact distance are returned (lance_hip_ivfsq_search_refine)"""
         d = self.centroids.shape[1]
         t = q if isinstance(q, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(q))
         q = t.to(self.data_dtype).to(_dev()).contiguous().reshape(-1, d)
         nq = q.shape[0]
         ids = torch.empty((nq, k), dtype=torch.int64, device=q.device)
         dists = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+        if refine_factor:
+            a = _allow_bytes(allow)
+            torch.cuda.synchronize()
+            check(self.engine.lib.lance_hip_ivfsq_search_refine(self.engine.h, self.h, _ptr(q), nq, k, nprobes, refine_factor, _ptr(a),
+                                                                0 if a is None else a.numel(), _ptr(ids), _ptr(dists)))
+            return ids, dists
         if allow is not None:
             a = allow if isinstance(allow, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(allow, dtype=bool))
             a = a.to(torch.uint8).to(_dev()).contiguous()

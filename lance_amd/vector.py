@@ -500,17 +500,27 @@ class IvfSqIndex(_Maintenance):
         part, codes = _transform_rows(ix.engine, "IVF_SQ", self.params.metric, x_new.to(ix.data_dtype), ix.centroids, bounds=ix.bounds)
         return DeviceSqIndex.create(ix.engine, ix.metric, ix.centroids, codes, part, ix.bounds, row_ids)
 
-    def search_device(self, q, k, nprobes):
-        return self._ix.search(q, k, nprobes)
+    def search_device(self, q, k, nprobes, refine_factor=0):
+        return self._ix.search(q, k, nprobes, refine_factor=refine_factor)
 
     def nearest(self, q, k=10, nprobes=1, prefilter=None, refine_factor=None, distance_range=None):
         """prefilter: boolean array over row ids; the mask is tested inside the scan kernels (no copy of the index)"""
-        if refine_factor is not None:
-            raise NotImplementedError("IVF_SQ: refine_factor (re-ranking on the raw vectors) is not supported by this engine")
         if distance_range is not None:
             raise NotImplementedError("IVF_SQ: distance_range is not supported by this engine")
-        ids, dists = self._ix.search(q, k, nprobes) if prefilter is None else self._ix.search(q, k, nprobes, allow=prefilter)
+        if refine_factor is not None:
+            if refine_factor < 1:
+                raise ValueError("Refine factor can not be zero")
+            if self._ix._raw is None:
+                raise NotImplementedError("IVF_SQ: refine_factor needs the raw vectors (re-ranking scores the candidates against the column): attach them "
+                                      "with set_raw(x), or build with create_index(..., keep_raw=True)")
+            ids, dists = self._ix.search(q, k, nprobes, allow=prefilter, refine_factor=int(refine_factor))
+        else:
+            ids, dists = self._ix.search(q, k, nprobes) if prefilter is None else self._ix.search(q, k, nprobes, allow=prefilter)
         return ids.cpu().numpy().view(np.uint64), dists.cpu().numpy()
+
+    def set_raw(self, raw):
+        """attach the column (indexed by row id; the ORIGINAL rows) for nearest(..., refine_factor=)"""
+        self._ix.set_raw(raw)
 
     def prefiltered(self, allow):
         """A compacted copy of the index restricted to the selected rows (for callers that reuse one filter for many batches;
@@ -534,8 +544,9 @@ class IvfSqIndex(_Maintenance):
 
 class IvfRqIndex:
     """IVF_RQ: IVF partitions over 1-bit RaBitQ codes (lance-index/src/vector/bq): d / 8 code bytes and two f32 factors per row, the
-    residual rotated by a matrix that is part of the model.  Resident in HBM; no index files, refine, distance ranges or maintenance
-    (the reference's RabitQ storage has no append_batch either)."""
+    residual rotated by a matrix that is part of the model.  Resident in HBM; nearest(refine_factor=) re-ranks k * refine_factor
+    candidates (up to 768) on the raw vectors; no index files, distance ranges or maintenance (the reference's RabitQ storage has no
+    append_batch either)."""
 
     def __init__(self, ix, params, stats, part_ids):
         self._ix = ix
@@ -552,18 +563,28 @@ class IvfRqIndex:
         """the rotation P [d][d] float32 stored with the index (rotated = P @ residual)"""
         return self._ix.rotation.cpu().numpy()
 
-    def search_device(self, q, k, nprobes):
-        return self._ix.search(q, k, nprobes)
+    def search_device(self, q, k, nprobes, refine_factor=0):
+        return self._ix.search(q, k, nprobes, refine_factor=refine_factor)
 
     def nearest(self, q, k=10, nprobes=1, prefilter=None, refine_factor=None, distance_range=None):
         """prefilter: boolean array over row ids; the mask is tested inside the scan kernels, and every selected row takes the f32
         distance (the reference's prefiltered FlatIndex::search never uses the quantised table)"""
-        if refine_factor is not None:
-            raise NotImplementedError("IVF_RQ: refine_factor (re-ranking on the raw vectors) is not supported by this engine")
         if distance_range is not None:
             raise NotImplementedError("IVF_RQ: distance_range is not supported by this engine")
-        ids, dists = self._ix.search(q, k, nprobes) if prefilter is None else self._ix.search(q, k, nprobes, allow=prefilter)
+        if refine_factor is not None:
+            if refine_factor < 1:
+                raise ValueError("Refine factor can not be zero")
+            if self._ix._raw is None:
+                raise NotImplementedError("IVF_RQ: refine_factor needs the raw vectors (re-ranking scores the candidates against the column): attach them "
+                                      "with set_raw(x), or build with create_index(..., keep_raw=True)")
+            ids, dists = self._ix.search(q, k, nprobes, allow=prefilter, refine_factor=int(refine_factor))
+        else:
+            ids, dists = self._ix.search(q, k, nprobes) if prefilter is None else self._ix.search(q, k, nprobes, allow=prefilter)
         return ids.cpu().numpy().view(np.uint64), dists.cpu().numpy()
+
+    def set_raw(self, raw):
+        """attach the column (indexed by row id; the ORIGINAL rows) for nearest(..., refine_factor=)"""
+        self._ix.set_raw(raw)
 
     def _unmaintained(self, what):
         raise NotImplementedError(f"IVF_RQ: {what} is not supported (the reference's RabitQ storage has no append_batch): rebuild the index")
@@ -858,6 +879,8 @@ def create_index(x, index_type="IVF_PQ", metric="l2", num_partitions=256, num_su
         part, dvc = timed("transform", transform)
         codes, add, scale = timed("encode", lambda: eng.rq_encode(x, part, dvc, cent, rot, params.metric))
         rx = timed("build_partitions", lambda: DeviceRqIndex.create(eng, params.metric, cent, rot, codes, add, scale, part))
+        if keep_raw:
+            rx.set_raw(x)
         out = IvfRqIndex(rx, params, stats, part)
         out._rows_offered = n
         return out
@@ -866,6 +889,8 @@ def create_index(x, index_type="IVF_PQ", metric="l2", num_partitions=256, num_su
         bounds = timed("train_sq", lambda: train_sq_bounds(x, params, eng))
         part, codes = _transform_rows(eng, itype, params.metric, x, cent, bounds=bounds, timed=timed)
         sx = timed("build_partitions", lambda: DeviceSqIndex.create(eng, params.metric, cent.to(x.dtype), codes, part, bounds))
+        if keep_raw:
+            sx.set_raw(x)          # the ORIGINAL column (a cosine index encoded its normalised rows): refine scores against it
         out = IvfSqIndex(sx, params, stats, part, codes if keep_raw else None)
         out._rows_offered = n
         return out
