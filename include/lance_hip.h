@@ -279,7 +279,8 @@ int lance_hip_index_export(lance_hip_ctx *ctx, const lance_hip_index *idx, uint3
  * and remap (builder.rs:256-359, pq/storage.rs:499-560, quantizer.rs:244-280) for IVF_PQ (8- and 4-bit), IVF_FLAT and IVF_SQ
  * handles.  A source is never modified: every call returns a NEW handle (own copy of the model, no raw vectors attached -- see
  * lance_hip_index_set_raw), destroyed with lance_hip_index_destroy.  The rows move HBM -> HBM; until the caller destroys the
- * sources, sources and result are resident together.  Partitions are neither split (builder.rs:1152-1176) nor joined (:1343-1400). */
+ * sources, sources and result are resident together.  These calls neither split a partition (builder.rs:1152-1176) nor join one
+ * (:1343-1400): lance_hip_index_split / lance_hip_index_join below do, on the handle a merge returns / ahead of a remap.          */
 /* new_ids[i] of lance_hip_index_remap: the row is deleted.  (The same value marks a missing result id in the search outputs.) */
 #define LANCE_HIP_ROW_DELETED 0xFFFFFFFFFFFFFFFFull
 /* For every partition: the rows of srcs[0] in stored order, then those of srcs[1], ...  1 <= n_srcs <= 64.  The sources must agree
@@ -298,6 +299,48 @@ int lance_hip_index_remap(lance_hip_ctx *ctx, const lance_hip_index *src, const 
  * transposed layout.                                                                                                              */
 int lance_hip_index_export_rows(lance_hip_ctx *ctx, const lance_hip_index *idx, uint32_t *part_offsets_host, void *rows_host,
                                 uint32_t *aux_host, uint64_t *row_ids_host);
+
+/* ---- partition split / join: the decision (split_partition_impl, join_partition_impl, reassign_vectors; builder.rs:1152-1814) ----
+ * Where every visited row goes, in one launch.  All pointers are DEVICE pointers.  The visited rows row_ids[n] come in n_cand + 1
+ * segments, seg_offsets[n_cand + 2] (seg_offsets[0] = 0, seg_offsets[n_cand + 1] = n): segment 0 holds the rows of the chosen
+ * partition P, segment s >= 1 the rows of candidate s - 1.  seg_centroids [n_cand + 1][d]: P's old centroid c0, then the candidates'
+ * centroids in candidate order.  cand_ids[n_cand]: the candidates' partition ids in the numbering of the RESULT.  n_cand <= 64
+ * (REASSIGN_RANGE).  A row's vector is raw[row id] (f32, [n_raw][d]); distances are the index metric's, bit for bit the reference's.
+ * LANCE_HIP_REASSIGN_SPLIT: centroids2 [2][d] = c1, c2, standing for the partitions part1 and part2.  With d0 / d1 / d2 the distances
+ *   FROM the row's own old centroid / c1 / c2 TO the row: a row of P with d0 <= d1 && d0 <= d2 takes the first minimum (f32::total_cmp)
+ *   of its distances (from the row) to the candidates and goes to that candidate when min <= d1 && min <= d2; every other row of P,
+ *   and every such row when n_cand == 0, goes to part1 when d1 <= d2, else to part2.  A row of a candidate stays where it is
+ *   (dest = LANCE_HIP_NONE) when d0 <= d1 && d0 <= d2, else it goes to part1 / part2 the same way.
+ * LANCE_HIP_REASSIGN_JOIN: every row of segment 0 goes to the candidate at the first minimum distance (n_cand >= 1; centroids2, part1
+ *   and part2 are ignored); rows of other segments get LANCE_HIP_NONE.
+ * A row id >= n_raw is never read: the call returns LANCE_HIP_EINVAL (that row's dest is LANCE_HIP_NONE).  Synchronises the stream. */
+#define LANCE_HIP_REASSIGN_SPLIT 0
+#define LANCE_HIP_REASSIGN_JOIN 1
+int lance_hip_reassign_rows(lance_hip_ctx *ctx, int metric, int mode, const float *raw, uint64_t n_raw, uint32_t d,
+                            const uint64_t *row_ids, uint64_t n, const uint32_t *seg_offsets, const float *seg_centroids,
+                            const uint32_t *cand_ids, uint32_t n_cand, const float *centroids2, uint32_t part1, uint32_t part2,
+                            uint32_t *dest);
+
+/* ---- partition split / join: the index (optimize_indices' split_partition_impl, remap's join_partition_impl) ---------------------
+ * Like merge / remap: the source is never written; the result is a NEW handle with nlist + 1 (split) or nlist - 1 (join) partitions,
+ * its own model copy with the new centroid array, rebuilt offsets, no raw vectors attached.  IVF_PQ (8- and 4-bit), IVF_FLAT and
+ * IVF_SQ handles over f32 columns; L2, cosine and dot.  raw [n_raw][d] f32 (device), indexed by the stored row ids: a VISITED row's id
+ * >= n_raw is LANCE_HIP_EINVAL and nothing is built (rows of partitions outside the candidate range are never read from raw and are
+ * not checked).  Candidates: the nearest min(65, nlist) centroids of the partition's centroid by
+ * (distance in f32::total_cmp order, partition id), without the partition itself, at most 64.  Rows are visited partition by partition
+ * (the chosen one, then -- split only -- the candidates in that order), in ascending row id, and decided by lance_hip_reassign_rows.
+ * Storage: in every partition the surviving rows keep their stored order and bytes; the arriving rows follow in visit order, re-encoded
+ * through the index's own chain with the partition id given (normalise for cosine; IVF_PQ: residual against the new partition's
+ * centroid unless dot, PQ encode; IVF_SQ: the code under the stored bounds).  Nothing is trained here.
+ * split: centroids2 [2][d] f32 (device) = c1, c2; c1 replaces centroid `part`, c2 becomes partition nlist.  Every row of `part` moves:
+ *   the result holds every row exactly once (the reference as written would keep a stale copy of the old rows).
+ *   LANCE_HIP_EINVAL: part >= nlist, fewer than 2 rows in `part`, nlist + 1 > 65536, an f16 / int8 or IVF_RQ handle.
+ * join: partition `part` is removed, its rows go to the nearest candidate, partition ids above `part` drop by one.
+ *   LANCE_HIP_EINVAL: part >= nlist, nlist == 1, an f16 / int8 or IVF_RQ handle.                                                    */
+int lance_hip_index_split(lance_hip_ctx *ctx, const lance_hip_index *src, uint32_t part, const float *centroids2, const float *raw,
+                          uint64_t n_raw, lance_hip_index **out);
+int lance_hip_index_join(lance_hip_ctx *ctx, const lance_hip_index *src, uint32_t part, const float *raw, uint64_t n_raw,
+                         lance_hip_index **out);
 
 /* ---- a14: IvfModel::find_partitions (ivf/storage.rs:107-119, kmeans.rs:1134-1158) -- */
 /* Batched.  Ascending by distance; equal distances ordered by partition id (the

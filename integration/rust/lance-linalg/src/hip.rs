@@ -139,6 +139,17 @@ extern "C" {
         n_map: u64, out: *mut *mut LanceHipIndex) -> i32;
     pub fn lance_hip_index_export_rows(ctx: *mut LanceHipCtx, idx: *const LanceHipIndex, part_offsets_host: *mut u32,
         rows_host: *mut c_void, aux_host: *mut u32, row_ids_host: *mut u64) -> i32;
+    // the decision of a partition split (mode 0) / join (mode 1), builder.rs:1152-1814: where every visited row goes.  Device pointers;
+    // segment 0 of row_ids = the chosen partition, segment s = candidate s - 1; dest[i] == u32::MAX (LANCE_HIP_NONE): the row stays
+    pub fn lance_hip_reassign_rows(ctx: *mut LanceHipCtx, metric: i32, mode: i32, raw: *const f32, n_raw: u64, d: u32,
+        row_ids: *const u64, n: u64, seg_offsets: *const u32, seg_centroids: *const f32, cand_ids: *const u32, n_cand: u32,
+        centroids2: *const f32, part1: u32, part2: u32, dest: *mut u32) -> i32;
+    // the index after a split (centroids2 = [c1, c2]) / a join of partition `part`: a new handle, the source untouched; raw [n_raw][d]
+    // f32 indexed by the stored row ids
+    pub fn lance_hip_index_split(ctx: *mut LanceHipCtx, src: *const LanceHipIndex, part: u32, centroids2: *const f32, raw: *const f32,
+        n_raw: u64, out: *mut *mut LanceHipIndex) -> i32;
+    pub fn lance_hip_index_join(ctx: *mut LanceHipCtx, src: *const LanceHipIndex, part: u32, raw: *const f32, n_raw: u64,
+        out: *mut *mut LanceHipIndex) -> i32;
     pub fn lance_hip_flat_topk(ctx: *mut LanceHipCtx, dtype: i32, metric: i32, x: *const c_void, row_ids: *const u64,
         n: u64, d: u32, q: *const c_void, nq: u32, k: u32, ids: *mut u64, dists: *mut f32) -> i32;
     /// multivec_distance (distance.rs:107-206) of one multivector query to every row of a List<FixedSizeList> column: `values` is the

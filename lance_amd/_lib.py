@@ -14,6 +14,7 @@ IVF_PQ, IVF_FLAT = 0, 1
 L2, COSINE, DOT = 0, 1, 2
 F32, F16, I8 = 0, 1, 2
 NONE = 0xFFFFFFFF
+REASSIGN_SPLIT, REASSIGN_JOIN = 0, 1      # LANCE_HIP_REASSIGN_* (include/lance_hip.h)
 SQ_MAX_DIM = 16384                   # LANCE_HIP_SQ_MAX_DIM (include/lance_hip.h)
 RQ_MAX_DIM = 2048                    # LANCE_HIP_RQ_MAX_DIM (include/lance_hip.h)
 MULTIVEC_MAX_QUERY_VECTORS = 256     # LANCE_HIP_MULTIVEC_MAX_QUERY_VECTORS (include/lance_hip.h)
@@ -46,6 +47,7 @@ SYMBOLS = [
     "lance_hip_comm_unique_id", "lance_hip_comm_create", "lance_hip_comm_adopt", "lance_hip_comm_from_callback", "lance_hip_comm_destroy", "lance_hip_kmeans_train_sharded", "lance_hip_kmeans_train_sharded_x",
     "lance_hip_kmeans_shard_estep_x",
     "lance_hip_index_merge", "lance_hip_index_remap", "lance_hip_index_export_rows",
+    "lance_hip_reassign_rows", "lance_hip_index_split", "lance_hip_index_join",
 ]
 
 
@@ -130,6 +132,9 @@ def load():
         "lance_hip_index_merge": (i32, [vp, C.POINTER(vp), u32, C.POINTER(vp)]),
         "lance_hip_index_remap": (i32, [vp, vp, vp, vp, u64, C.POINTER(vp)]),
         "lance_hip_index_export_rows": (i32, [vp, vp, vp, vp, vp, vp]),
+        "lance_hip_reassign_rows": (i32, [vp, i32, i32, vp, u64, u32, vp, u64, vp, vp, vp, u32, vp, u32, u32, vp]),
+        "lance_hip_index_split": (i32, [vp, vp, u32, vp, vp, u64, C.POINTER(vp)]),
+        "lance_hip_index_join": (i32, [vp, vp, u32, vp, u64, C.POINTER(vp)]),
         "lance_hip_find_partitions": (i32, [vp, i32, i32, vp, u32, u32, vp, u32, u32, vp, vp]),
         "lance_hip_pq_scan_topk": (i32, [vp, i32, i32, vp, u32, vp, u32, u32, vp, vp, u64, u32, i32, f32, f32, vp, vp,
                                          C.POINTER(u32)]),

@@ -531,9 +531,10 @@ static int index_alloc_common(lance_hip_ctx *ctx, int dtype, int metric, uint32_
 
 extern "C++" {
 namespace lh {
-// an empty IVF_PQ handle whose model is `src`'s f32 copies (index_update.hip): same search constants as any new handle
-int index_alloc_like_pq(lance_hip_ctx *ctx, const lance_hip_index *src, lance_hip_index **out) {
-  return index_alloc_model(ctx, src->dtype, LANCE_HIP_F32, src->metric, src->d, src->centroids, src->nlist, src->codebook, src->m, src->nbits, out);
+// an empty IVF_PQ handle whose model is `src`'s f32 copies -- codebook, and the centroid array given (src's own, or the one of a
+// split / joined index) -- (index_update.hip): same search constants as any new handle
+int index_alloc_like_pq_centroids(lance_hip_ctx *ctx, const lance_hip_index *src, const float *centroids, uint32_t nlist, lance_hip_index **out) {
+  return index_alloc_model(ctx, src->dtype, LANCE_HIP_F32, src->metric, src->d, centroids, nlist, src->codebook, src->m, src->nbits, out);
 }
 }  // namespace lh
 }

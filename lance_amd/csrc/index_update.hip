@@ -6,7 +6,8 @@
 // Every operation builds a NEW handle (fresh serial: captured searches of the sources stay valid) and never writes a source.  The
 // payload -- PQ codes, IVF_FLAT vectors, SQ codes + their sums, row ids -- moves HBM -> HBM through one copy kernel; only the
 // partition offsets (at most 65,537 words per handle, already mirrored on the host) are computed on the host.
-// What is built is the reference's no-split / no-join branch: partitions are neither split on append nor joined on remap.
+// What is built here is the reference's no-split / no-join branch: partitions are neither split on append nor joined on remap
+// (rebalance.hip: lance_hip_index_split / _join, built from the pieces below).
 #include <algorithm>
 #include <vector>
 
@@ -34,6 +35,7 @@ __device__ __forceinline__ uint32_t iu_partition_of(const uint32_t *__restrict__
 //   perm                 gather:  destination row r takes source row perm[r]                                (remap)
 //   src_offs + dst_base  scatter: source row r of partition p goes to dst_base[p] + (r - src_offs[p])      (merge, one source)
 //   neither              row r -> row r, possibly between different strides                                 (export of padded rows)
+//   all three            gather and scatter at once: row perm[r] goes where grouped row r belongs           (split / join)
 // A row is row_bytes bytes, moved as row_bytes / width pieces of `width` bytes (16, 8, 4 or 1): the host picks the widest that
 // divides both strides, row_bytes and both base addresses.
 struct IuCopy {
@@ -51,9 +53,8 @@ __global__ __launch_bounds__(256) void iu_copy_rows_kernel(IuCopy a) {
     const int64_t r = g / cpr;
     const int c = (int)(g - r * cpr);
     int64_t sr = r, dr = r;
-    if (a.perm) {
-      sr = (int64_t)a.perm[r];
-    } else if (a.src_offs) {
+    if (a.perm) sr = (int64_t)a.perm[r];
+    if (a.src_offs) {
       const uint32_t p = iu_partition_of(a.src_offs, a.nlist, (uint32_t)r);
       dr = (int64_t)a.dst_base[p] + (r - (int64_t)a.src_offs[p]);
     }
@@ -116,8 +117,8 @@ static int iu_width(const void *src, const void *dst, int64_t src_stride, int64_
   return 1;
 }
 
-static int iu_copy(lance_hip_ctx *ctx, const void *src, void *dst, uint64_t n_rows, int64_t src_stride, int64_t dst_stride, int row_bytes,
-                   const uint32_t *perm, const uint32_t *src_offs, const uint32_t *dst_base, uint32_t nlist) {
+int iu_copy(lance_hip_ctx *ctx, const void *src, void *dst, uint64_t n_rows, int64_t src_stride, int64_t dst_stride, int row_bytes,
+            const uint32_t *perm, const uint32_t *src_offs, const uint32_t *dst_base, uint32_t nlist) {
   if (n_rows == 0 || row_bytes == 0) return LANCE_HIP_OK;
   IuCopy a;
   a.src = static_cast<const uint8_t *>(src); a.dst = static_cast<uint8_t *>(dst);
@@ -130,18 +131,17 @@ static int iu_copy(lance_hip_ctx *ctx, const void *src, void *dst, uint64_t n_ro
   return LANCE_HIP_OK;
 }
 
-enum { IU_PQ = 0, IU_FLAT = 1, IU_SQ = 2 };
-static int iu_kind(const lance_hip_index *ix) { return ix->sq ? IU_SQ : (ix->m == 0 ? IU_FLAT : IU_PQ); }
+int iu_kind(const lance_hip_index *ix) { return ix->sq ? IU_SQ : (ix->m == 0 ? IU_FLAT : IU_PQ); }
 static const char *iu_kind_name(int k) { return k == IU_SQ ? "IVF_SQ" : (k == IU_FLAT ? "IVF_FLAT" : "IVF_PQ"); }
-static uint32_t iu_lists(const lance_hip_index *ix) { return ix->sq ? ix->sq_nlist : ix->nlist; }
+uint32_t iu_lists(const lance_hip_index *ix) { return ix->sq ? ix->sq_nlist : ix->nlist; }
 // the per-row payload next to the row ids: SQ codes (padded rows), IVF_FLAT vectors, PQ codes
-static uint32_t iu_stride(const lance_hip_index *ix) { return ix->sq ? ix->sq_ld : (ix->m == 0 ? ix->d * 4u : ix->code_bytes()); }
-static const uint8_t *iu_payload(const lance_hip_index *ix) {
+uint32_t iu_stride(const lance_hip_index *ix) { return ix->sq ? ix->sq_ld : (ix->m == 0 ? ix->d * 4u : ix->code_bytes()); }
+const uint8_t *iu_payload(const lance_hip_index *ix) {
   return iu_kind(ix) == IU_FLAT ? reinterpret_cast<const uint8_t *>(ix->vectors) : ix->codes;
 }
-static uint8_t *iu_payload(lance_hip_index *ix) { return iu_kind(ix) == IU_FLAT ? reinterpret_cast<uint8_t *>(ix->vectors) : ix->codes; }
+uint8_t *iu_payload(lance_hip_index *ix) { return iu_kind(ix) == IU_FLAT ? reinterpret_cast<uint8_t *>(ix->vectors) : ix->codes; }
 
-static int iu_check_handle(const lance_hip_ctx *ctx, const lance_hip_index *ix, const char *what) {
+int iu_check_handle(const lance_hip_ctx *ctx, const lance_hip_index *ix, const char *what) {
   LH_REQUIRE(ix, "%s: NULL index", what);
   LH_REQUIRE(!ix->rq, "%s: IVF_RQ indices are not maintained (the reference's RabitQ storage has no append_batch): rebuild the index", what);
   LH_REQUIRE(!ix->ephemeral && ix->part_offsets && ix->part_offsets_h.size() == (size_t)iu_lists(ix) + 1 && ix->centroids,
@@ -151,7 +151,7 @@ static int iu_check_handle(const lance_hip_ctx *ctx, const lance_hip_index *ix, 
   return LANCE_HIP_OK;
 }
 
-static int iu_malloc(void **out, size_t bytes) {
+int iu_malloc(void **out, size_t bytes) {
   const hipError_t e = hipMalloc(out, std::max<size_t>(bytes, 16));
   if (e != hipSuccess) {
     set_error("hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
@@ -161,17 +161,18 @@ static int iu_malloc(void **out, size_t bytes) {
 }
 
 // An empty handle with src's parameters and model (copied from src's f32 copies, never re-widened), no rows yet.  The lazy search
-// constants (pt / ms / cq / raw_u8) start empty, `raw` is not inherited.
-static int iu_new_like(lance_hip_ctx *ctx, const lance_hip_index *src, lance_hip_index **out) {
-  if (iu_kind(src) == IU_PQ) return index_alloc_like_pq(ctx, src, out);      // (runs qscan_index_constants for 8-bit codes)
+// constants (pt / ms / cq / raw_u8) start empty, `raw` is not inherited.  centroids / lists: another centroid array (f32, device) for
+// the handle of a split / joined index (rebalance.hip); NULL: src's own.
+int iu_new_like(lance_hip_ctx *ctx, const lance_hip_index *src, const float *centroids, uint32_t lists, lance_hip_index **out) {
+  if (!centroids) { centroids = src->centroids; lists = iu_lists(src); }
+  if (iu_kind(src) == IU_PQ) return index_alloc_like_pq_centroids(ctx, src, centroids, lists, out);      // (runs qscan_index_constants for 8-bit codes)
   auto *ix = new lance_hip_index();
   ix->device = ctx->device; ix->metric = src->metric; ix->dtype = src->dtype; ix->d = src->d; ix->m = 0; ix->nbits = src->nbits;
-  ix->nlist = src->nlist;                 // 0 for IVF_SQ (index.h)
-  ix->sq = src->sq; ix->sq_lo = src->sq_lo; ix->sq_hi = src->sq_hi; ix->sq_nlist = src->sq_nlist; ix->sq_ld = src->sq_ld;
-  const uint32_t lists = iu_lists(src);
+  ix->nlist = src->sq ? 0 : lists;        // 0 for IVF_SQ (index.h)
+  ix->sq = src->sq; ix->sq_lo = src->sq_lo; ix->sq_hi = src->sq_hi; ix->sq_nlist = src->sq ? lists : 0; ix->sq_ld = src->sq_ld;
   int r = iu_malloc(reinterpret_cast<void **>(&ix->centroids), (size_t)lists * src->d * 4);
   if (r == LANCE_HIP_OK) r = iu_malloc(reinterpret_cast<void **>(&ix->part_offsets), (size_t)(lists + 1) * 4);
-  if (r == LANCE_HIP_OK && hipMemcpyAsync(ix->centroids, src->centroids, (size_t)lists * src->d * 4, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) {
+  if (r == LANCE_HIP_OK && hipMemcpyAsync(ix->centroids, centroids, (size_t)lists * src->d * 4, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) {
     set_error("index update: copying the centroids failed");
     r = LANCE_HIP_ERUNTIME;
   }
@@ -181,7 +182,7 @@ static int iu_new_like(lance_hip_ctx *ctx, const lance_hip_index *src, lance_hip
 }
 
 // the per-row arrays of a handle that will hold n rows
-static int iu_alloc_rows(lance_hip_index *ix, uint64_t n) {
+int iu_alloc_rows(lance_hip_index *ix, uint64_t n) {
   ix->n = n;
   const int kind = iu_kind(ix);
   if (kind == IU_FLAT) {
@@ -197,7 +198,7 @@ static int iu_alloc_rows(lance_hip_index *ix, uint64_t n) {
 }
 
 // what depends on the layout: offsets on both sides, the largest partition, IVF_FLAT's 256-row block list
-static int iu_finish_layout(lance_hip_ctx *ctx, lance_hip_index *ix, const lance_hip_index *src, const std::vector<uint32_t> &offs) {
+int iu_finish_layout(lance_hip_ctx *ctx, lance_hip_index *ix, const lance_hip_index *src, const std::vector<uint32_t> &offs) {
   const uint32_t lists = iu_lists(ix);
   ix->part_offsets_h = offs;
   ix->model_finite = src->model_finite;      // the same model bit for bit
@@ -323,7 +324,7 @@ extern "C" int lance_hip_index_merge(lance_hip_ctx *ctx, const lance_hip_index *
     LH_REQUIRE(fh[1] == 0, "index_merge: the sources' codebook differs (every source must carry the same PQ codebook, bit for bit)");
   }
   lance_hip_index *ix = nullptr;
-  LH_TRY(iu_new_like(ctx, s0, &ix));
+  LH_TRY(iu_new_like(ctx, s0, nullptr, 0, &ix));
   const int r = iu_merge(ctx, srcs, n_srcs, ix);
   if (r != LANCE_HIP_OK) { delete ix; return r; }
   *out = ix;
@@ -350,7 +351,7 @@ extern "C" int lance_hip_index_remap(lance_hip_ctx *ctx, const lance_hip_index *
     LH_REQUIRE(fh == 0, "index_remap: old_ids must be strictly ascending (unsorted or duplicate ids)");
   }
   lance_hip_index *ix = nullptr;
-  LH_TRY(iu_new_like(ctx, src, &ix));
+  LH_TRY(iu_new_like(ctx, src, nullptr, 0, &ix));
   const int r = iu_remap(ctx, src, old_ids, new_ids, n_map, ix);
   if (r != LANCE_HIP_OK) { delete ix; return r; }
   *out = ix;

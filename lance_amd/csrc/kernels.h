@@ -195,7 +195,24 @@ int launch_normalize_planes(lance_hip_ctx *ctx, const float *x, int64_t n, int d
 
 // quantised 4-query filter scan + exact re-evaluation (search_q.hip), driven by ivfpq_scan_merge_pm
 int qscan_index_constants(lance_hip_ctx *ctx, lance_hip_index *ix);
-int index_alloc_like_pq(lance_hip_ctx *ctx, const lance_hip_index *src, lance_hip_index **out);   // build.hip
+// build.hip: an empty IVF_PQ handle with src's codebook and the centroid array given (f32, device)
+int index_alloc_like_pq_centroids(lance_hip_ctx *ctx, const lance_hip_index *src, const float *centroids, uint32_t nlist, lance_hip_index **out);
+// index_update.hip: the pieces of merge / remap that split / join (rebalance.hip) are built from
+enum { IU_PQ = 0, IU_FLAT = 1, IU_SQ = 2 };
+int iu_kind(const lance_hip_index *ix);
+uint32_t iu_lists(const lance_hip_index *ix);
+uint32_t iu_stride(const lance_hip_index *ix);
+const uint8_t *iu_payload(const lance_hip_index *ix);
+uint8_t *iu_payload(lance_hip_index *ix);
+int iu_check_handle(const lance_hip_ctx *ctx, const lance_hip_index *ix, const char *what);
+int iu_malloc(void **out, size_t bytes);
+int iu_new_like(lance_hip_ctx *ctx, const lance_hip_index *src, const float *centroids, uint32_t lists, lance_hip_index **out);
+int iu_alloc_rows(lance_hip_index *ix, uint64_t n);
+int iu_copy(lance_hip_ctx *ctx, const void *src, void *dst, uint64_t n_rows, int64_t src_stride, int64_t dst_stride, int row_bytes,
+            const uint32_t *perm, const uint32_t *src_offs, const uint32_t *dst_base, uint32_t nlist);
+int iu_finish_layout(lance_hip_ctx *ctx, lance_hip_index *ix, const lance_hip_index *src, const std::vector<uint32_t> &offs);
+// sq.hip: the per-row sums of squared codes of padded SQ rows [n][ld]
+int sq_row_sums(lance_hip_ctx *ctx, const uint8_t *codes, uint64_t n, uint32_t ld, uint32_t *out);
 constexpr int QSCAN_SEG_CAP = 256;   // survivors kept per (query, probe)
 struct SelectOut;
 // search_qt.hip: M = 48 / 64 / 96 (table tiled over the sub-quantisers); class-B queries of those shapes go to the rescan kernel

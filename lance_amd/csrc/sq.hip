@@ -619,6 +619,15 @@ extern "C" int lance_hip_sq_distance(lance_hip_ctx *ctx, int dtype, int metric, 
   return LANCE_HIP_OK;
 }
 
+namespace lh {
+int sq_row_sums(lance_hip_ctx *ctx, const uint8_t *codes, uint64_t n, uint32_t ld, uint32_t *out) {
+  if (n == 0) return LANCE_HIP_OK;
+  hipLaunchKernelGGL(sq_norms_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, ctx->stream, codes, (int64_t)n, (int)ld, out);
+  LH_CHECK_HIP(hipGetLastError());
+  return LANCE_HIP_OK;
+}
+}  // namespace lh
+
 extern "C" int lance_hip_ivfsq_create(lance_hip_ctx *ctx, int dtype, int metric, uint32_t d, const void *centroids, uint32_t nlist,
                                       const uint8_t *codes, const uint32_t *part_ids, const uint64_t *row_ids, uint64_t n,
                                       const double *bounds_host, lance_hip_index **out) {

@@ -379,6 +379,31 @@ class Engine:
         check(self.lib.lance_hip_residual(self.h, dt, _ptr(x), x.shape[0], x.shape[1], _ptr(centroids), _ptr(p), _ptr(out)))
         return out
 
+    def reassign_rows(self, metric, raw, row_ids, seg_offsets, seg_centroids, cand_ids, centroids2=None, part1=_lib.NONE, part2=_lib.NONE):
+        """lance_hip_reassign_rows: where the visited rows of a partition split (centroids2 = [c1, c2], standing for the partitions
+        part1 / part2) or join (centroids2 None) go.  row_ids [n] in visit order, in segments seg_offsets [C + 2] (segment 0: the chosen
+        partition, segment s: candidate s - 1); seg_centroids [C + 1][d]: the old centroid, then the candidates'; cand_ids [C] in the
+        result's numbering; raw [n_raw][d] float32, indexed by row id.  -> dest int32 [n] on the device (-1 = LANCE_HIP_NONE: stays)"""
+        if _dtype_name(raw) not in ("float32", "float64"):
+            raise ValueError(f"reassign_rows: raw vectors must be float32, got {_dtype_name(raw)} (float16 and int8 columns are not supported)")
+        raw = _raw_column(raw, torch.float32)
+        n_raw, d = raw.shape
+        rid = to_device(row_ids, torch.int64).reshape(-1)
+        seg = to_device(seg_offsets, torch.int32).reshape(-1)
+        cent = to_device(seg_centroids, torch.float32).reshape(-1, d)
+        cand = to_device(cand_ids, torch.int32).reshape(-1)
+        ncand = cand.numel()
+        if seg.numel() != ncand + 2 or cent.shape[0] != ncand + 1:
+            raise ValueError(f"reassign_rows: {ncand} candidates need {ncand + 2} segment offsets and {ncand + 1} centroids, "
+                             f"got {seg.numel()} and {cent.shape[0]}")
+        c12 = None if centroids2 is None else to_device(centroids2, torch.float32).reshape(2, d)
+        dest = torch.empty(rid.numel(), dtype=torch.int32, device=raw.device)
+        torch.cuda.synchronize()
+        check(self.lib.lance_hip_reassign_rows(self.h, METRICS[metric], _lib.REASSIGN_JOIN if c12 is None else _lib.REASSIGN_SPLIT, _ptr(raw),
+                                               n_raw, d, _ptr(rid), rid.numel(), _ptr(seg), _ptr(cent), _ptr(cand), ncand, _ptr(c12),
+                                               int(part1), int(part2), _ptr(dest)))
+        return dest
+
     def pq_encode(self, x, codebook, metric="l2"):
         x, dt = _vec(x); codebook = _model(codebook, x)
         n, d = x.shape
@@ -639,6 +664,40 @@ def _remap_handle(engine, handle, old_ids, new_ids):
     return h
 
 
+def _export_ids(engine, handle, nlist):
+    """lance_hip_index_export_rows without the payload -> (part_offsets u32[nlist + 1], row_ids u64[n]) in stored order"""
+    n = C.c_uint64()
+    check(engine.lib.lance_hip_index_info(handle, C.byref(n), None, None, None))
+    offs = np.empty(nlist + 1, np.uint32)
+    rid = np.empty(n.value, np.uint64)
+    torch.cuda.synchronize()
+    check(engine.lib.lance_hip_index_export_rows(engine.h, handle, offs.ctypes.data_as(C.c_void_p), None, None, rid.ctypes.data_as(C.c_void_p)))
+    return offs, rid
+
+
+def _rebalance_handle(engine, handle, centroids, part, raw, centroids2=None):
+    """lance_hip_index_split (centroids2 = [c1, c2]) / lance_hip_index_join (centroids2 None) of partition `part` -> (a new handle, its
+    centroid tensor: c1 in row `part` and c2 appended, or row `part` removed).  raw [n_raw][d] float32, indexed by the stored row ids."""
+    if raw is None:
+        raise ValueError("split / join: the raw vectors are required (rows are re-assigned and re-encoded from them)")
+    if _dtype_name(raw) not in ("float32", "float64"):
+        raise ValueError(f"split / join: raw vectors must be float32, got {_dtype_name(raw)} (float16 and int8 columns are not supported)")
+    raw = _raw_column(raw, torch.float32)
+    d = centroids.shape[1]
+    if raw.shape[1] != d:
+        raise ValueError(f"split / join: raw vectors must be [rows][{d}], got {tuple(raw.shape)}")
+    part = int(part)
+    h = C.c_void_p()
+    torch.cuda.synchronize()
+    if centroids2 is None:
+        check(engine.lib.lance_hip_index_join(engine.h, handle, part, _ptr(raw), raw.shape[0], C.byref(h)))
+        return h, torch.cat([centroids[:part], centroids[part + 1:]]).contiguous()
+    c12 = to_device(centroids2, torch.float32).reshape(2, d)
+    check(engine.lib.lance_hip_index_split(engine.h, handle, part, _ptr(c12), _ptr(raw), raw.shape[0], C.byref(h)))
+    c = c12.to(centroids.dtype)
+    return h, torch.cat([centroids[:part], c[:1], centroids[part + 1:], c[1:]]).contiguous()
+
+
 def _export_rows(engine, handle, nlist, row_bytes, aux=False):
     """lance_hip_index_export_rows -> (part_offsets u32[nlist + 1], rows u8 [n, row_bytes], aux u32[n] | None, row_ids u64[n])"""
     n = C.c_uint64()
@@ -700,6 +759,16 @@ class DeviceFlatIndex:
     def remap(self, old_ids, new_ids):
         """lance_hip_index_remap with a mapping already sorted by old id -> a new index"""
         return type(self)(self.engine, _remap_handle(self.engine, self.h, old_ids, new_ids), self.metric, self.centroids, self.data_dtype)
+
+    def split(self, part, centroids2, raw):
+        """lance_hip_index_split -> a new index with nlist + 1 partitions (c1 = centroids2[0] replaces centroid `part`, c2 is appended)"""
+        h, cent = _rebalance_handle(self.engine, self.h, self.centroids, part, raw, centroids2)
+        return type(self)(self.engine, h, self.metric, cent, self.data_dtype)
+
+    def join(self, part, raw):
+        """lance_hip_index_join -> a new index without partition `part`: its rows go to their nearest neighbours"""
+        h, cent = _rebalance_handle(self.engine, self.h, self.centroids, part, raw)
+        return type(self)(self.engine, h, self.metric, cent, self.data_dtype)
 
     def export_rows(self):
         """-> (part_offsets u32[nlist + 1], vectors f32 [n, d], row_ids u64[n]) in stored order"""
@@ -878,6 +947,16 @@ class DeviceSqIndex:
         return type(self)(self.engine, _remap_handle(self.engine, self.h, old_ids, new_ids), self.metric, self.centroids, self.data_dtype,
                           self.bounds)
 
+    def split(self, part, centroids2, raw):
+        """lance_hip_index_split -> a new index with nlist + 1 partitions (c1 = centroids2[0] replaces centroid `part`, c2 is appended)"""
+        h, cent = _rebalance_handle(self.engine, self.h, self.centroids, part, raw, centroids2)
+        return type(self)(self.engine, h, self.metric, cent, self.data_dtype, self.bounds)
+
+    def join(self, part, raw):
+        """lance_hip_index_join -> a new index without partition `part`: its rows go to their nearest neighbours"""
+        h, cent = _rebalance_handle(self.engine, self.h, self.centroids, part, raw)
+        return type(self)(self.engine, h, self.metric, cent, self.data_dtype, self.bounds)
+
     def export_rows(self):
         """-> (part_offsets u32[nlist + 1], codes u8 [n, d], sums of squared codes u32[n], row_ids u64[n]) in stored order"""
         nlist, d = self.centroids.shape
@@ -1009,6 +1088,17 @@ class DeviceIndex:
         """lance_hip_index_remap with a mapping already sorted by old id -> a new index"""
         return type(self)(self.engine, _remap_handle(self.engine, self.h, old_ids, new_ids), self.metric, self.centroids, self.codebook, raw,
                           self.data_dtype)
+
+    def split(self, part, centroids2, raw):
+        """lance_hip_index_split -> a new index with nlist + 1 partitions (c1 = centroids2[0] replaces centroid `part`, c2 is appended);
+        no raw vectors attached"""
+        h, cent = _rebalance_handle(self.engine, self.h, self.centroids, part, raw, centroids2)
+        return type(self)(self.engine, h, self.metric, cent, self.codebook, None, self.data_dtype)
+
+    def join(self, part, raw):
+        """lance_hip_index_join -> a new index without partition `part`: its rows go to their nearest neighbours"""
+        h, cent = _rebalance_handle(self.engine, self.h, self.centroids, part, raw)
+        return type(self)(self.engine, h, self.metric, cent, self.codebook, None, self.data_dtype)
 
     def export_rows(self):
         """-> (part_offsets u32[nlist + 1], codes u8 [n, code bytes] row-major, row_ids u64[n]) in stored order"""

@@ -14,14 +14,14 @@ lancedb/lance tree):
 All computation happens in liblance_hip.so; this module only orchestrates.
 """
 import time
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import Optional
 
 import numpy as np
 import torch
 
 from ._lib import EINVAL, METRICS, NONE, ROW_DELETED, LanceHipError
-from .engine import DeviceFlatIndex, DeviceIndex, DeviceRqIndex, DeviceSqIndex, Engine, _dtype_name, check_multivector, to_device
+from .engine import DeviceFlatIndex, DeviceIndex, DeviceRqIndex, DeviceSqIndex, Engine, _dtype_name, _export_ids, check_multivector, to_device
 
 _engine = None
 
@@ -151,10 +151,55 @@ def _mapping_arrays(mapping):
     return old, new
 
 
+# ---- partition split / join: which partition, if any (rust/lance/src/index/vector/builder.rs:1152-1176, :1343-1400) ---------------
+MAX_PARTITION_SIZE_FACTOR = 4          # lance-index/src/lib.rs:52-53
+MIN_PARTITION_SIZE_PERCENT = 25
+
+
+def target_partition_size(index_type):
+    """IndexType::target_partition_size (lance-index/src/lib.rs:284-295): the rows a partition of this index kind should hold"""
+    sizes = {"IVF_FLAT": 4096, "IVF_PQ": 8192, "IVF_SQ": 8192}
+    key = str(index_type).upper()
+    if key not in sizes:
+        raise ValueError(f"target_partition_size: index type {index_type} has no partition split / join (IVF_FLAT, IVF_PQ, IVF_SQ)")
+    return sizes[key]
+
+
+def should_split(sizes, target):
+    """sizes: the rows of every partition, old and appended together -> the partition optimize_indices would split, or None: the one
+    with the most rows among those with MORE than 4 * target; on equal sizes the lowest id (the reference keeps a candidate only
+    on `>`).  Pure host code."""
+    best, best_size = None, 0
+    for p, size in enumerate(sizes):
+        size = int(size)
+        if size > MAX_PARTITION_SIZE_FACTOR * int(target) and size > best_size:
+            best, best_size = p, size
+    return best
+
+
+def should_join(sizes, target):
+    """sizes: the rows of every partition that SURVIVE the mapping of a remap (rows mapped to deleted do not count) -> the partition
+    remap would join into its neighbours, or None: the one with the fewest rows among those with FEWER than 25 * target / 100
+    (integer arithmetic); on equal sizes the lowest id; never when there is only one partition.  Pure host code."""
+    sizes = list(sizes)
+    if len(sizes) <= 1:
+        return None
+    best, best_size = None, 0
+    for p, size in enumerate(sizes):
+        size = int(size)
+        if size < MIN_PARTITION_SIZE_PERCENT * int(target) // 100 and (best is None or size < best_size):
+            best, best_size = p, size
+    return best
+
+
 class _Maintenance:
     """append / remap / delete of an index wrapper (lance_hip_index_merge / _remap): every call returns a NEW index and leaves this one
-    as it is -- both are resident until the caller drops one.  What is built is the reference's no-split / no-join branch of
-    optimize_indices and remap (rust/lance/src/index/vector/ivf.rs:355-560, builder.rs:256-359)."""
+    as it is -- both are resident until the caller drops one.  By default append and remap take the reference's no-split / no-join
+    branch of optimize_indices and remap (rust/lance/src/index/vector/ivf.rs:355-560, builder.rs:256-359); with rebalance=True they
+    go on as the reference does: append splits the largest over-full partition of the merged index, remap / delete join the smallest
+    under-full partition before the mapping is applied (should_split / should_join above, split_partition / join_partition below:
+    lance_hip_index_split / _join)."""
+    _index_type = None        # "IVF_PQ" | "IVF_FLAT" | "IVF_SQ": selects target_partition_size
     _rows_offered = None      # rows handed to create_index / append so far: the next positional row id (None: opened from files, merged)
 
     def _wrap(self, dev_index, rows_offered):
@@ -167,11 +212,74 @@ class _Maintenance:
         """the stored rows in stored order, row-major (DeviceIndex / DeviceFlatIndex / DeviceSqIndex.export_rows)"""
         return self._ix.export_rows()
 
-    def append(self, x_new, row_ids=None, raw=None):
+    def _rewrap(self, dev_index):
+        out = self._wrap(dev_index, self._rows_offered)
+        out.params = replace(self.params, num_partitions=int(dev_index.centroids.shape[0]))
+        return out
+
+    def _target(self, size):
+        return target_partition_size(self._index_type) if size is None else int(size)
+
+    def split_partition(self, part, raw, centroids=None, seed=0):
+        """The index with partition `part` split in two (split_partition_impl, builder.rs:1177-1340): c1 replaces its centroid, c2 becomes
+        partition nlist; its rows and the rows of its up to 64 nearest neighbours are re-assigned on the GPU and the movers re-encoded
+        with this index's own model.  raw [rows][d] float32, indexed by the stored row ids.  centroids: [c1, c2], or None to train them
+        as the reference does -- k-means with k = 2, 50 iterations, on the partition's raw rows in ascending row id (normalised and
+        trained in L2 for cosine); where the reference samples 512 rows at random, the first 512 in that order are taken."""
+        ix = self._ix
+        try:
+            if centroids is None:
+                centroids = self._train_split(int(part), raw, seed)
+            return self._rewrap(ix.split(part, centroids, raw))
+        except LanceHipError as e:
+            if e.code == EINVAL:
+                raise ValueError(str(e)) from e
+            raise
+
+    def join_partition(self, part, raw):
+        """The index without partition `part` (join_partition_impl, builder.rs:1401-1530): every one of its rows goes to the nearest of
+        its up to 64 neighbouring partitions and is re-encoded there; partition ids above `part` drop by one."""
+        try:
+            return self._rewrap(self._ix.join(part, raw))
+        except LanceHipError as e:
+            if e.code == EINVAL:
+                raise ValueError(str(e)) from e
+            raise
+
+    def _train_split(self, part, raw, seed):
+        ix = self._ix
+        if raw is None:
+            raise ValueError("split_partition: the raw vectors are required")
+        if ix.data_dtype != torch.float32:
+            raise ValueError(f"split_partition: f32 columns only in this version (the index holds {ix.data_dtype} vectors)")
+        nlist = int(ix.centroids.shape[0])
+        if not 0 <= part < nlist:
+            raise ValueError(f"split_partition: partition {part} does not exist (nlist = {nlist})")
+        offs, ids = _export_ids(ix.engine, ix.h, nlist)
+        mine = np.sort(ids[int(offs[part]):int(offs[part + 1])])[:2 * 256]          # sample_rate 256 x k 2
+        if mine.size < 2:
+            raise ValueError(f"split_partition: partition {part} holds {mine.size} rows, a split needs at least 2")
+        raw_t = to_device(raw, torch.float32)
+        if int(mine.max()) >= raw_t.shape[0]:
+            raise ValueError(f"split_partition: a stored row id is >= n_raw={raw_t.shape[0]} (the raw vectors do not cover the index)")
+        rows = raw_t[to_device(mine.astype(np.int64))]
+        metric = _normalize_metric_type(self.params.metric)
+        if metric == "cosine":
+            rows = ix.engine.normalize(rows)
+        cent, _, _ = ix.engine.kmeans_train(rows, 2, max_iters=50, seed=seed, metric="l2" if metric == "cosine" else metric)
+        return cent.to(torch.float32)
+
+    def append(self, x_new, row_ids=None, raw=None, rebalance=False, target_partition_size=None, seed=0):
         """The index with the rows x_new added: they are transformed with THIS index's model (centroids, codebook, SQ bounds -- nothing is
         re-trained, ivf.rs:377-378) through the calls create_index makes, grouped into a delta index and merged behind the stored rows of
         every partition.  Non-finite rows are dropped.  row_ids: one id per row of x_new; None continues create_index's position
-        convention (rows offered so far + i), which an index opened from files cannot do.  raw (IVF_PQ): the vectors for refine."""
+        convention (rows offered so far + i), which an index opened from files cannot do.  raw (IVF_PQ): the vectors for refine.
+        rebalance=True (raw required: the vectors of the old AND the new rows, indexed by row id): after the merge, the partition
+        should_split picks among the merged sizes -- at most one -- is split (split_partition with trained centroids, `seed`).
+        target_partition_size: None = the index type's reference value.  An IVF_PQ result has raw attached for refine whether or
+        not a partition was split."""
+        if rebalance and raw is None:
+            raise ValueError("append(rebalance=True): the raw vectors are required (old and new rows, indexed by row id)")
         x_new = to_device(x_new)
         if x_new.dim() != 2 or x_new.shape[1] != self._ix.centroids.shape[1]:
             raise ValueError(f"append: rows must be [n][{self._ix.centroids.shape[1]}], got {tuple(x_new.shape)}")
@@ -189,13 +297,44 @@ class _Maintenance:
             merged = type(self._ix).merge([self._ix, delta], raw=raw)
         finally:
             delta.close()
-        return self._wrap(merged, None if self._rows_offered is None else self._rows_offered + n_new)
+        out = self._wrap(merged, None if self._rows_offered is None else self._rows_offered + n_new)
+        if rebalance:
+            offs, _ = _export_ids(merged.engine, merged.h, int(merged.centroids.shape[0]))
+            part = should_split(np.diff(offs.astype(np.int64)), self._target(target_partition_size))
+            if part is not None:
+                try:
+                    grown = out.split_partition(part, raw, seed=seed)
+                finally:
+                    merged.close()
+                if isinstance(self, IvfPqIndex):
+                    grown._ix.set_raw(raw)                      # as the merged index: the vectors stay attached for refine
+                return grown
+        return out
 
-    def remap(self, mapping, raw=None):
+    def remap(self, mapping, raw=None, rebalance=False, target_partition_size=None):
         """The index after a compaction or a delete: mapping = dict {old id: new id | None} or a pair (old_ids, new_ids) with None / -1 for
         a deleted row.  Stored rows keep their order; a row whose id is not an old id stays as it is; all lookups are against the ids
-        before the call (a swap swaps).  Duplicate old ids raise ValueError."""
+        before the call (a swap swaps).  Duplicate old ids raise ValueError.
+        rebalance=True (raw required, indexed by the ids stored NOW): the partition should_join picks among the sizes that survive the
+        mapping -- at most one, rows mapped to deleted do not count -- is joined first, then the mapping is applied (the reference's
+        order).  target_partition_size: None = the index type's reference value."""
         old, new = _mapping_arrays(mapping)
+        if rebalance:
+            if raw is None:
+                raise ValueError("remap / delete(rebalance=True): the raw vectors are required (indexed by the stored row ids)")
+            ix = self._ix
+            offs, ids = _export_ids(ix.engine, ix.h, int(ix.centroids.shape[0]))
+            gone = np.isin(ids, old[new == np.uint64(ROW_DELETED)])
+            part_of = np.repeat(np.arange(offs.size - 1), np.diff(offs.astype(np.int64)))
+            part = should_join(np.bincount(part_of[~gone], minlength=offs.size - 1), self._target(target_partition_size))
+            if part is not None:
+                joined = self.join_partition(part, raw)
+                try:
+                    return joined.remap((old, new), raw=raw if isinstance(self, IvfPqIndex) else None)
+                finally:
+                    joined._ix.close()
+            if not isinstance(self, IvfPqIndex):
+                raw = None                                      # (only IVF_PQ attaches raw vectors to the result, for refine)
         old_t, new_t = to_device(old), to_device(new)
         key = old_t ^ torch.iinfo(torch.int64).min          # signed order of the key = unsigned order of the id
         key, order = torch.sort(key)
@@ -204,10 +343,10 @@ class _Maintenance:
         kw = {"raw": raw} if raw is not None else {}
         return self._wrap(self._ix.remap(old_t[order], new_t[order], **kw), self._rows_offered)
 
-    def delete(self, row_ids, raw=None):
+    def delete(self, row_ids, raw=None, rebalance=False, target_partition_size=None):
         """remap with every given id mapped to deleted"""
         ids = np.unique(_ids_u64(row_ids))
-        return self.remap((ids, np.full(ids.size, ROW_DELETED, np.uint64)), raw=raw)
+        return self.remap((ids, np.full(ids.size, ROW_DELETED, np.uint64)), raw=raw, rebalance=rebalance, target_partition_size=target_partition_size)
 
 
 def _ids_u64(row_ids):
@@ -243,6 +382,7 @@ def merge_indices(indices, raw=None):
 
 class IvfPqIndex(_Maintenance):
     """An IVF_PQ index resident in HBM with the reference's query semantics."""
+    _index_type = "IVF_PQ"
 
     def __init__(self, dev_index, params, stats=None, part_ids=None, codes=None):
         self._ix = dev_index
@@ -418,6 +558,7 @@ class IvfPqIndex(_Maintenance):
 
 class IvfFlatIndex(_Maintenance):
     """IVF_FLAT: IVF partitions over the raw vectors (exact distances inside the probed partitions)."""
+    _index_type = "IVF_FLAT"
 
     def __init__(self, ix, params, stats, part_ids):
         self._ix = ix
@@ -473,6 +614,7 @@ class IvfFlatIndex(_Maintenance):
 class IvfSqIndex(_Maintenance):
     """IVF_SQ: IVF partitions over 8-bit scalar-quantised codes (lance-index/src/vector/sq.rs, sq/storage.rs): IVF_FLAT's search
     over a quarter of its bytes, distances computed between codes."""
+    _index_type = "IVF_SQ"
 
     def __init__(self, ix, params, stats, part_ids, codes=None):
         self._ix = ix
@@ -597,6 +739,12 @@ class IvfRqIndex:
 
     def delete(self, *a, **kw):
         self._unmaintained("delete")
+
+    def split_partition(self, *a, **kw):
+        self._unmaintained("split_partition")
+
+    def join_partition(self, *a, **kw):
+        self._unmaintained("join_partition")
 
     def save(self, index_dir):
         raise NotImplementedError("IVF_RQ index files are not supported (IVF_PQ and IVF_FLAT are)")
