@@ -13,6 +13,14 @@
  *     parameter name ends in `_host`; buffers are caller-owned, row-major, and no
  *     allocation crosses the ABI except opaque handles.  lance_hip_malloc/free/memcpy
  *     are provided so a host without its own HIP binding can stage data.
+ *   - Alignment: a data pointer needs the alignment of its ELEMENT and no more (4 bytes for f32 /
+ *     u32 / f32 outputs, 2 for f16, 1 for int8 and code bytes, 8 for u64 row ids): a slice of an
+ *     Arrow FixedSizeList column that starts at any row is a valid argument, inputs and outputs
+ *     alike.  16-byte alignment only selects faster kernels (vector loads, the matrix-core
+ *     routes); an operand off that grid is served by kernels that read element by element, with
+ *     the same bits in every result ("Pointer alignment"; tests/test_zz_gpu_unaligned.py).
+ *     One entry point refuses instead of falling back: lance_hip_rq_distance with d % 128 == 0
+ *     (code rows of whole 16-byte words) answers LANCE_HIP_EINVAL unless `codes` is 16-byte aligned.
  *   - Return 0 on success, a negative LANCE_HIP_E* code on failure; the message is
  *     available from lance_hip_last_error() (thread-local).  Never throws or aborts.
  *   - Work is issued on the context's stream; calls return after the stream has been

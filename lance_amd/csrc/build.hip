@@ -433,7 +433,7 @@ int lance_hip_ivfpq_encode(lance_hip_ctx *ctx, int dtype, int metric, const void
     return encode_finish(ctx, n, nlist, dists, part_ids, loss_out_host);
   }
   const bool mfma_enc = metric != LANCE_HIP_COSINE && pq_mfma_encode_supported(dtype, (int)d, (int)m, (int)nbits, x, centf, cbf, (int64_t)n);
-  const bool native = metric != LANCE_HIP_COSINE && (mfma_enc || encode_fused_supported(dtype, (int)d, (int)m, (int)nbits, x, centf, cbf));
+  const bool native = metric != LANCE_HIP_COSINE && (mfma_enc || encode_fused_supported(dtype, (int)d, (int)m, (int)nbits, x, centf, cbf, codes));
   bool assign_native = false;
   if (native) {
     pa.x_native = x; pa.x_dtype = dtype;

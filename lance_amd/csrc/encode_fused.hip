@@ -102,7 +102,7 @@ __global__ __launch_bounds__(256) void encode_fused_kernel(const TX *__restrict_
   }
 }
 
-bool encode_fused_supported(int dtype, int d, int m, int nbits, const void *x, const float *cent, const float *codebook) {
+bool encode_fused_supported(int dtype, int d, int m, int nbits, const void *x, const float *cent, const float *codebook, const uint8_t *codes) {
   static const bool off = getenv("LANCE_HIP_NO_FUSED_ENCODE") != nullptr;
   if (off || nbits != 8 || m <= 0 || d % m != 0) return false;
   const int sd = d / m;
@@ -110,6 +110,8 @@ bool encode_fused_supported(int dtype, int d, int m, int nbits, const void *x, c
   const size_t es = dtype == LANCE_HIP_F16 ? 2 : (dtype == LANCE_HIP_I8 ? 1 : 4);
   if (reinterpret_cast<uintptr_t>(x) % (4 * es)) return false;
   if ((reinterpret_cast<uintptr_t>(cent) & 15) || (reinterpret_cast<uintptr_t>(codebook) & 15)) return false;
+  // a lane stores its row's m code bytes as 16-byte pieces (m = 16, 32) or as 4-byte words (m = 8): the caller's codes must allow that
+  if (reinterpret_cast<uintptr_t>(codes) & (m % 16 == 0 ? 15 : 3)) return false;
   return true;
 }
 

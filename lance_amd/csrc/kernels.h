@@ -103,7 +103,7 @@ int launch_flat_filter_mfma_wide(lance_hip_ctx *ctx, const FlatPool &e, int d, i
 int launch_assign(lance_hip_ctx *ctx, const PairwiseArgs &p, int d, int metric, int batches);
 bool assign_reads_native(PairwiseArgs p, int d, int batches);
 // residual + PQ encode in one kernel, rows read in the column's own element type (encode_fused.hip)
-bool encode_fused_supported(int dtype, int d, int m, int nbits, const void *x, const float *cent, const float *codebook);
+bool encode_fused_supported(int dtype, int d, int m, int nbits, const void *x, const float *cent, const float *codebook, const uint8_t *codes);
 int launch_encode_fused(lance_hip_ctx *ctx, int dtype, const void *x, int64_t n, int d, const float *cent, const uint32_t *part_ids,
                         int residual, const float *codebook, int m, uint8_t *codes);
 // the whole transform in one pass over the rows: coarse assign + exact re-check + residual + PQ encode (xform_fused.hip)

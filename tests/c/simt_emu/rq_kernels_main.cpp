@@ -35,16 +35,36 @@ static uint8_t *aligned_bytes(size_t bytes) {      // 16-byte aligned, NOT padde
   return p;
 }
 
+// exactly `bytes` bytes that start `shift` bytes past a 16-byte boundary and end the heap block
+struct Shifted {
+  void *base = nullptr;
+  uint8_t *p;
+  Shifted(const void *src, size_t bytes, size_t shift) {
+    if (posix_memalign(&base, 16, bytes + shift + (bytes + shift == 0))) exit(2);
+    p = static_cast<uint8_t *>(base) + shift;
+    if (bytes) memcpy(p, src, bytes);
+  }
+  Shifted(const Shifted &) = delete;
+  ~Shifted() { free(base); }
+};
+
+// argv[3] (optional): bytes a caller-owned base is moved off the 16-byte grid -- the partition's codes handed to rq_distance always (rows
+// of whole 16-byte words are refused there, as lance_hip_rq_distance refuses them: counted, and run aligned), the f32 rows given to
+// rq_encode when it is a multiple of 4.
 // in: u32 n, d, nlist, nq, nprobes, k, dot, has_allow | f32 x[n][d] | f32 q[nq][d] | f32 cent[nlist][d] | f32 P[d][d] | u32 part[n] |
 // f32 dist_v_c[n] | u32 n_kept, perm[n_kept], offs[nlist + 1] | u64 row_ids[n] | u32 probes[nq][nprobes] | f32 pdists[nq][nprobes] |
 // f32 dist_q_c[nq][nlist] (every pair, for the per-partition distance kernel) | u32 allow_bits[n_kept / 32 + 4] (if has_allow)
 int main(int argc, char **argv) {
   if (argc < 3) return 2;
+  const size_t shift = argc > 3 ? (size_t)atoi(argv[3]) : 0;
+  unsigned refused = 0;
   FILE *f = fopen(argv[1], "rb");
   if (!f) return 2;
   const auto h = rd<uint32_t>(f, 8);
   const uint32_t n = h[0], d = h[1], nlist = h[2], nq = h[3], nprobes = h[4], k = h[5], dot = h[6], has_allow = h[7];
-  const auto x = rd<float>(f, (size_t)n * d);
+  const auto x_in = rd<float>(f, (size_t)n * d);
+  const Shifted xs(x_in.data(), x_in.size() * 4, shift % 4 == 0 ? shift : 0);
+  struct FView { const float *p; const float *data() const { return p; } } x{reinterpret_cast<const float *>(xs.p)};
   const auto q = rd<float>(f, (size_t)nq * d);
   const auto cent = rd<float>(f, (size_t)nlist * d);
   const auto P = rd<float>(f, (size_t)d * d);
@@ -92,8 +112,12 @@ int main(int argc, char **argv) {
       dqc[i] = dqc_all[(size_t)i * nlist + p];
       for (uint32_t j = 0; j < d; ++j) qr[(size_t)i * d + j] = q[(size_t)i * d + j] - cent[(size_t)p * d + j];
     }
-    uint8_t *pc = aligned_bytes((size_t)np * cb);      // the partition alone: reads past its last row are errors
-    memcpy(pc, stored + (size_t)offs[p] * cb, (size_t)np * cb);
+    // the partition alone: reads past its last row are errors.  lance_hip_rq_distance: "codes of 16-byte rows must be 16-byte aligned"
+    const bool refuse = d % 128 == 0 && shift % 16 != 0;
+    refused += refuse;
+    const Shifted pcs(stored + (size_t)offs[p] * cb, (size_t)np * cb, refuse ? 0 : shift);
+    const uint8_t *pc = pcs.p;
+    if (reinterpret_cast<uintptr_t>(pc) % 16 != (refuse ? 0 : shift % 16)) return 4;
     for (int quantised = 1; quantised >= 0; --quantised) {
       std::vector<float> out((size_t)nq * np, -7.0f);
       simt_launch(std::min<uint32_t>((np + 255) / 256, 64), nq, 256, [&] {
@@ -102,7 +126,6 @@ int main(int argc, char **argv) {
       });
       dist_out.insert(dist_out.end(), out.begin(), out.end());
     }
-    free(pc);
   }
 
   // search: scan, merge (the IVF_SQ merge kernel), replay
@@ -130,6 +153,7 @@ int main(int argc, char **argv) {
   wr(o, ids.data(), ids.size()); wr(o, dists.data(), dists.size()); wr(o, flags.data(), flags.size()); wr(o, fast_ids.data(), fast_ids.size());
   fclose(o);
   free(stored);
+  printf("refused %u\n", refused);
   puts("ok");
   return 0;
 }

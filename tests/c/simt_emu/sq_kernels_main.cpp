@@ -22,18 +22,39 @@ static uint8_t *aligned_copy(const uint8_t *src, size_t bytes) {      // 16-byte
   return p;
 }
 
+// exactly `bytes` bytes that start `shift` bytes past a 16-byte boundary and end the heap block: the base is off the grid, and a read past
+// the last element is an error
+struct Shifted {
+  void *base = nullptr;
+  uint8_t *p;
+  Shifted(const void *src, size_t bytes, size_t shift) {
+    if (posix_memalign(&base, 16, bytes + shift + (bytes + shift == 0))) exit(2);
+    p = static_cast<uint8_t *>(base) + shift;
+    if (bytes) memcpy(p, src, bytes);
+  }
+  Shifted(const Shifted &) = delete;
+  ~Shifted() { free(base); }
+};
+
+// argv[3] (optional): bytes every caller-owned base is moved off the 16-byte grid -- the codes handed to sq_distance always, the rows
+// and keys (f32) when it is a multiple of 4.  The host's gate (lance_hip_sq_distance: `wide`) is applied as the library applies it.
 // in: u32 n, d, nlist, nq, nprobes, k, dot, has_allow | f64 lo, hi | f32 x[n][d] | f32 q[nq][d] (the rows / keys AS STORED: normalised
 // for cosine) | u32 part[n] (the stable grouping is the caller's: perm follows) | u32 n_kept, perm[n_kept], offs[nlist + 1] |
 // u64 row_ids[n] | u32 probes[nq][nprobes] | u32 allow_bits[n_kept / 32 + 4] (if has_allow)
 int main(int argc, char **argv) {
   if (argc < 3) return 2;
+  const size_t shift = argc > 3 ? (size_t)atoi(argv[3]) : 0;
   FILE *f = fopen(argv[1], "rb");
   if (!f) return 2;
   const auto h = rd<uint32_t>(f, 8);
   const uint32_t n = h[0], d = h[1], nlist = h[2], nq = h[3], nprobes = h[4], k = h[5], dot = h[6], has_allow = h[7];
   const auto b = rd<double>(f, 2);
-  const auto x = rd<float>(f, (size_t)n * d);
-  const auto q = rd<float>(f, (size_t)nq * d);
+  const auto x_in = rd<float>(f, (size_t)n * d);
+  const auto q_in = rd<float>(f, (size_t)nq * d);
+  const size_t fshift = shift % 4 == 0 ? shift : 0;
+  const Shifted xs(x_in.data(), x_in.size() * 4, fshift), qs_(q_in.data(), q_in.size() * 4, fshift);
+  struct FView { const float *p; const float *data() const { return p; } } x{reinterpret_cast<const float *>(xs.p)}, q{reinterpret_cast<const float *>(qs_.p)};
+  if (reinterpret_cast<uintptr_t>(x.p) % 16 != fshift % 16 || reinterpret_cast<uintptr_t>(q.p) % 16 != fshift % 16) return 4;
   const auto nk = rd<uint32_t>(f, 1);
   const uint32_t n_kept = nk[0];
   const auto perm = rd<uint32_t>(f, n_kept);
@@ -60,10 +81,17 @@ int main(int argc, char **argv) {
   simt_launch((nq + 255) / 256, 1, 256, [&] { sq_norms_kernel(qc, (int64_t)nq, (int)ld, qq.data()); });
   // distance_all, both row readers
   std::vector<float> dist_words((size_t)nq * n), dist_wide((size_t)nq * n, -1.0f);
-  simt_launch((n + 255) / 256, nq, 256, [&] { sq_distance_kernel<false>(codes.data(), (int64_t)n, (int)d, qc, (int)ld, (int)dot, r2, dist_words.data()); });
+  const Shifted cs(codes.data(), codes.size(), shift);
+  if (reinterpret_cast<uintptr_t>(cs.p) % 16 != shift % 16) return 4;
+  simt_launch((n + 255) / 256, nq, 256, [&] { sq_distance_kernel<false>(cs.p, (int64_t)n, (int)d, qc, (int)ld, (int)dot, r2, dist_words.data()); });
   uint8_t *codes_al = aligned_copy(codes.data(), codes.size());
-  if (d % 16 == 0)
-    simt_launch((n + 255) / 256, nq, 256, [&] { sq_distance_kernel<true>(codes_al, (int64_t)n, (int)d, qc, (int)ld, (int)dot, r2, dist_wide.data()); });
+  if (d % 16 == 0) {      // the second reader as lance_hip_sq_distance picks it for this base
+    const uint8_t *cp = shift ? cs.p : codes_al;
+    const bool wide = d % 16 == 0 && (reinterpret_cast<uintptr_t>(cp) & 15) == 0;
+    printf("sq_distance wide %d\n", (int)wide);
+    if (wide) simt_launch((n + 255) / 256, nq, 256, [&] { sq_distance_kernel<true>(cp, (int64_t)n, (int)d, qc, (int)ld, (int)dot, r2, dist_wide.data()); });
+    else simt_launch((n + 255) / 256, nq, 256, [&] { sq_distance_kernel<false>(cp, (int64_t)n, (int)d, qc, (int)ld, (int)dot, r2, dist_wide.data()); });
+  }
   // the index: gather + norms
   uint8_t *stored = aligned_copy(nullptr, (size_t)n_kept * ld);
   std::vector<uint64_t> rid(n_kept);

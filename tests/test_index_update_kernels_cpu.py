@@ -99,7 +99,8 @@ def sources_for(stride, sizes, nlist=5, seed=0, aux=False):
 
 # strides: 8 (4-bit M=16), 12 (d=24, M=12), 16, 96 (an IVF_FLAT row of d=24), 32 (IVF_SQ d=20 padded, with its sums and an unpadding export)
 @pytest.mark.parametrize("stride,shift,aux,unpad,width", [(8, 0, False, 0, 8), (12, 0, False, 0, 4), (16, 0, False, 0, 16), (96, 0, False, 0, 16),
-                                                           (32, 0, True, 20, 16), (16, 4, False, 0, 4), (16, 1, False, 0, 1), (8, 8, False, 0, 8)])
+                                                           (32, 0, True, 20, 16), (16, 4, False, 0, 4), (16, 1, False, 0, 1), (8, 8, False, 0, 8),
+                                                           (16, 8, False, 0, 8), (96, 4, False, 0, 4), (96, 1, False, 0, 1), (8, 4, False, 0, 4)])
 def test_merge_three_sources_one_empty(emulator, stride, shift, aux, unpad, width):
     srcs = sources_for(stride, (300, 0, 41), aux=aux)
     refused, offs, payload, ids, xx, flat, widths = run(emulator, 0, 5, srcs, shift=shift, unpad=unpad)
@@ -114,7 +115,8 @@ def test_merge_three_sources_one_empty(emulator, stride, shift, aux, unpad, widt
         assert np.array_equal(flat, want[1][:, :unpad]) and widths[-1] == 4
 
 
-@pytest.mark.parametrize("stride,shift,aux", [(8, 0, False), (12, 0, False), (16, 0, False), (96, 0, False), (32, 0, True), (16, 1, False)])
+@pytest.mark.parametrize("stride,shift,aux", [(8, 0, False), (12, 0, False), (16, 0, False), (96, 0, False), (32, 0, True), (16, 1, False), (16, 4, False),
+                                              (16, 8, False)])
 def test_remap(emulator, stride, shift, aux):
     (offs, ids, payload, xx), = sources_for(stride, (330,), aux=aux, seed=9)
     first, last = int(ids[0]), int(ids[-1])

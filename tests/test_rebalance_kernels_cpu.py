@@ -61,7 +61,7 @@ def emulator(tmp_path_factory):
     return exe, work
 
 
-def run(emulator, metric, mode, raw, ids, seg_offs, seg_cent, cand_ids, c12, part1, part2):
+def run(emulator, metric, mode, raw, ids, seg_offs, seg_cent, cand_ids, c12, part1, part2, shift=0):
     """-> (flag, staged, dest)"""
     exe, work = emulator
     inp, outp = str(work / "in.bin"), str(work / "out.bin")
@@ -72,7 +72,7 @@ def run(emulator, metric, mode, raw, ids, seg_offs, seg_cent, cand_ids, c12, par
         np.ascontiguousarray(seg_cent, np.float32).tofile(fh); np.asarray(cand_ids, np.uint32).tofile(fh)
         if mode == R.SPLIT:
             np.ascontiguousarray(c12, np.float32).tofile(fh)
-    r = subprocess.run([exe, inp, outp], capture_output=True, text=True, timeout=900)
+    r = subprocess.run([exe, inp, outp] + ([str(shift)] if shift else []), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout[-1000:] + r.stderr[-4000:]
     out = np.fromfile(outp, np.uint32)
     assert out.size == 2 + len(ids)
@@ -128,6 +128,22 @@ def test_join_dest_equals_the_specification(emulator, metric, nlist, d):
     assert flag == 0 and staged == (d < 100) and len(dest) > 32
     assert np.array_equal(dest, want["dest"])
     assert set(dest.tolist()) <= set(want["cand_ids"].tolist()) and dest.max() < nlist - 1      # the numbering without the joined partition
+
+
+@pytest.mark.parametrize("metric,nlist,d,staged", [("l2", 5, 20, 1), ("cosine", 5, 16, 1), ("dot", 70, 142, 0)])
+def test_raw_off_the_16_byte_grid(emulator, metric, nlist, d, staged):
+    """The raw vectors are the caller's: a slice of an f32 column starts on a 4-byte boundary only.  Both readers of `raw` (the copy into
+    LDS and the in-place route past 64 KiB) with the base 4 and 8 bytes off the grid, the block ending with the last row: the same
+    destinations as the aligned run and the specification, nothing read past a row, no access wider than the element."""
+    c = R.make_case(17, nlist, d, metric, n=400, shaped=nlist == 5)
+    want = R.split_dest(metric, c["centroids"], c["offs"], c["ids"], c["part"], c["raw"], c["c12"])
+    args = (emulator, metric, R.SPLIT, c["raw"], c["ids"][want["pos"]], want["seg_offs"], want["seg_cent"], want["cands"], c["c12"], c["part"],
+            len(c["centroids"]))
+    aligned = run(*args)
+    assert aligned[0] == 0 and aligned[1] == staged and np.array_equal(aligned[2], want["dest"])
+    for shift in (4, 8):
+        flag, took, dest = run(*args, shift=shift)
+        assert flag == 0 and took == staged and np.array_equal(dest, aligned[2]), shift
 
 
 def test_row_ids_out_of_range_raise_the_flag_and_are_never_read(emulator):

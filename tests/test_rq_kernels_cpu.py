@@ -61,7 +61,7 @@ def emulator(tmp_path_factory):
     return exe, work
 
 
-def run_case(emulator, oracle, x, q, cent, P, metric, k, nprobes, row_ids, prefilter=None):
+def run_case(emulator, oracle, x, q, cent, P, metric, k, nprobes, row_ids, prefilter=None, shift=0):
     exe, work = emulator
     x, q, cent, P = (np.ascontiguousarray(a, f32) for a in (x, q, cent, P))
     n, d = x.shape
@@ -89,9 +89,11 @@ def run_case(emulator, oracle, x, q, cent, P, metric, k, nprobes, row_ids, prefi
         row_ids.astype(np.uint64).tofile(fh); probes.astype(np.uint32).tofile(fh); pd.astype(f32).tofile(fh); dqc_all.tofile(fh)
         if prefilter is not None:
             bits.tofile(fh)
-    r = subprocess.run([exe, inp, outp], capture_output=True, text=True, timeout=600)
+    r = subprocess.run([exe, inp, outp] + ([str(shift)] if shift else []), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout[-1000:] + r.stderr[-4000:]
     raw = np.fromfile(outp, np.uint8)
+    if shift:
+        return raw, int(re.search(r"refused (\d+)", r.stdout).group(1))
     pos = 0
 
     def take(count, dt):
@@ -149,6 +151,27 @@ def test_three_branches(emulator, oracle, metric, d, rot, k, nprobes):
     rid = R.permuted_ids(len(x), 2)
     run_case(emulator, oracle, x, q, cent, P, metric, k, nprobes, rid)
     run_case(emulator, oracle, x, q, cent, P, metric, k, 5, rid, prefilter=np.ones(int(rid.max()) // 2, bool))
+
+
+@pytest.mark.parametrize("d", [64, 128])
+def test_offset_bases(emulator, oracle, d):
+    """Caller-owned bases 1, 4 and 8 bytes off the 16-byte grid.  d = 64: rows of 8 code bytes, read byte by byte from any base; d = 128:
+    rows of one 16-byte word, which lance_hip_rq_distance refuses off the grid -- the program counts the refusals and never hands the
+    16-byte reader such a base.  At 4 and 8 the f32 rows of rq_encode move too.  Every output byte equals the aligned run's."""
+    src = open(os.path.join(CSRC, "rq.hip")).read()
+    gate = 'LH_REQUIRE(d % 128 != 0 || (reinterpret_cast<uintptr_t>(codes) & 15) == 0, "rq_distance: codes of 16-byte rows must be 16-byte aligned");'
+    assert gate in src, f"rq.hip no longer holds {gate!r} (the refusal of lance_hip_rq_distance): tests/c/simt_emu/rq_kernels_main.cpp mirrors it, update both"
+    x, cent = R.sized_partitions([40, 33], d, seed=d + 1)
+    q = queries(x, cent, 2, seed=4)
+    P = R.rotations(d, seed=5)["qr"]
+    rid = R.permuted_ids(len(x), 2)
+    args = (emulator, oracle, x, q, cent, P, "l2", 10, 2, rid)
+    run_case(*args)
+    aligned = np.fromfile(str(emulator[1] / "out.bin"), np.uint8)
+    for shift in (1, 4, 8):
+        got, refused = run_case(*args, shift=shift)
+        assert np.array_equal(got, aligned), shift
+        assert refused == (2 if d == 128 else 0)
 
 
 def test_row_addresses(emulator, oracle):

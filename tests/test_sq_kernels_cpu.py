@@ -56,7 +56,7 @@ def emulator(tmp_path_factory):
     return exe, work
 
 
-def run_case(emulator, oracle, x, q, cent, metric, k, nprobes, bounds, row_ids, prefilter=None):
+def run_case(emulator, oracle, x, q, cent, metric, k, nprobes, bounds, row_ids, prefilter=None, shift=0, want_wide=None):
     exe, work = emulator
     xs, part = S.prepare_rows(oracle, x, cent, metric)
     qs = oracle.normalize(q) if metric == "cosine" else q
@@ -82,9 +82,13 @@ def run_case(emulator, oracle, x, q, cent, metric, k, nprobes, bounds, row_ids, 
         row_ids.astype(np.uint64).tofile(fh); probes.astype(np.uint32).tofile(fh)
         if prefilter is not None:
             bits.tofile(fh)
-    r = subprocess.run([exe, inp, outp], capture_output=True, text=True, timeout=600)
+    r = subprocess.run([exe, inp, outp] + ([str(shift)] if shift else []), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout[-1000:] + r.stderr[-4000:]
+    if want_wide is not None:
+        assert f"sq_distance wide {int(want_wide)}" in r.stdout, r.stdout
     raw = np.fromfile(outp, np.uint8)
+    if shift:
+        return raw
     pos = 0
 
     def take(count, dt):
@@ -163,6 +167,26 @@ def test_row_addresses(emulator, oracle):
     b = S.bounds(x[100:164])
     assert run_case(emulator, oracle, x, q, cent, "l2", 10, 3, b, rid) < 2
     run_case(emulator, oracle, x, q, cent, "l2", 128, 8, b, rid, prefilter=np.ones(1000, bool))
+
+
+@pytest.mark.parametrize("d", [16, 20])
+def test_offset_bases(emulator, oracle, d):
+    """Caller-owned bases 1, 4 and 8 bytes off the 16-byte grid: the codes handed to sq_distance (both readers; at d = 16 the host's
+    gate must leave the 16-byte reader), and at 4 and 8 the f32 rows and keys read by the bounds and encode kernels.  Every buffer ends
+    with its last element, so the sanitizers see a read past a row or a misaligned wide load; every output byte equals the aligned run's."""
+    src = open(os.path.join(CSRC, "sq.hip")).read()
+    gate = "const bool wide = d % 16 == 0 && (reinterpret_cast<uintptr_t>(codes) & 15) == 0;"
+    assert gate in src, f"sq.hip no longer holds {gate!r} (the gate of lance_hip_sq_distance): tests/c/simt_emu/sq_kernels_main.cpp mirrors it, update both"
+    x, q = S.gaussian(300, d, 2, seed=8)
+    rid = S.permuted_ids(300, 3)
+    cent = S.centroids_with_gaps(x[:250], 4, seed=2)
+    b = S.bounds(x[50:114])
+    args = (emulator, oracle, x, q, cent, "l2", 10, 3, b, rid)
+    run_case(*args, want_wide=True if d == 16 else None)
+    aligned = np.fromfile(str(emulator[1] / "out.bin"), np.uint8)
+    for shift in (1, 4, 8):
+        got = run_case(*args, shift=shift, want_wide=False if d == 16 else None)
+        assert np.array_equal(got, aligned), shift
 
 
 def test_constant_column(emulator, oracle):
