@@ -72,6 +72,12 @@ struct FmArgs {
 };
 
 constexpr int FM_SQ_CAP = 2048;
+// The margin E = 2^-12 (|x|^2 + |q|^2) is a RELATIVE bound: it holds while no square, product or sum sits in the denormal range and
+// nothing overflows.  As in mfma_assign.hip / xform_fused.hip / pq_mfma.hip a pair whose E is not above 2^-100 is not filtered at all
+// (E <= 2^-100 needs both 2^-12 |x|^2 and 2^-12 |q|^2 <= 2^-100: that is what is tested), nor is one whose |x|^2 or |q|^2 is not below
+// 2^126 (so xk + |q|^2 stays finite for every pair that IS filtered): the exact evaluation decides those.
+constexpr float FM_E_TINY = 7.888609052210118e-31f;      // 2^-100
+constexpr float FM_NORM_HUGE = 8.507059173023462e37f;    // 2^126
 
 template <int KS, int METRIC, typename TX>
 __global__ __launch_bounds__(256, LH_FM_WAVES) void flat_filter_mfma_kernel(FmArgs a) {
@@ -82,7 +88,8 @@ __global__ __launch_bounds__(256, LH_FM_WAVES) void flat_filter_mfma_kernel(FmAr
   float *xs = reinterpret_cast<float *>(smem);                       // [FM_ROWS][XS]  (phase 1)
   uint16_t *qbuf = reinterpret_cast<uint16_t *>(smem);               // [2][2][FM_QT][CS] bf16 (phase 2)
   float *tqs = reinterpret_cast<float *>(smem + (size_t)2 * 2 * FM_QT * CS * 2);   // [2][FM_QT] threshold + query part of E
-  float *qns = tqs + 2 * FM_QT;                                                     // [2][FM_QT] |q|^2 (dot: unused)
+  float *qns = tqs + 2 * FM_QT;                                                     // [2][FM_QT] |q|^2
+  uint32_t *qodd = reinterpret_cast<uint32_t *>(qns + 2 * FM_QT);                   // [2] the tile holds a query whose |q|^2 is not below 2^126
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int j = lane & 31, g = lane >> 5;
   const int64_t row0 = p.r0 + (int64_t)blockIdx.x * FM_ROWS;
@@ -116,6 +123,11 @@ __global__ __launch_bounds__(256, LH_FM_WAVES) void flat_filter_mfma_kernel(FmAr
   // per-lane constant of the test  s - E <= T  <=>  (|q|^2 (1 - 2^-12) + T)'s partner: xk = |x|^2 (1 - 2^-12)
   const float xk = METRIC == METRIC_DOT ? -0.000244140625f * xn2 : xn2 - 0.000244140625f * xn2;
 
+  // rows outside the range where the margin holds (see FM_E_TINY): odd -- every query takes the row; tiny -- every query whose own
+  // 2^-12 |q|^2 is not above 2^-100 takes it, the others keep the filter (their |q|^2 carries the margin)
+  const bool odd = !(xn2 < FM_NORM_HUGE);
+  const bool tiny = !(0.000244140625f * xn2 > FM_E_TINY);
+  const bool slow_row = odd || tiny;
   const int ntiles = (p.nq + FM_QT - 1) / FM_QT;
   constexpr int NCH = FM_QT * D / 8;
   constexpr int CH = (NCH + 255) / 256;
@@ -143,6 +155,9 @@ __global__ __launch_bounds__(256, LH_FM_WAVES) void flat_filter_mfma_kernel(FmAr
         const float T = tk >= 0xFF800000u ? INFINITY : key_to_float(tk);
         pqn = qn;
         ptq = METRIC == METRIC_DOT ? T + 0.000244140625f * qn + 4.7683716e-7f : T - (qn - 0.000244140625f * qn);      // (dot, + 2^-22: the reference's distance is the f32 value of 1 - x.q)   // s' <= ptq  with  s' = xk - 2 x.q  (dot: xk + 1 - x.q)
+        // |q|^2 at the top of the range or a NaN (T - |q|^2 is a NaN once it overflowed, xk + |q|^2 may overflow below it, the
+        // products may be inf - inf): every row passes, through the slow path (qodd)
+        if (!(qn < FM_NORM_HUGE)) ptq = INFINITY;
       }
     }
   };
@@ -157,7 +172,11 @@ __global__ __launch_bounds__(256, LH_FM_WAVES) void flat_filter_mfma_kernel(FmAr
         *reinterpret_cast<uint4 *>(lo + cr * CS + cc * 8) = pl[u];
       }
     }
-    if (threadIdx.x < FM_QT) { tqs[buf * FM_QT + threadIdx.x] = ptq; qns[buf * FM_QT + threadIdx.x] = pqn; }
+    if (threadIdx.x < FM_QT) {      // (wave 0, whole)
+      tqs[buf * FM_QT + threadIdx.x] = ptq; qns[buf * FM_QT + threadIdx.x] = pqn;
+      const bool any_odd = __any(!(pqn < FM_NORM_HUGE));
+      if (threadIdx.x == 0) qodd[buf] = any_odd ? 1u : 0u;
+    }
   };
   const int t0 = blockIdx.z;
   if (t0 >= ntiles) return;
@@ -168,6 +187,7 @@ __global__ __launch_bounds__(256, LH_FM_WAVES) void flat_filter_mfma_kernel(FmAr
   for (int t = t0; t < ntiles; t += gridDim.z, ++it) {
     const int buf = it & 1;
     const int tn = t + gridDim.z;
+    const uint32_t tile_qodd = qodd[buf];      // (read here: the MFMA stream below hides the LDS latency)
     if (tn < ntiles) fetch(tn);
     const uint16_t *hi = qbuf + (size_t)(buf * 2 + 0) * FM_QT * CS, *lo = qbuf + (size_t)(buf * 2 + 1) * FM_QT * CS;
     fm_f32x16 acc0, acc1;
@@ -187,7 +207,7 @@ __global__ __launch_bounds__(256, LH_FM_WAVES) void flat_filter_mfma_kernel(FmAr
       acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al1, xh[s], acc1, 0, 0, 0);
     }
     const int q0 = t * FM_QT;
-    const float *tqb = tqs + buf * FM_QT;
+    const float *tqb = tqs + buf * FM_QT, *qnb = qns + buf * FM_QT;
     // fast reject: minimum over the lane's 32 pairs of  s = xk - 2 x.q - tq'  (dot: xk + 1 - x.q - tq'), two pairs per packed op.
     // A NaN s is ignored by the minimum and fails `<=` in the slow path alike (as `sp <= tq` did).
     const f2 mul2 = METRIC == METRIC_DOT ? f2{-1.0f, -1.0f} : f2{-2.0f, -2.0f};
@@ -211,9 +231,9 @@ __global__ __launch_bounds__(256, LH_FM_WAVES) void flat_filter_mfma_kernel(FmAr
     // Every pair the round-2 test `fma(-2, x.q, xk) <= tq` passed still passes: for finite operands the two forms differ by
     // 2^-24 |xk - tq|, and a pair near the boundary has |xk - tq| ~ 2 |x.q| <= |x|^2 + |q|^2, far inside the 3 * 2^-14 (|x|^2 +
     // |q|^2) the margin has to spare; tq = +inf gives s = -inf; a row whose |x|^2 overflowed (xk not finite: inf - inf = NaN,
-    // which the minimum ignores) takes the slow path with the permissive comparison below.
-    const bool odd = !(__builtin_fabsf(xk1) < INFINITY);
-    if ((mn <= 0.0f || odd) && rvalid) {   // rare per lane (~1 % of lane-tiles): find the pairs, queue the row for each of their queries
+    // which the minimum ignores) takes the slow path below as an `odd` row.
+    const bool special = slow_row || tile_qodd != 0u;      // (false on every lane for ordinary data: the branches on it are skipped)
+    if ((mn <= 0.0f || special) && rvalid) {   // rare per lane (~1 % of lane-tiles): find the pairs, queue the row for each of their queries
 #pragma unroll
       for (int blk = 0; blk < 2; ++blk) {
 #pragma unroll
@@ -224,8 +244,13 @@ __global__ __launch_bounds__(256, LH_FM_WAVES) void flat_filter_mfma_kernel(FmAr
           for (int e = 0; e < 4; ++e) {
             const float dot = blk ? acc1[vq * 4 + e] : acc0[vq * 4 + e];
             const float sv = __builtin_fmaf(mul2.x, dot, xk1 - tq4[e]);
-            if (odd ? !(sv > 0.0f) : (sv <= 0.0f)) {
-              const int qi = q0 + ib + e;   // < nq: padded queries carry tq' = -inf
+            const int qi = q0 + ib + e;   // padded queries (qi >= nq) carry tq' = -inf: sv is +inf or a NaN, `<=` fails
+            bool pass = sv <= 0.0f;
+            if (special) {                // ... but a row or query outside the margin's range passes without looking at sv: check qi
+              const float qn = qnb[ib + e];
+              pass = qi < p.nq && (pass || odd || !(qn < FM_NORM_HUGE) || (tiny && !(0.000244140625f * qn > FM_E_TINY)));
+            }
+            if (pass) {
               const uint32_t pos = atomicAdd(&a.scnt[qi], 1u);
               if (pos < (uint32_t)FM_SQ_CAP) a.squeue[(int64_t)qi * FM_SQ_CAP + pos] = (uint32_t)(row - p.r0);
             }
@@ -285,7 +310,7 @@ int flat_mfma_prepare(lance_hip_ctx *ctx, const float *q, int nq, int d, const u
 template <int KS>
 static void fm_launch_ks(lance_hip_ctx *ctx, const FmArgs &a, int metric, dim3 grid) {
   constexpr int D = KS * 16;
-  const size_t lds = std::max((size_t)FM_ROWS * (D + 4) * 4, (size_t)2 * 2 * FM_QT * (D + 8) * 2 + (size_t)4 * FM_QT * 4);
+  const size_t lds = std::max((size_t)FM_ROWS * (D + 4) * 4, (size_t)2 * 2 * FM_QT * (D + 8) * 2 + (size_t)4 * FM_QT * 4 + 16);
   auto go = [&](auto tag) {
     using TX = decltype(tag);
     if (metric == METRIC_DOT) hipLaunchKernelGGL((flat_filter_mfma_kernel<KS, METRIC_DOT, TX>), grid, dim3(256), lds, ctx->stream, a);
@@ -333,6 +358,7 @@ int launch_flat_filter_mfma(lance_hip_ctx *ctx, const FlatPool &e, int d, int me
     default: fm_launch_ks<8>(ctx, a, metric, grid); break;
   }
   fm_launch_eval(ctx, a, metric, d);
+  ctx->count_stage("flat_mfma");      // tests assert that this filter served the epoch
   LH_CHECK_HIP(hipGetLastError());
   return LANCE_HIP_OK;
 }

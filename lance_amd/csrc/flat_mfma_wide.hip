@@ -53,6 +53,13 @@ typedef float fw_f32x16 __attribute__((ext_vector_type(16)));
 constexpr int FW_SQ_CAP = 2048;       // queued rows per query and epoch
 constexpr float FW_EW = 0.0084f;      // > 2^-7 + 2^-16 + 4096 * 2^-23 = 0.00832 (first written as 0.0045 = one operand's roundoff: the CPU spec test caught it)
 constexpr float FW_EWC = 0.0085f;
+// The margins are RELATIVE bounds: they hold while no square, product or sum sits in the denormal range and nothing overflows.  As in
+// flat_mfma.hip a pair whose 2^-12 (|x|^2 + |q|^2) is not above 2^-100 (both terms are tested) is not filtered, nor is one whose |x|^2 or
+// |q|^2 is not below 2^126; under cosine the product of the norms carries the margin, so a norm not above 2^-50 on EITHER side (its square
+// was summed among denormals) makes the row or the query degenerate.  The exact evaluation decides all of those.
+constexpr float FW_E_TINY = 7.888609052210118e-31f;      // 2^-100
+constexpr float FW_NORM_HUGE = 8.507059173023462e37f;    // 2^126
+constexpr float FW_COS_TINY = 8.881784197001252e-16f;    // 2^-50
 
 __device__ __forceinline__ uint32_t fw_bf16_rne(float x) {
   const uint32_t u = __float_as_uint(x);
@@ -135,6 +142,7 @@ __global__ __launch_bounds__(256, 2) void flat_filter_mfma_wide_kernel(FwArgs a)
   const int64_t row0 = p.r0 + (int64_t)rt * (64 * BR);
 
   // per-query threshold term
+  int q_odd = 0;      // this thread's query passes every row (norm at the top of the range or a NaN: the products may be inf - inf)
   if (threadIdx.x < FW_TN) {
     const int qi = q0 + threadIdx.x;
     float t;
@@ -143,12 +151,15 @@ __global__ __launch_bounds__(256, 2) void flat_filter_mfma_wide_kernel(FwArgs a)
       const float T = tk >= 0xFF800000u ? INFINITY : key_to_float(tk);      // no threshold yet / NaN threshold: every row is a candidate
       if constexpr (METRIC == METRIC_COSINE) {
         const float qn = p.q_norm[qi];
-        t = (qn > 0.0f && qn < INFINITY) ? (1.0f - FW_EWC - T) * qn : -INFINITY;      // degenerate query: everything passes to the exact evaluation
+        t = (qn > FW_COS_TINY && qn < INFINITY) ? (1.0f - FW_EWC - T) * qn : -INFINITY;      // degenerate query: everything passes to the exact evaluation
+        q_odd = !(qn > FW_COS_TINY && qn < INFINITY);
       } else if constexpr (METRIC == METRIC_DOT) {
         t = T + FW_EW * a.qn2[qi] + 4.7683716e-7f;      // (+ 2^-22: the reference's distance is the f32 value of 1 - x.q -- products closer than an ulp of 1 tie there)
+        q_odd = !(a.qn2[qi] < FW_NORM_HUGE);
       } else {
         const float qn = a.qn2[qi];
         t = T - (qn - FW_EW * qn);
+        q_odd = !(qn < FW_NORM_HUGE);
       }
     } else {
       t = METRIC == METRIC_COSINE ? INFINITY : -INFINITY;      // padded query: nothing passes (and the queue test below checks qi < nq)
@@ -192,7 +203,7 @@ __global__ __launch_bounds__(256, 2) void flat_filter_mfma_wide_kernel(FwArgs a)
 
   fetch(0);
   store();
-  __syncthreads();
+  const bool tile_qodd = __syncthreads_or(q_odd) != 0;      // some query of the tile takes every row: all lanes walk the pairs
   for (int k0 = 0; k0 < d; k0 += FW_KT) {
     const bool more = k0 + FW_KT < d;
     if (more) fetch(k0 + FW_KT);
@@ -219,15 +230,17 @@ __global__ __launch_bounds__(256, 2) void flat_filter_mfma_wide_kernel(FwArgs a)
     const int64_t row = row0 + wr * 32 * BR + bi * 32 + j;
     const bool rvalid = row < p.r1;
     float xk = 0.0f;        // per-row constant of the test
-    bool odd = false;       // row whose norm is not usable: permissive comparison
+    bool odd = false;       // row whose norm is not usable: every query takes it
+    bool tiny = false;      // row whose part of the margin is in the denormal range: the queries that are tiny too take it
     if (rvalid) {
       if constexpr (METRIC == METRIC_COSINE) {
         xk = p.row_sy[row];      // sqrt(y_norm) of the reference
-        odd = !(xk > 0.0f && xk < INFINITY);
+        odd = !(xk > FW_COS_TINY && xk < INFINITY);
       } else {
         const float n2 = a.xn2[row];
         xk = METRIC == METRIC_DOT ? 1.0f - FW_EW * n2 : n2 - FW_EW * n2;
-        odd = !(__builtin_fabsf(xk) < INFINITY);
+        odd = !(n2 < FW_NORM_HUGE);
+        tiny = !(0.000244140625f * n2 > FW_E_TINY);
       }
     }
     float mn = INFINITY;
@@ -248,7 +261,7 @@ __global__ __launch_bounds__(256, 2) void flat_filter_mfma_wide_kernel(FwArgs a)
         }
       }
     }
-    if ((mn <= 0.0f || odd) && rvalid) {      // rare per lane: find the pairs, queue the row for each of their queries
+    if ((mn <= 0.0f || odd || tiny || tile_qodd) && rvalid) {      // rare per lane: find the pairs, queue the row for each of their queries
 #pragma unroll
       for (int bj = 0; bj < BQ; ++bj) {
         const float *tqb = tqs + wq * 32 * BQ + bj * 32 + 4 * g;
@@ -263,7 +276,16 @@ __global__ __launch_bounds__(256, 2) void flat_filter_mfma_wide_kernel(FwArgs a)
             else if constexpr (METRIC == METRIC_DOT) sv = (xk - t4[e]) - dot;
             else sv = __builtin_fmaf(-2.0f, dot, xk - t4[e]);
             const int qi = q0 + wq * 32 * BQ + bj * 32 + 8 * vq + 4 * g + e;
-            if (qi < p.nq && (odd ? !(sv > 0.0f) : (sv <= 0.0f))) {
+            bool pass = false;
+            if (qi < p.nq) {
+              pass = odd || sv <= 0.0f;
+              if constexpr (METRIC == METRIC_COSINE) {
+                if (!pass && tile_qodd) { const float qn = p.q_norm[qi]; pass = !(qn > FW_COS_TINY && qn < INFINITY); }
+              } else {
+                if (!pass && (tile_qodd || tiny)) { const float qn = a.qn2[qi]; pass = !(qn < FW_NORM_HUGE) || (tiny && !(0.000244140625f * qn > FW_E_TINY)); }
+              }
+            }
+            if (pass) {
               const uint32_t pos = atomicAdd(&a.scnt[qi], 1u);
               if (pos < (uint32_t)FW_SQ_CAP) a.squeue[(int64_t)qi * FW_SQ_CAP + pos] = (uint32_t)(row - p.r0);
             }

@@ -234,6 +234,7 @@ __global__ __launch_bounds__(256) void ms_prep_kernel(MsPrepArgs p) {
     eu = E * s * 1.1f + 3.0f;
     lim = (T * 1.0000077f + E) - n2l;  // T (1 + 2^-17) + E - |r|^2; the cancellation's rounding sits inside the 2^-13 term
     zsum = (T * 1.0000077f + E) * s;
+    // (tests/magnitude_spec.py: ms_pair_ok_l2 mirrors this branch, lines 230-238, to place its sweep where `ok` flips: change both together)
     ok = !badl && T > 0.0f && T < INFINITY && s > 0.0f && s < INFINITY && n2l < INFINITY && vml * p.sigma < 60000.0f &&
          eu <= MS_SLACK_CAP && fabsf(lim * sig2) < INFINITY && n2l * s < 1e30f;
   }

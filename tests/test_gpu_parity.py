@@ -1144,6 +1144,7 @@ def test_flat_batch_on_matrix_cores_bit_exact(eng, oracle, d, metric):
     included, and the run with LANCE_HIP_NO_MFMA_FLAT (exact VALU kernel) must agree bit for bit."""
     rng = np.random.default_rng(d)
     n, nq = 60000, 300
+    served = eng.timing_query("count:flat_mfma")[1]
     x = sift_like(n, d, 900 + d)
     x[1000:1040] = x[7]                              # 40 identical rows: ties broken by row id
     q = sift_like(nq, d, 901 + d)
@@ -1160,6 +1161,7 @@ def test_flat_batch_on_matrix_cores_bit_exact(eng, oracle, d, metric):
     gi, gd = eng.flat_topk(xr, qr, 10, metric)
     oi, od = oracle.flat_knn(xr, qr, 10, metric)
     assert (_np(gi).view(np.uint64) == oi).all() and (_np(gd).view(np.uint32) == od.view(np.uint32)).all()
+    assert eng.timing_query("count:flat_mfma")[1] >= served + 3, "flat_mfma.hip did not serve the three calls"
 
 
 @pytest.mark.parametrize("kind,metric", [("f16", "l2"), ("int8", "l2"), ("int8", "dot")])
