@@ -448,6 +448,35 @@ int lance_hip_flat_multivec_topk(lance_hip_ctx *ctx, int dtype, int metric, cons
                                  const uint64_t *row_ids, uint64_t n_rows, uint32_t d, const void *q, uint32_t nqv,
                                  uint32_t k, uint64_t *ids, float *dists);
 
+/* ---- multivector ANN: per-query-vector candidate lists joined by row id and scored with XTR-style imputation ----------
+ * (Scanner::multivec_ann, scanner.rs:3471-3552; MultivectorScoringExec, knn.rs:1132-1329).  The index is an ordinary IVF_PQ index
+ * over the FLATTENED vectors of the column whose row_ids repeat the row's id once per vector; one ANN search per query vector
+ * gives a candidate list of keff = k * overfetch pairs in (dist, rowid) order.  For a multivector query of nqv vectors, every
+ * operation one f32 rounding, lists taken in query-vector order j = 0 .. nqv - 1:
+ *   min_sim_j = 1 - (distance of the list's last entry), 0 for an empty list;  sim_j(r) = 1 - dist of r's FIRST entry in list j
+ *   missed_j  = ((0 + min_sim_0) + min_sim_1) + ... + min_sim_{j-1}
+ *   s(r)      = sim_{j0}(r) + missed_{j0}, j0 = r's first list;  then for j = j0 + 1 .. nqv - 1: s += r in list j ? sim_j(r) : min_sim_j
+ *   distance  = (float)nqv - s
+ * and the k_out smallest by (distance in total order, row id) come back; slots beyond the joined rows: id UINT64_MAX, +inf.
+ * (The reference joins the lists in stream-arrival order; order 0 .. nqv - 1 is one of those and is this library's definition.)
+ * Limits, each refused with LANCE_HIP_EINVAL: 1 <= nqv <= LANCE_HIP_MULTIVEC_MAX_QUERY_VECTORS per query,
+ * 1 <= keff <= LANCE_HIP_MULTIVEC_ANN_MAX_KEFF, 1 <= k_out <= LANCE_HIP_MULTIVEC_ANN_MAX_K_OUT.                                  */
+#define LANCE_HIP_MULTIVEC_ANN_MAX_KEFF 4096
+#define LANCE_HIP_MULTIVEC_ANN_MAX_K_OUT 1024
+/* The join and score stage alone, for a batch of B multivector queries: cand_ids / cand_dists [q_offsets[B]][keff] (device) hold
+ * one list per query vector -- valid entries first, then id UINT64_MAX / +inf --, the lists of query b are rows
+ * q_offsets[b] .. q_offsets[b + 1] - 1; q_offsets [B + 1] is a HOST array starting at 0.  ids / dists [B][k_out] (device).  Any
+ * index type's lists will do.                                                                                                  */
+int lance_hip_multivec_xtr_score(lance_hip_ctx *ctx, const uint64_t *cand_ids, const float *cand_dists,
+                                 const uint64_t *q_offsets, uint32_t B, uint32_t keff, uint32_t k_out, uint64_t *ids,
+                                 float *dists);
+/* One IVF_PQ search of all q_offsets[B] query vectors (q [q_offsets[B]][d] in the index's element type, device) with
+ * k = keff = k * overfetch and no refine, into the context's scratch, then the stage above.  allow_by_rowid / n_allow as in
+ * lance_hip_ivfpq_search_filtered (NULL: no prefilter).                                                                        */
+int lance_hip_ivfpq_multivec_search(lance_hip_ctx *ctx, const lance_hip_index *idx, const void *q, const uint64_t *q_offsets,
+                                    uint32_t B, uint32_t k, uint32_t nprobes, uint32_t overfetch, uint32_t k_out,
+                                    const uint8_t *allow_by_rowid, uint64_t n_allow, uint64_t *ids, float *dists);
+
 /* ---- N4: IVF_FLAT (FlatIndex sub-index over raw vectors: flat/index.rs:82-177, flat/storage.rs:345-402) ------ */
 /* Builds the per-partition FlatFloatStorage on the device: x[n][d] (dtype elements, widened exactly to f32) is
  * gathered into partition order (stable, rows with part id LANCE_HIP_NONE dropped).  L2, Dot and Cosine (f32 and f16 columns;

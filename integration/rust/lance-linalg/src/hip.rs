@@ -159,6 +159,17 @@ extern "C" {
     /// the same followed by SortExec(dist, rowid).fetch(k) (flat.rs:129-133); row_ids NULL -> row index
     pub fn lance_hip_flat_multivec_topk(ctx: *mut LanceHipCtx, dtype: i32, metric: i32, values: *const c_void, offsets: *const u64,
         row_ids: *const u64, n_rows: u64, d: u32, q: *const c_void, nqv: u32, k: u32, ids: *mut u64, dists: *mut f32) -> i32;
+    /// MultivectorScoringExec (knn.rs:1132-1329) for a batch of `b` multivector queries: `cand_ids` / `cand_dists` [q_offsets[b]][keff]
+    /// (device) hold one candidate list per query vector in (dist, rowid) order, `q_offsets` [b + 1] is a HOST array; the lists are
+    /// joined in query-vector order and the `k_out` best rows by (distance, row id) written to `ids` / `dists` [b][k_out] (device).
+    pub fn lance_hip_multivec_xtr_score(ctx: *mut LanceHipCtx, cand_ids: *const u64, cand_dists: *const f32, q_offsets: *const u64,
+        b: u32, keff: u32, k_out: u32, ids: *mut u64, dists: *mut f32) -> i32;
+    /// Scanner::multivec_ann (scanner.rs:3471-3552) on an IVF_PQ index over the flattened vectors of a multivector column (row ids
+    /// repeated per vector): one search of all query vectors with k * overfetch candidates each, then the stage above.
+    /// `allow_by_rowid` NULL: no prefilter.
+    pub fn lance_hip_ivfpq_multivec_search(ctx: *mut LanceHipCtx, idx: *const LanceHipIndex, q: *const c_void, q_offsets: *const u64,
+        b: u32, k: u32, nprobes: u32, overfetch: u32, k_out: u32, allow_by_rowid: *const u8, n_allow: u64, ids: *mut u64,
+        dists: *mut f32) -> i32;
 }
 
 /// Maps a return code to the error type the reference path already produces (`Error::Index`), with the library's message.

@@ -10,7 +10,7 @@ from . import _lib
 from ._lib import LanceHipError
 
 __all__ = ["_lib", "LanceHipError", "Engine", "DeviceIndex", "KMeans", "IvfPqParams", "IvfPqIndex", "IvfSqIndex", "DeviceSqIndex", "IvfRqIndex", "DeviceRqIndex", "create_index",
-           "flat_knn", "multivector_distance", "multivector_flat_knn", "train_ivf_centroids", "train_pq_codebook", "train_sq_bounds", "default_engine", "load_index",
+           "flat_knn", "multivector_distance", "multivector_flat_knn", "create_multivector_index", "IvfPqMultivectorIndex", "train_ivf_centroids", "train_pq_codebook", "train_sq_bounds", "default_engine", "load_index",
            "validate_vector_index", "merge_indices", "target_partition_size", "should_split", "should_join", "IndicesBuilder", "IvfModel", "PqModel"]
 
 
@@ -20,6 +20,7 @@ def __getattr__(name):
         from . import engine
         return getattr(engine, name)
     if name in ("KMeans", "IvfPqParams", "IvfPqIndex", "create_index", "flat_knn", "multivector_distance", "multivector_flat_knn",
+                "create_multivector_index", "IvfPqMultivectorIndex",
                 "train_ivf_centroids", "IvfSqIndex", "IvfRqIndex", "train_sq_bounds",
                 "train_pq_codebook", "default_engine", "load_index", "validate_vector_index", "merge_indices", "target_partition_size",
                 "should_split", "should_join"):

@@ -18,6 +18,8 @@ REASSIGN_SPLIT, REASSIGN_JOIN = 0, 1      # LANCE_HIP_REASSIGN_* (include/lance_
 SQ_MAX_DIM = 16384                   # LANCE_HIP_SQ_MAX_DIM (include/lance_hip.h)
 RQ_MAX_DIM = 2048                    # LANCE_HIP_RQ_MAX_DIM (include/lance_hip.h)
 MULTIVEC_MAX_QUERY_VECTORS = 256     # LANCE_HIP_MULTIVEC_MAX_QUERY_VECTORS (include/lance_hip.h)
+MULTIVEC_ANN_MAX_KEFF = 4096         # LANCE_HIP_MULTIVEC_ANN_MAX_KEFF (include/lance_hip.h)
+MULTIVEC_ANN_MAX_K_OUT = 1024        # LANCE_HIP_MULTIVEC_ANN_MAX_K_OUT (include/lance_hip.h)
 U64_MAX = 0xFFFFFFFFFFFFFFFF
 ROW_DELETED = U64_MAX               # LANCE_HIP_ROW_DELETED (include/lance_hip.h)
 
@@ -36,7 +38,8 @@ SYMBOLS = [
     "lance_hip_pq_scan_topk", "lance_hip_ivfpq_search", "lance_hip_ivfpq_search_async", "lance_hip_ivfpq_search_range",
     "lance_hip_ivfpq_search_candidates",
     "lance_hip_search_stats", "lance_hip_ivfpq_search_filtered", "lance_hip_ivfpq_search_filtered_range",
-    "lance_hip_flat_topk", "lance_hip_multivec_distance", "lance_hip_flat_multivec_topk", "lance_hip_ivfflat_create", "lance_hip_ivfflat_search", "lance_hip_ivfflat_search_filtered",
+    "lance_hip_flat_topk", "lance_hip_multivec_distance", "lance_hip_flat_multivec_topk",
+    "lance_hip_multivec_xtr_score", "lance_hip_ivfpq_multivec_search", "lance_hip_ivfflat_create", "lance_hip_ivfflat_search", "lance_hip_ivfflat_search_filtered",
     "lance_hip_sq_bounds", "lance_hip_sq_encode", "lance_hip_sq_distance", "lance_hip_ivfsq_create", "lance_hip_ivfsq_search", "lance_hip_ivfsq_search_filtered",
     "lance_hip_ivfsq_search_refine", "lance_hip_ivfrq_search_refine",
     "lance_hip_rq_encode", "lance_hip_rq_distance", "lance_hip_ivfrq_create", "lance_hip_ivfrq_search", "lance_hip_ivfrq_search_filtered",
@@ -148,6 +151,8 @@ def load():
         "lance_hip_flat_topk": (i32, [vp, i32, i32, vp, vp, u64, u32, vp, u32, u32, vp, vp]),
         "lance_hip_multivec_distance": (i32, [vp, i32, i32, vp, vp, u64, u32, vp, u32, vp]),
         "lance_hip_flat_multivec_topk": (i32, [vp, i32, i32, vp, vp, vp, u64, u32, vp, u32, u32, vp, vp]),
+        "lance_hip_multivec_xtr_score": (i32, [vp, vp, vp, vp, u32, u32, u32, vp, vp]),
+        "lance_hip_ivfpq_multivec_search": (i32, [vp, vp, vp, vp, u32, u32, u32, u32, u32, vp, u64, vp, vp]),
         "lance_hip_ivfflat_create": (i32, [vp, i32, i32, u32, vp, u32, vp, vp, vp, u64, C.POINTER(vp)]),
         "lance_hip_ivfflat_search": (i32, [vp, vp, vp, u32, u32, u32, vp, vp]),
         "lance_hip_ivfflat_search_filtered": (i32, [vp, vp, vp, u32, u32, u32, vp, u64, vp, vp]),

@@ -115,6 +115,28 @@ def check_multivector(values, offsets, q, metric, k=None):
     return m, off
 
 
+def check_query_offsets(q_offsets):
+    """q_offsets [B + 1] of a batch of multivector queries (query b holds the vectors q_offsets[b] .. q_offsets[b + 1] - 1) -> a
+    contiguous uint64 numpy array; every query holds 1 .. MULTIVEC_MAX_QUERY_VECTORS vectors"""
+    off = np.ascontiguousarray(np.asarray(q_offsets.detach().cpu().numpy() if isinstance(q_offsets, torch.Tensor) else q_offsets).astype(np.int64))
+    if off.ndim != 1 or off.size < 1 or off[0] != 0:
+        raise ValueError("q_offsets must be a 1-D array of B + 1 entries starting at 0")
+    nqv = np.diff(off)
+    if (nqv < 1).any():
+        raise ValueError(f"query {int(np.argmax(nqv < 1))} holds no vector: a multivector query has at least one")
+    if (nqv > _lib.MULTIVEC_MAX_QUERY_VECTORS).any():
+        b = int(np.argmax(nqv > _lib.MULTIVEC_MAX_QUERY_VECTORS))
+        raise ValueError(f"query {b} holds {int(nqv[b])} vectors, above the limit of {_lib.MULTIVEC_MAX_QUERY_VECTORS} query vectors per query")
+    return off.astype(np.uint64)
+
+
+def check_multivector_ann_sizes(keff, k_out):
+    if not 1 <= int(keff) <= _lib.MULTIVEC_ANN_MAX_KEFF:
+        raise ValueError(f"keff = k * overfetch = {keff} candidates per query vector not supported (1..{_lib.MULTIVEC_ANN_MAX_KEFF})")
+    if not 1 <= int(k_out) <= _lib.MULTIVEC_ANN_MAX_K_OUT:
+        raise ValueError(f"k_out = k * refine_factor = {k_out} not supported (1..{_lib.MULTIVEC_ANN_MAX_K_OUT})")
+
+
 _DT = {"float32": (torch.float32, 0), "float16": (torch.float16, 1), "int8": (torch.int8, 2)}
 
 SQ_FRESH_BOUNDS = (float(np.finfo(np.float64).max), float(np.finfo(np.float64).min))     # ScalarQuantizer::new (sq.rs:43-55)
@@ -510,6 +532,27 @@ class Engine:
         torch.cuda.synchronize()
         check(self.lib.lance_hip_flat_multivec_topk(self.h, dt, METRICS[m], _ptr(v), _ptr(od), _ptr(rid), n, v.shape[1], _ptr(qd),
                                                     qd.shape[0], k, _ptr(ids), _ptr(dists)))
+        return ids, dists
+
+    def multivec_xtr_score(self, cand_ids, cand_dists, q_offsets, k_out):
+        """The join and score stage of the multivector ANN search (lance_hip_multivec_xtr_score; MultivectorScoringExec,
+        knn.rs:1132-1329) for a batch of B multivector queries: cand_ids / cand_dists [sum nqv][keff] hold one candidate list per
+        query vector in (distance, row id) order (valid entries first, then id -1 / +inf), the lists of query b are rows
+        q_offsets[b] .. q_offsets[b + 1] - 1.  -> (ids [B][k_out] int64 (-1 = none), distances [B][k_out]) sorted by (distance, row id)"""
+        off = check_query_offsets(q_offsets)
+        B = off.size - 1
+        ci = to_device(cand_ids, torch.int64)
+        cd = to_device(cand_dists, torch.float32)
+        if ci.dim() != 2 or tuple(ci.shape) != tuple(cd.shape) or ci.shape[0] != int(off[-1]):
+            raise ValueError(f"cand_ids / cand_dists must both be [{int(off[-1])}][keff] (one list per query vector), got "
+                             f"{tuple(ci.shape)} and {tuple(cd.shape)}")
+        keff = int(ci.shape[1])
+        check_multivector_ann_sizes(keff, k_out)
+        ids = torch.empty((B, k_out), dtype=torch.int64, device=ci.device)
+        dists = torch.empty((B, k_out), dtype=torch.float32, device=ci.device)
+        torch.cuda.synchronize()
+        check(self.lib.lance_hip_multivec_xtr_score(self.h, _ptr(ci), _ptr(cd), off.ctypes.data_as(C.c_void_p), B, keff, k_out, _ptr(ids),
+                                                    _ptr(dists)))
         return ids, dists
 
     # ---- 8-bit scalar quantisation (lance-index/src/vector/sq.rs) -------------------------
@@ -1197,6 +1240,35 @@ class DeviceIndex:
         _torch_inputs_ready()
         check(self.engine.lib.lance_hip_ivfpq_search_filtered(self.engine.h, self.h, _ptr(q), nq, k, nprobes, refine_factor, _ptr(a),
                                                               a.numel(), _ptr(ids), _ptr(dists)))
+        return ids, dists
+
+    def multivec_search(self, q, q_offsets, k, nprobes, overfetch=10, k_out=None, allow=None):
+        """ANN search of a multivector column through THIS index over its flattened vectors (row ids repeated per vector), for a
+        batch of B multivector queries: q [sum nqv][d], the vectors of query b are rows q_offsets[b] .. q_offsets[b + 1] - 1.  One
+        IVF_PQ search of all query vectors with k = k * overfetch, then the join by row id (lance_hip_ivfpq_multivec_search).
+        allow: boolean array indexed by row id (the prefilter).  -> (ids [B][k_out] int64 (-1 = none), distances [B][k_out]),
+        k_out = k by default"""
+        off = check_query_offsets(q_offsets)
+        B = off.size - 1
+        k_out = int(k if k_out is None else k_out)
+        if int(k) < 1 or int(overfetch) < 1:
+            raise ValueError(f"k={k}, overfetch={overfetch}: both must be at least 1")
+        check_multivector_ann_sizes(int(k) * int(overfetch), k_out)
+        d = self.centroids.shape[1]
+        t = q if isinstance(q, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(q))
+        q = t.to(self.data_dtype).to(_dev()).contiguous().reshape(-1, d)
+        if q.shape[0] != int(off[-1]):
+            raise ValueError(f"q holds {q.shape[0]} vectors, q_offsets end at {int(off[-1])}")
+        a = None
+        if allow is not None:
+            a = allow if isinstance(allow, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(allow, dtype=bool))
+            a = a.to(torch.uint8).to(_dev()).contiguous()
+        ids = torch.empty((B, k_out), dtype=torch.int64, device=q.device)
+        dists = torch.empty((B, k_out), dtype=torch.float32, device=q.device)
+        _torch_inputs_ready()
+        check(self.engine.lib.lance_hip_ivfpq_multivec_search(self.engine.h, self.h, _ptr(q), off.ctypes.data_as(C.c_void_p), B, int(k),
+                                                              min(int(nprobes), self.centroids.shape[0]), int(overfetch), k_out, _ptr(a),
+                                                              0 if a is None else a.numel(), _ptr(ids), _ptr(dists)))
         return ids, dists
 
     def search_candidates(self, q, keff, nprobes, exact=True, engine=None):

@@ -20,8 +20,9 @@ from typing import Optional
 import numpy as np
 import torch
 
-from ._lib import EINVAL, METRICS, NONE, ROW_DELETED, LanceHipError
-from .engine import DeviceFlatIndex, DeviceIndex, DeviceRqIndex, DeviceSqIndex, Engine, _dtype_name, _export_ids, check_multivector, to_device
+from ._lib import EINVAL, METRICS, MULTIVEC_MAX_QUERY_VECTORS, NONE, ROW_DELETED, LanceHipError
+from .engine import (DeviceFlatIndex, DeviceIndex, DeviceRqIndex, DeviceSqIndex, Engine, _dtype_name, _export_ids, check_multivector,
+                     check_multivector_ann_sizes, to_device)
 
 _engine = None
 
@@ -910,10 +911,11 @@ def _transform_rows(eng, itype, metric, x, cent, codebook=None, bounds=None, tim
 
 
 def create_index(x, index_type="IVF_PQ", metric="l2", num_partitions=256, num_sub_vectors=16, num_bits=None, max_iters=50,
-                 sample_rate=256, ivf_centroids=None, pq_codebook=None, seed=42, keep_raw=True, engine=None, rq_rotation=None):
+                 sample_rate=256, ivf_centroids=None, pq_codebook=None, seed=42, keep_raw=True, engine=None, rq_rotation=None, _row_ids=None):
     """Dataset.create_index(column, "IVF_PQ", ...) for a vector matrix resident (or copied) in HBM.
     num_bits: None = the index type's default (8 for IVF_PQ / IVF_SQ, 1 for IVF_RQ, as in the reference's build parameters).
-    rq_rotation: IVF_RQ only (ignored otherwise) -- the [d][d] float32 rotation of the model; None: rq_rotation_matrix(d, seed)."""
+    rq_rotation: IVF_RQ only (ignored otherwise) -- the [d][d] float32 rotation of the model; None: rq_rotation_matrix(d, seed).
+    _row_ids: IVF_PQ only, create_multivector_index's -- the id stored with every row (several rows may share one); None: the row index."""
     # ---- argument rules of Dataset.create_index (python/python/lance/dataset.py:2708-2960), checked before any device work
     if not isinstance(metric, str):
         raise ValueError(f"Metric {metric} not supported.")
@@ -1053,7 +1055,7 @@ def create_index(x, index_type="IVF_PQ", metric="l2", num_partitions=256, num_su
             if pq_pool is not None:
                 pq_pool.shutdown(wait=True)
     part, codes = _transform_rows(eng, itype, params.metric, x, cent, codebook=cb, timed=timed)
-    ix = timed("build_partitions", lambda: DeviceIndex.create(eng, params.metric, cent, cb, part, codes, None,
+    ix = timed("build_partitions", lambda: DeviceIndex.create(eng, params.metric, cent, cb, part, codes, _row_ids,
                                                               raw=x if keep_raw else None,
                                                               dtype="int8" if x.dtype == torch.int8 else None))
     # Index::prewarm (ivf/v2.rs:349-352): the search-side constants (matrix-core scan tables, the lossless u8 refine copy of an
@@ -1142,3 +1144,136 @@ def multivector_flat_knn(values, offsets, q, k=10, metric="cosine", engine=None,
     src = torch.repeat_interleave(od[:-1][keep] - sub_off[:-1], lens) + torch.arange(total, device=od.device)
     rid = keep if row_ids is None else to_device(row_ids, torch.int64)[keep]
     return eng.multivec_topk(vt[src].contiguous(), sub_off.cpu().numpy(), q, k, metric, row_ids=rid)
+
+
+class IvfPqMultivectorIndex:
+    """An IVF_PQ index over the FLATTENED vectors of a multivector column (Arrow List<FixedSizeList<T, d>>), the row's id repeated once
+    per vector (the reference's Flatten transformer, lance-index/src/vector/transform.rs:203-216), searched as the reference's second
+    multivector path does (Scanner::multivec_ann, scanner.rs:3471-3552): one ANN search per query vector with k * overfetch candidates,
+    the lists joined by row id and scored with XTR-style imputation (MultivectorScoringExec, knn.rs:1132-1329) on the device."""
+    _index_type = "IVF_PQ"
+
+    def __init__(self, dev_index, params, stats, values, offsets):
+        self._ix = dev_index
+        self.params = params
+        self.stats = stats
+        self._values = values          # the column, kept by reference (None: built with keep_raw=False) -- the re-rank reads it
+        self._offsets = offsets        # int64 [n_rows + 1] on the device
+        self.n_rows = int(offsets.numel()) - 1
+
+    @property
+    def centroids(self):
+        return self._ix.centroids.cpu().numpy()
+
+    @property
+    def codebook(self):
+        return self._ix.codebook.cpu().numpy()
+
+    def info(self):
+        return self._ix.info()
+
+    def _queries(self, q):
+        """one [nqv][d] array or a list of them -> (all vectors [sum nqv][d] on the device, q_offsets, the queries, batched?)"""
+        d = self._ix.centroids.shape[1]
+        batched = isinstance(q, (list, tuple))
+        qs = list(q) if batched else [q]
+        if not qs:
+            raise ValueError("q holds no query")
+        ts = []
+        for one in qs:
+            t = one if isinstance(one, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(one))
+            if t.dim() != 2 or int(t.shape[1]) != d:
+                raise ValueError(f"a multivector query must be [nqv][d] with d = {d}, the dimension of the column, got shape {tuple(t.shape)}")
+            if int(t.shape[0]) < 1:
+                raise ValueError("q holds no vector: a multivector query has at least one")
+            if int(t.shape[0]) > MULTIVEC_MAX_QUERY_VECTORS:
+                raise ValueError(f"q holds {int(t.shape[0])} vectors, above the limit of {MULTIVEC_MAX_QUERY_VECTORS} query vectors per query")
+            ts.append(to_device(t, self._ix.data_dtype))
+        off = np.zeros(len(ts) + 1, np.int64)
+        off[1:] = np.cumsum([int(t.shape[0]) for t in ts])
+        return torch.cat(ts, 0).contiguous(), off, ts, batched
+
+    def _rerank(self, q, cand, k):
+        """the exact multivector distance (the flat scan's kernel) of the candidate rows to the ORIGINAL query -> the best k"""
+        eng = self._ix.engine
+        cand = cand[cand >= 0]
+        if cand.numel() == 0:
+            dev = cand.device
+            return torch.full((k,), -1, dtype=torch.int64, device=dev), torch.full((k,), float("inf"), dtype=torch.float32, device=dev)
+        od = self._offsets
+        lens = od[cand + 1] - od[cand]
+        sub_off = torch.zeros(cand.numel() + 1, dtype=torch.int64, device=od.device)
+        sub_off[1:] = torch.cumsum(lens, 0)
+        total = int(sub_off[-1])
+        src = torch.repeat_interleave(od[cand] - sub_off[:-1], lens) + torch.arange(total, device=od.device)
+        return eng.multivec_topk(self._values[src].contiguous(), sub_off.cpu().numpy(), q, k, "cosine", row_ids=cand)
+
+    def nearest(self, q, k=10, nprobes=1, refine_factor=None, prefilter=None, overfetch=10, distance_range=None, minimum_nprobes=None,
+                maximum_nprobes=None):
+        """q: one multivector query [nqv][d], or a list of them (a batch).  -> (row ids uint64 [k] (2^64 - 1 = missing), distances
+        f32 [k]) as numpy, [B][k] for a batch, sorted by (distance, row id).
+        overfetch: candidates per query vector = k * overfetch (the reference's LANCE_XTR_OVERFETCH, default 10).
+        refine_factor: None -- the k best by the imputed score; n >= 1 -- the k * n best by that score are scored exactly
+        (multivector_flat_knn's distance, the original query) and the best k returned (scanner.rs:2884-2904).
+        prefilter: boolean array over the rows (True = the row may be returned), tested inside the scan kernels."""
+        for name, val in (("distance_range", distance_range), ("minimum_nprobes", minimum_nprobes), ("maximum_nprobes", maximum_nprobes)):
+            if val is not None:
+                raise NotImplementedError(f"multivector index: {name} is not supported")
+        k, overfetch = int(k), int(overfetch)
+        if k < 1 or overfetch < 1:
+            raise ValueError(f"k={k}, overfetch={overfetch}: both must be at least 1")
+        if refine_factor is not None and int(refine_factor) < 1:
+            raise ValueError("Refine factor cannot be zero")
+        rf = 1 if refine_factor is None else int(refine_factor)
+        check_multivector_ann_sizes(k * overfetch, k * rf)
+        if refine_factor is not None and self._values is None:
+            raise NotImplementedError("multivector index: refine_factor needs the column (re-ranking scores the candidate rows exactly): "
+                                      "build with create_multivector_index(..., keep_raw=True)")
+        if prefilter is not None:
+            shape = tuple(prefilter.shape)
+            if shape != (self.n_rows,) or str(prefilter.dtype).replace("torch.", "") != "bool":
+                raise ValueError(f"prefilter must be a boolean array over the {self.n_rows} rows, got {prefilter.dtype} {shape}")
+        qv, off, qs, batched = self._queries(q)
+        ids, dists = self._ix.multivec_search(qv, off, k, nprobes, overfetch=overfetch, k_out=k * rf, allow=prefilter)
+        if refine_factor is not None:
+            out = [self._rerank(qs[b], ids[b], k) for b in range(len(qs))]
+            ids, dists = torch.stack([o[0] for o in out]), torch.stack([o[1] for o in out])
+        ids, dists = ids.cpu().numpy().view(np.uint64), dists.cpu().numpy()
+        return (ids, dists) if batched else (ids[0], dists[0])
+
+    def close(self):
+        self._ix.close()
+
+
+def create_multivector_index(values, offsets, metric="cosine", num_partitions=256, num_sub_vectors=16, num_bits=8, max_iters=50,
+                             sample_rate=256, ivf_centroids=None, pq_codebook=None, seed=42, keep_raw=True, engine=None):
+    """Dataset.create_index on a multivector column (values [total vectors][d] float32 / float16, offsets [n_rows + 1];
+    arrow_io.multivector_from_arrow gives both): IVF_PQ over the flattened vectors through exactly the calls create_index makes, with
+    row_ids = the row index repeated once per vector.  Rows without vectors are allowed (they can never be found).  Only the cosine
+    metric, as in the reference (lance/src/index/vector.rs:328).  keep_raw: keep the column (by reference) for nearest(refine_factor=)."""
+    if not isinstance(metric, str):
+        raise ValueError(f"Metric {metric} not supported.")
+    if _normalize_metric_type(metric) != "cosine":
+        raise ValueError("multivector type supports only cosine distance")
+    name = _dtype_name(values)
+    if name not in ("float32", "float16"):
+        raise ValueError(f"unsupported multivector element type {name}: the column must be float32 or float16")
+    if len(values.shape) != 2 or int(values.shape[1]) < 1:
+        raise ValueError(f"values must be the flattened [total vectors][d] child array, got shape {tuple(values.shape)}")
+    if offsets is None:
+        raise ValueError("the multivector column holds null rows: not supported")
+    off = offsets.detach().cpu().numpy() if isinstance(offsets, torch.Tensor) else np.asarray(offsets)
+    if off.ndim != 1 or off.size < 1 or off.dtype.kind not in "iu":
+        raise ValueError("offsets must be a 1-D integer array of n_rows + 1 entries")
+    off = np.ascontiguousarray(off.astype(np.int64))
+    if off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != int(values.shape[0]):
+        raise ValueError(f"offsets must start at 0, never decrease and end at len(values) = {int(values.shape[0])}")
+    # the argument rules, the training and the transform are create_index's own; only the storage differs (repeated row ids, no raw matrix)
+    flat = create_index(values, "IVF_PQ", metric="cosine", num_partitions=num_partitions, num_sub_vectors=num_sub_vectors, num_bits=num_bits,
+                        max_iters=max_iters, sample_rate=sample_rate, ivf_centroids=ivf_centroids, pq_codebook=pq_codebook, seed=seed,
+                        keep_raw=False, engine=engine, _row_ids=np.repeat(np.arange(off.size - 1, dtype=np.int64), np.diff(off)))
+    vt = None
+    if keep_raw:
+        vt = values.to(flat._ix.centroids.device) if isinstance(values, torch.Tensor) else to_device(values)
+    out = IvfPqMultivectorIndex(flat._ix, flat.params, flat.stats, vt, to_device(off))
+    return out
