@@ -248,7 +248,7 @@ int msbound_launch(lance_hip_ctx *ctx, const lance_hip_index *ix, const float *q
 int qscan_items(lance_hip_ctx *ctx, const uint32_t *pair_starts, int nvp, int G, uint32_t *item_start, int4 *desc, uint32_t max_items);   // search_q.hip: work items of G grouped pairs
 // search.hip: the exact re-ranking shared by every index type with a refine_factor.  cand_rid [nq][keff]: a query's valid ids are a prefix
 // (empty slots ~0), launch_cand_count counts them; launch_refine scores them against the index's raw vectors in its metric with the ORIGINAL
-// query (widened to f32) -- refine_pair_kernel / refine_u8_kernel / refine_kernel by dtype, metric and d --, orders by (dist, rowid) and
+// query (widened to f32) -- refine_pair_kernel / refine_u8_kernel / refine_rows_u8_kernel / refine_kernel by dtype, metric and d --, orders by (dist, rowid) and
 // writes the first k; a row id >= n_raw sets FLAG_BADROW in flags [nq] (zeroed by the caller), which check_flags (synchronises) reports
 int launch_cand_count(lance_hip_ctx *ctx, const uint64_t *ids, uint32_t nq, uint32_t keff, uint32_t *cnt);
 int launch_refine(lance_hip_ctx *ctx, const lance_hip_index *ix, const float *q, uint32_t nq, int d, const uint64_t *cand_rid, const uint32_t *cand_cnt,

@@ -1002,6 +1002,187 @@ __global__ __launch_bounds__(256) void refine_u8_kernel(const float *__restrict_
   refine_emit_topk(key, rid, pos, P, c, k, qi, out_ids, out_dists);
 }
 
+// The u8 refine for up to 128 candidates: whole rows per load, ONE WAVE per query.
+// What bound the kernel above, by its counters (profiles/refine_rows_pmc.json, refine_rows_notes.txt; C2: 10,000 x 100 rows of 128 B):
+// not bytes -- both kernels ask L2 for the same 1.2 M lines, 7 % of them hits -- and not the 37 row-read instructions per query either,
+// but VALU issue: 2,469 VALU (and 1,914 SALU) wave-instructions per query, three times what the distances need, a SIMD 75 % VALU-busy.
+// About 1,000 of them were the rank of P slots against P.  This kernel runs 1,234 VALU per query (57 % VALU-busy; those instructions
+// alone are 20 us of its 35); what is left over them is the serial life of a wave, covered by four waves per SIMD.  Here:
+//  - rows: eight lanes x 16 bytes cover one 128-byte block of a row, so a wave-instruction reads 8 whole (blocks of) rows; all 16
+//    instructions of a query's 128 slots are issued before the first is consumed.  Rows shorter than a block (d = 16, 48, the last block of
+//    d = 144, 272) use the first d / 16 lanes of the group: a lane never reads outside its row.
+//  - the loaded blocks pass through a 64-row x 128 B wave-local LDS tile (ds_write_b128, 16-byte chunks xor-swizzled by (row >> 1) & 7 so
+//    that the reads below are conflict-free) and are read back in the layout of the kernel above: lane h of a pair takes the bytes
+//    [8h, 8h+8) of every 16-element chunk.  The arithmetic is that kernel's, literally: no extra VALU, the same bits.
+//  - a query belongs to one wave (4 queries per workgroup, none shared): no __syncthreads; LDS operations of a wave execute in order.
+//    LDS per wave: 8 KB tile + 1 KB row offsets + 4d bytes of query = 9.5 KB at d = 128: 16 queries in flight per CU (79 VGPRs would
+//    allow 24).  Rows longer than a block (d > 128) keep 32 accumulators live across the blocks: 137 VGPRs, 12 queries per CU.
+//  - the selection ranks only the slots at or under the got-th smallest key (found by a 32-step bit search on ballots), not P against
+//    P (at the code).  The same kernel with the rank over the live slots instead: 0.077 ms against the pair kernel's 0.068 and this
+//    one's 0.050 (scripts/variants/refine_rows_count_rank.patch).
+// Rows longer than 1,792 elements (the workgroup's 64 KB of LDS) and lists longer than 128 stay with the kernel above.
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+constexpr int RR_WAVES = 4;        // queries per workgroup
+constexpr int RR_SLOTS = 128;      // candidates per query
+static size_t refine_rows_lds_per_wave(int d) { return 64 * 128 + RR_SLOTS * 8 + (size_t)d * 4; }
+
+template <int METRIC, bool ONE>      // ONE: d <= 128, a row is one block -- no accumulator is live while the loads are issued
+__global__ __launch_bounds__(64 * RR_WAVES, ONE ? 4 : 3) void refine_rows_u8_kernel(const float *__restrict__ q, int d, const uint8_t *__restrict__ raw, uint64_t n_raw,
+                                                                       const uint64_t *__restrict__ cand_rid, const uint32_t *__restrict__ cand_cnt,
+                                                                       int keff, int k, int nq, int lds_per_wave, uint64_t *__restrict__ out_ids,
+                                                                       float *__restrict__ out_dists, uint32_t *__restrict__ flags,
+                                                                       float *__restrict__ cand_exact = nullptr) {
+  static_assert(METRIC == METRIC_L2 || METRIC == METRIC_DOT, "squared L2 / dot");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // in an SGPR: the count and every branch on it stay scalar
+  const int qi = blockIdx.x * RR_WAVES + wv;
+  if (qi >= nq) return;      // wave-uniform, and no workgroup barrier below
+  char *tile = smem + (size_t)wv * lds_per_wave;                      // [64][128 B], swizzled
+  uint64_t *roff = reinterpret_cast<uint64_t *>(tile + 64 * 128);    // [RR_SLOTS] byte offset of the slot's row
+  f4 *qs4 = reinterpret_cast<f4 *>(roff + RR_SLOTS);                  // [d / 4] the query
+  uint32_t *key = reinterpret_cast<uint32_t *>(tile);                 // [RR_SLOTS], over the tile once the rows are consumed
+  // the ids in flight with the count and the query; slots beyond the count are masked after the loads come back.  Lane l keeps the
+  // ids of the slots l and l + 64 to the end: the selection below works on them in registers.
+  uint64_t r_lo = ~0ull, r_hi = ~0ull;
+  if (lane < keff) r_lo = cand_rid[(int64_t)qi * keff + lane];
+  if (lane + 64 < keff) r_hi = cand_rid[(int64_t)qi * keff + lane + 64];
+  const int c = __builtin_amdgcn_readfirstlane(min((int)cand_cnt[qi], keff));
+  const f4 *qv4 = reinterpret_cast<const f4 *>(q + (int64_t)qi * d);
+  for (int e = lane; e < d / 4; e += 64) qs4[e] = qv4[e];
+  if (lane >= c) r_lo = ~0ull;
+  if (lane + 64 >= c) r_hi = ~0ull;
+  const bool ok_lo = r_lo < n_raw, ok_hi = r_hi < n_raw;      // a dead slot holds ~0: not ok
+  const uint64_t okm_lo = __ballot(ok_lo), okm_hi = __ballot(ok_hi);
+  roff[lane] = ok_lo ? r_lo * (uint64_t)d : 0;      // a dead or bad slot reads row 0; its key is 0xFFFFFFFF whatever it reads
+  roff[lane + 64] = ok_hi ? r_hi * (uint64_t)d : 0;
+  if ((lane < c && !ok_lo) || (lane + 64 < c && !ok_hi))
+    atomicOr(&flags[qi], FLAG_BADROW);      // stored row id beyond the raw vectors handed to set_raw: reported, not ranked
+  __builtin_amdgcn_wave_barrier();
+  const int g = lane >> 3, p = lane & 7;             // load side: row g of an instruction's 8, 16-byte piece p
+  const int w0 = g * 128 + ((p ^ (g >> 1)) << 4);    // tile byte of (row j * 8 + g, piece p) = j * 1024 + (w0 ^ ((j & 1) * 64))
+  const int slot = lane >> 1, h = lane & 1;          // consume side: 32 rows per pass, two lanes each
+  const int rd0 = slot * 128 + h * 8, s7 = (slot >> 1) & 7;
+  const int nchunk = d >> 4;
+  float acc[4][8];      // [pass of 32 slots][accumulator 8h + e]
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[t][e] = 0.0f;
+  for (int c0 = 0; c0 < (ONE ? 1 : nchunk); c0 += 8) {      // 128-byte blocks of the rows
+    const int nb = ONE ? nchunk : min(8, nchunk - c0);
+    u32x4 st[2][8];
+    if (p < nb) {
+      const uint8_t *src = raw + (size_t)(c0 + p) * 16;
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf)
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          if (hf * 64 + j * 8 < c) st[hf][j] = *reinterpret_cast<const u32x4 *>(src + roff[hf * 64 + j * 8 + g]);
+    }
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf)
+      if (hf * 64 < c) {
+        if (p < nb) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j)
+            if (hf * 64 + j * 8 < c) *reinterpret_cast<u32x4 *>(tile + j * 1024 + (w0 ^ ((j & 1) * 64))) = st[hf][j];
+        }
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int ps = 0; ps < 2; ++ps)
+          if (hf * 64 + ps * 32 < c) {
+            float(&a)[8] = acc[hf * 2 + ps];
+            const f4 *xp = qs4 + 2 * h;
+#pragma unroll
+            for (int cc = 0; cc < 8; ++cc)
+              if (cc < nb) {
+                const u32x2 yb = *reinterpret_cast<const u32x2 *>(tile + ps * 4096 + rd0 + ((cc ^ s7) << 4));
+                const f4 x0 = xp[(c0 + cc) * 4], x1 = xp[(c0 + cc) * 4 + 1];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                  const float y0 = (float)((yb.x >> (8 * e)) & 255u), y1 = (float)((yb.y >> (8 * e)) & 255u);
+                  if constexpr (METRIC == METRIC_DOT) {
+                    a[e] += x0[e] * y0;
+                    a[4 + e] += x1[e] * y1;
+                  } else {
+                    const float d0 = x0[e] - y0, d1 = x1[e] - y1;
+                    a[e] += d0 * d0;
+                    a[4 + e] += d1 * d1;
+                  }
+                }
+              }
+          }
+        __builtin_amdgcn_wave_barrier();      // the next half (or block) overwrites the tile
+      }
+  }
+  uint32_t kreg[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    kreg[t] = 0xFFFFFFFFu;
+    if (t * 32 < c) {
+      float oth[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e)      // the pair's other lane: DPP quad_perm [1, 0, 3, 2]
+        oth[e] = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(acc[t][e]), 0xB1, 0xF, 0xF, false));
+      float tot = 0.0f;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) tot = tot + acc[t][e];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) tot = tot + oth[e];
+      tot = 0.0f + tot;      // `s + tot` of dist_exact_rt with an empty scalar tail
+      if (((t < 2 ? okm_lo : okm_hi) >> ((t & 1) * 32 + slot)) & 1) kreg[t] = order_key(finish_metric<METRIC>(tot));
+    }
+  }
+  if (h == 0) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) key[t * 32 + slot] = kreg[t];
+  }
+  __builtin_amdgcn_wave_barrier();
+  const uint32_t k_lo = key[lane], k_hi = key[lane + 64];      // the keys beside their ids: slots lane and lane + 64
+  if (cand_exact) {
+    if (lane < keff) cand_exact[(int64_t)qi * keff + lane] = (lane < c && k_lo != 0xFFFFFFFFu) ? key_to_float(k_lo) : INFINITY;
+    if (lane + 64 < keff) cand_exact[(int64_t)qi * keff + lane + 64] = (lane + 64 < c && k_hi != 0xFFFFFFFFu) ? key_to_float(k_hi) : INFINITY;
+  }
+  // The selection of refine_emit_topk, (key, rid, slot) order, in registers.  First T = the got-th smallest key of the live slots, a
+  // bit per step from the top (two ballots and scalar counts).  Every slot that can rank below got has key <= T, and whatever precedes
+  // such a slot has key <= T too (a dead slot holds (0xFFFFFFFF, ~0) at a higher index than any live one: it precedes none), so the
+  // rank among the slots with key <= T is the rank among all P slots: about got slots ranked against about got, not P against P.
+  const int got = min(c, k);
+  const uint64_t live_lo = __ballot(lane < c), live_hi = __ballot(lane + 64 < c);
+  if (got > 0) {
+    uint64_t a_lo = live_lo, a_hi = live_hi;      // live slots whose key agrees with T in the bits decided so far
+    uint32_t T = 0;
+    int need = got;
+    for (int b = 31; b >= 0; --b) {
+      const uint64_t z_lo = __ballot(((k_lo >> b) & 1u) == 0) & a_lo, z_hi = __ballot(((k_hi >> b) & 1u) == 0) & a_hi;
+      const int z = __popcll(z_lo) + __popcll(z_hi);
+      if (need <= z) { a_lo = z_lo; a_hi = z_hi; }
+      else { need -= z; a_lo &= ~z_lo; a_hi &= ~z_hi; T |= 1u << b; }
+    }
+    const uint64_t s_lo = __ballot(k_lo <= T) & live_lo, s_hi = __ballot(k_hi <= T) & live_hi;
+    int rank_lo = 0, rank_hi = 0;
+    auto count = [&](uint32_t kj, uint64_t rj, int sj) {      // does slot sj precede this lane's two slots?
+      rank_lo += ((kj < k_lo) | ((kj == k_lo) & ((rj < r_lo) | ((rj == r_lo) & (sj < lane))))) ? 1 : 0;
+      rank_hi += ((kj < k_hi) | ((kj == k_hi) & ((rj < r_hi) | ((rj == r_hi) & (sj < lane + 64))))) ? 1 : 0;
+    };
+    for (uint64_t m = s_lo; m; m &= m - 1) {
+      const int j = __builtin_ctzll(m);
+      count((uint32_t)__builtin_amdgcn_readlane((int)k_lo, j),
+            (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)r_lo, j) | ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(r_lo >> 32), j) << 32), j);
+    }
+    for (uint64_t m = s_hi; m; m &= m - 1) {
+      const int j = __builtin_ctzll(m);
+      count((uint32_t)__builtin_amdgcn_readlane((int)k_hi, j),
+            (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)r_hi, j) | ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(r_hi >> 32), j) << 32), j + 64);
+    }
+    if (((s_lo >> lane) & 1) && rank_lo < got) { out_ids[(int64_t)qi * k + rank_lo] = r_lo; out_dists[(int64_t)qi * k + rank_lo] = key_to_float(k_lo); }
+    if (((s_hi >> lane) & 1) && rank_hi < got) { out_ids[(int64_t)qi * k + rank_hi] = r_hi; out_dists[(int64_t)qi * k + rank_hi] = key_to_float(k_hi); }
+  }
+  for (int i = got + lane; i < k; i += 64) { out_ids[(int64_t)qi * k + i] = ~0ull; out_dists[(int64_t)qi * k + i] = INFINITY; }
+}
+
 // ---- the lossless u8 refine source (index.h: raw_u8) ---------------------------------------------------------------------------------
 // One pass over the f32 column: 16 elements per lane -> 16 bytes, and a flag if ANY element is not the widening of its byte (a fraction,
 // a value outside [0, 255], NaN).  The flag decides whether the copy is kept.  -0.0 is accepted as the byte 0 (numpy's rint / clip
@@ -1339,7 +1520,18 @@ int launch_refine(lance_hip_ctx *ctx, const lance_hip_index *ix, const float *q,
       const uint8_t *raw8 = pair ? raw_compact_prepare(ctx, ix) : nullptr;      // integer-valued column: its lossless u8 copy (index.h)
       if (raw8) {
         ScopedTimer t8(ctx, "refine_u8");      // the same launch under its own name: tests assert which source the refine read
-        if (ix->metric == LANCE_HIP_DOT)
+        // up to 128 candidates (the IVF_PQ refine): whole rows per load, a wave per query (LANCE_HIP_REFINE_U8_V1=1: the pair kernel, A/B).
+        // Longer lists (the IVF_SQ / IVF_RQ re-ranking, up to 768) keep the pair kernel: 128 slots are what a wave's tile and rank hold.
+        static const bool u8v1 = getenv("LANCE_HIP_REFINE_U8_V1") != nullptr;
+        const size_t lds_wave = refine_rows_lds_per_wave(d);
+        if (!u8v1 && keff <= RR_SLOTS && ix->n_raw > 0 && lds_wave * RR_WAVES <= 64 * 1024) {
+          const dim3 grid((unsigned)cdiv(nq, RR_WAVES));
+          ctx->count_stage("refine_rows");      // count:refine_rows -- which of the two u8 kernels answered
+          auto kern = ix->metric == LANCE_HIP_DOT ? (d <= 128 ? refine_rows_u8_kernel<METRIC_DOT, true> : refine_rows_u8_kernel<METRIC_DOT, false>)
+                                                  : (d <= 128 ? refine_rows_u8_kernel<METRIC_L2, true> : refine_rows_u8_kernel<METRIC_L2, false>);
+          hipLaunchKernelGGL(kern, grid, dim3(64 * RR_WAVES), lds_wave * RR_WAVES, ctx->stream, q, d, raw8, ix->n_raw, cand_rid, cand_cnt, (int)keff,
+                             (int)k, (int)nq, (int)lds_wave, ids, dists, flags, cand_exact);
+        } else if (ix->metric == LANCE_HIP_DOT)
           hipLaunchKernelGGL((refine_u8_kernel<METRIC_DOT>), dim3(nq), dim3(256), lds_pair, ctx->stream, q, d, raw8, ix->n_raw, cand_rid,
                              cand_cnt, (int)keff, (int)k, P, ids, dists, flags, cand_exact);
         else
