@@ -191,14 +191,14 @@ __device__ __forceinline__ uint32_t find_partition(const uint32_t *__restrict__ 
 // transposed per-partition blocks <-> row-major.  dir 0: transposed -> row-major, 1: reverse
 __global__ __launch_bounds__(256) void retile_codes_kernel(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, int64_t n,
                                                            int m, const uint32_t *__restrict__ offs, int nlist, int dir) {
-  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (g >= n * m) return;
-  const uint32_t slot = (uint32_t)(g / m);
-  const int mm = (int)(g % m);
-  const uint32_t p = find_partition(offs, nlist, slot);
-  const uint32_t off = offs[p], np = offs[p + 1] - off;
-  const int64_t t = (int64_t)off * m + (int64_t)mm * np + (slot - off);
-  if (dir == 0) out[g] = in[t]; else out[t] = in[g];
+  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < n * m; g += (int64_t)gridDim.x * 256) {      // (grid.h)
+    const uint32_t slot = (uint32_t)(g / m);
+    const int mm = (int)(g % m);
+    const uint32_t p = find_partition(offs, nlist, slot);
+    const uint32_t off = offs[p], np = offs[p + 1] - off;
+    const int64_t t = (int64_t)off * m + (int64_t)mm * np + (slot - off);
+    if (dir == 0) out[g] = in[t]; else out[t] = in[g];
+  }
 }
 
 static int dev_dup(lance_hip_ctx *ctx, const void *src, size_t bytes, void **out) {
@@ -237,11 +237,11 @@ int launch_residual(lance_hip_ctx *ctx, const float *x, int64_t n, int d, const 
 
 // 4-bit packing, pq.rs:168-172: byte b = (code[2b+1] << 4) | code[2b]
 __global__ __launch_bounds__(256) void pack_nibbles_kernel(const uint8_t *__restrict__ in, int64_t n, int m, uint8_t *__restrict__ out) {
-  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (g >= n * (m / 2)) return;
-  const int64_t r = g / (m / 2);
-  const int b = (int)(g % (m / 2));
-  out[g] = (uint8_t)((in[r * m + 2 * b + 1] << 4) | in[r * m + 2 * b]);
+  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < n * (m / 2); g += (int64_t)gridDim.x * 256) {      // (grid.h)
+    const int64_t r = g / (m / 2);
+    const int b = (int)(g % (m / 2));
+    out[g] = (uint8_t)((in[r * m + 2 * b + 1] << 4) | in[r * m + 2 * b]);
+  }
 }
 
 int pq_encode_launch(lance_hip_ctx *ctx, int metric, const float *x, int64_t n, int d, const float *codebook, int m,
@@ -259,7 +259,7 @@ int pq_encode_launch(lance_hip_ctx *ctx, int metric, const float *x, int64_t n, 
   pa.lanes32 = lanes32;      // f16 sub-vectors of more than 16 elements under dot: dot_scalar::<f16, f32, 32> (dot.rs:91-102)
   LH_TRY(launch_assign(ctx, pa, d / m, metric, m));
   if (nbits == 4 && n > 0) {
-    hipLaunchKernelGGL(pack_nibbles_kernel, dim3((unsigned)cdiv((uint64_t)n * (m / 2), 256)), dim3(256), 0, ctx->stream, dst, n, m, codes);
+    hipLaunchKernelGGL(pack_nibbles_kernel, dim3(grid_stride_blocks((uint64_t)n * (m / 2))), dim3(256), 0, ctx->stream, dst, n, m, codes);
     LH_CHECK_HIP(hipGetLastError());
   }
   return LANCE_HIP_OK;
@@ -599,7 +599,7 @@ int lance_hip_index_from_storage(lance_hip_ctx *ctx, int dtype, int metric, uint
   if (r == LANCE_HIP_OK) r = dev_dup(ctx, transposed ? nullptr : codes, (size_t)n * mbytes, reinterpret_cast<void **>(&ix->codes));
   if (r == LANCE_HIP_OK) r = dev_dup(ctx, row_ids, (size_t)n * 8, reinterpret_cast<void **>(&ix->row_ids));
   if (r == LANCE_HIP_OK && transposed && n > 0) {
-    hipLaunchKernelGGL(retile_codes_kernel, dim3((unsigned)cdiv(n * mbytes, 256)), dim3(256), 0, ctx->stream, codes, ix->codes,
+    hipLaunchKernelGGL(retile_codes_kernel, dim3(grid_stride_blocks(n * mbytes)), dim3(256), 0, ctx->stream, codes, ix->codes,
                        (int64_t)n, (int)mbytes, ix->part_offsets, (int)nlist, 0);
     if (hipGetLastError() != hipSuccess) r = LANCE_HIP_ERUNTIME;
   }
@@ -645,7 +645,7 @@ int lance_hip_index_export(lance_hip_ctx *ctx, const lance_hip_index *idx, uint3
     const uint32_t mbytes = idx->code_bytes();
     uint8_t *tmp = ctx->scratch_t<uint8_t>("index.export", (size_t)idx->n * mbytes);
     if (!tmp) return LANCE_HIP_ENOMEM;
-    hipLaunchKernelGGL(retile_codes_kernel, dim3((unsigned)cdiv(idx->n * mbytes, 256)), dim3(256), 0, ctx->stream, idx->codes, tmp,
+    hipLaunchKernelGGL(retile_codes_kernel, dim3(grid_stride_blocks(idx->n * mbytes)), dim3(256), 0, ctx->stream, idx->codes, tmp,
                        (int64_t)idx->n, (int)mbytes, idx->part_offsets, (int)idx->nlist, 1);
     LH_CHECK_HIP(hipGetLastError());
     LH_CHECK_HIP(hipMemcpyAsync(codes_transposed_host, tmp, (size_t)idx->n * mbytes, hipMemcpyDeviceToHost, ctx->stream));

@@ -136,3 +136,4 @@ struct CtxLock {
 };
 inline uint64_t cdiv(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
 }  // namespace lh
+#include "grid.h"

@@ -142,7 +142,8 @@ __device__ __forceinline__ f4 load4(const int8_t *p) {
 // (f16 elements are widened one by one, l2.rs:128-159).
 // SWAP (L2): the difference is taken as b - a.  Its square is the same bit for bit; what differs is a NaN element of b, which the
 // GPU's subtract returns with the sign flipped when it is the subtrahend and unchanged when it is the minuend (the reference's CPU
-// hands a NaN operand on unchanged from either side).  multivec.hip, where the sign of a NaN decides a maximum, sets it.
+// hands a NaN operand on unchanged from either side).  Every caller whose b is a ROW of the column sets it: the sign decides whether the
+// row's NaN distance sorts last (the reference) or first (multivec.hip: a maximum; the flat and refine kernels: the (distance, row id) order).
 template <int METRIC, typename TB = float, int LANES = 16, bool SWAP = false>
 __device__ __forceinline__ float dist_exact_rt(const float *__restrict__ a, const TB *__restrict__ bp, int d) {
   struct BView { const TB *p; __device__ __forceinline__ float operator[](int i) const { return ld_elem(p, i); } };
@@ -179,6 +180,21 @@ __device__ __forceinline__ float dist_exact_rt(const float *__restrict__ a, cons
 #pragma unroll
   for (int i = 0; i < LANES; ++i) tot = tot + sums[i];
   return s + tot;
+}
+
+// 1 - x as the reference's CPU subtraction leaves it: a NaN operand is handed on with its sign, and f32::total_cmp then sorts the
+// positive NaN of a row with a NaN element LAST.  The GPU's subtract negates the operand on its way into the adder and returns the NaN
+// with the sign bit SET, which sorts FIRST (finish_metric does the same for dot).
+__device__ __forceinline__ float one_minus(float x) {
+  const float v = 1.0f - x;
+  return x != x ? x : v;
+}
+// The last step of a cosine distance, 1 - quot with quot = xy / (the norms).  A NaN dot product xy (a NaN element in the row) stays the
+// NaN it is, as above.  A NaN that the DIVISION makes (a zero row: 0 / 0; inf / inf) is left to the subtraction as before: its sign is
+// the dividing machine's on the reference's side too (tests/test_zz_gpu_flat_wide.py::test_degenerate_rows).
+__device__ __forceinline__ float cosine_finish(float xy, float quot) {
+  const float v = 1.0f - quot;
+  return xy != xy ? xy : v;
 }
 
 // ---- a3: flat cosine (cosine.rs:127-231, norm_l2.rs:106-129) ---------------------------
@@ -233,7 +249,7 @@ __device__ __forceinline__ float cosine_scalar32_rt(const float *__restrict__ x,
 #pragma unroll
   for (int i = 0; i < 32; ++i) { txy = txy + pxy[i]; tyy = tyy + pyy[i]; }
   const float xy = sxy + txy, y_sq = syy + tyy;
-  return 1.0f - xy / (x_norm * sqrtf(y_sq));
+  return cosine_finish(xy, xy / (x_norm * sqrtf(y_sq)));
 }
 
 __device__ __forceinline__ float reduce8_tree(const float (&a)[8]) {
@@ -257,7 +273,8 @@ __device__ __forceinline__ float cosine_exact_rt(const float *__restrict__ x, fl
 #pragma unroll
       for (int i = 0; i < 8; ++i) { t[i] = x[i] * y[i]; u[i] = y[i] * y[i]; }
     }
-    return 1.0f - reduce8_tree(t) / x_norm / sqrtf(reduce8_tree(u));
+    const float xy = reduce8_tree(t), v = 1.0f - xy / x_norm / sqrtf(reduce8_tree(u));
+    return xy != xy ? xy : v;      // cosine_finish, written out (as below): the CPU emulation of the kernels cuts this function out by name
   }
   const int unrolled = d / 16 * 16, aligned = d / 8 * 8;
   float xy16[16], yn16[16], xy8[8], yn8[8];
@@ -283,7 +300,8 @@ __device__ __forceinline__ float cosine_exact_rt(const float *__restrict__ x, fl
   const float nrest = norm_l2_rt<TB>(yp + aligned, d - aligned);
   const float y_norm = reduce8_tree(u16) + reduce8_tree(yn8) + nrest * nrest;
   const float xy = reduce8_tree(t16) + reduce8_tree(xy8) + dist_exact_rt<METRIC_DOT, TB>(x + aligned, yp + aligned, d - aligned);
-  return 1.0f - xy / x_norm / sqrtf(y_norm);
+  const float v = 1.0f - xy / x_norm / sqrtf(y_norm);
+  return xy != xy ? xy : v;
 }
 
 // cosine_exact_rt split for kernels that hold x in registers and visit every y with MANY x (multivec.hip): the y-only half
@@ -336,14 +354,15 @@ __device__ __forceinline__ float cosine_exact_fixed(const RegVec<D> &x, float x_
     float t[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) t[i] = D == 16 ? x.get(i) * y[i] + x.get(i + 8) * y[i + 8] : x.get(i) * y[i];
-    return 1.0f - reduce8_tree(t) / x_norm / y_sqrt;
+    const float xy = reduce8_tree(t);
+    return cosine_finish(xy, xy / x_norm / y_sqrt);
   } else {
     float xy16[16], xy8[8], t16[8];
     cosine_acc16<D, false>(&x, y, xy16);
 #pragma unroll
     for (int i = 0; i < 8; ++i) { xy8[i] = 0.0f; t16[i] = xy16[i] + xy16[i + 8]; }
     const float xy = reduce8_tree(t16) + reduce8_tree(xy8) + dist_exact_rt<METRIC_DOT, float>(y + D, y + D, 0);
-    return 1.0f - xy / x_norm / y_sqrt;
+    return cosine_finish(xy, xy / x_norm / y_sqrt);
   }
 }
 

@@ -127,7 +127,7 @@ __global__ __launch_bounds__(256) void flat_scan_generic_kernel(FlatArgs p, int 
       for (int r = 0; r < tr; ++r) {
         float v;
         if constexpr (METRIC == METRIC_COSINE) v = H32 ? cosine_scalar32_rt(qv, qnorm, &tile[r * p.d], p.d) : cosine_exact_rt(qv, qnorm, &tile[r * p.d], p.d);
-        else v = finish_metric<METRIC>(dist_exact_rt<METRIC, float, (H32 && METRIC == METRIC_DOT) ? 32 : 16>(qv, &tile[r * p.d], p.d));
+        else v = finish_metric<METRIC>(dist_exact_rt<METRIC, float, (H32 && METRIC == METRIC_DOT) ? 32 : 16, METRIC == METRIC_L2>(qv, &tile[r * p.d], p.d));      // (L2: row - q, exact.cuh SWAP)
         const uint32_t key = order_key(v);
         if (key < wkey || cnt < p.k || (key == wkey && trid[r] < wrid)) flat_insert(lk, lr, p.k, cnt, key, trid[r], wkey, wrid);
       }
@@ -316,24 +316,28 @@ __device__ __forceinline__ uint16_t cr_bf16_rne(float x) {
 __global__ __launch_bounds__(256) void cosine_rownorm_kernel(const float *__restrict__ x, int64_t n, int d, float *__restrict__ out,
                                                              uint16_t *__restrict__ xb) {
   const int lane = threadIdx.x & 63, i = lane & 15;
-  const int64_t row = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 4;
-  float a = 0.0f;
-  if (row < n) {
-    const float *src = x + row * d;
-    if (xb) {
-      uint16_t *dst = xb + row * d;
-      for (int c = 0; c < d; c += 16) { const float v = src[c + i]; a = __fmaf_rn(v, v, a); dst[c + i] = cr_bf16_rne(v); }
-    } else {
-      for (int c = 0; c < d; c += 16) { const float v = src[c + i]; a = __fmaf_rn(v, v, a); }
+  // grid-stride over groups of four rows (grid.h: n * 16 threads reach 2^32 at 2^28 rows); the first row of a wave's group is the same
+  // on all its lanes, so every lane of a wave takes the same number of turns and the shuffles below always see the whole wave
+  for (int64_t r0 = ((int64_t)blockIdx.x * 256 + (threadIdx.x & ~63)) >> 4; r0 < n; r0 += (int64_t)gridDim.x * 16) {
+    const int64_t row = r0 + (lane >> 4);
+    float a = 0.0f;
+    if (row < n) {
+      const float *src = x + row * d;
+      if (xb) {
+        uint16_t *dst = xb + row * d;
+        for (int c = 0; c < d; c += 16) { const float v = src[c + i]; a = __fmaf_rn(v, v, a); dst[c + i] = cr_bf16_rne(v); }
+      } else {
+        for (int c = 0; c < d; c += 16) { const float v = src[c + i]; a = __fmaf_rn(v, v, a); }
+      }
     }
+    const float t = a + __shfl(a, lane + 8);        // i < 8: t_i = a_i + a_{i+8}
+    const float s = t + __shfl(t, lane + 4);        // i < 4: s_i = t_i + t_{i+4}
+    const float u = s + __shfl(s, lane + 2);        // i < 2: u0 = s0 + s2, u1 = s1 + s3
+    float y = u + __shfl(u, lane + 1);              // i = 0: (s0+s2) + (s1+s3)
+    y = y + 0.0f;                                   // + reduce_sum(yn8 = 0)
+    y = y + 0.0f;                                   // + norm_l2(empty tail)^2
+    if (row < n && i == 0) out[row] = sqrtf(y);
   }
-  const float t = a + __shfl(a, lane + 8);        // i < 8: t_i = a_i + a_{i+8}
-  const float s = t + __shfl(t, lane + 4);        // i < 4: s_i = t_i + t_{i+4}
-  const float u = s + __shfl(s, lane + 2);        // i < 2: u0 = s0 + s2, u1 = s1 + s3
-  float y = u + __shfl(u, lane + 1);              // i = 0: (s0+s2) + (s1+s3)
-  y = y + 0.0f;                                   // + reduce_sum(yn8 = 0)
-  y = y + 0.0f;                                   // + norm_l2(empty tail)^2
-  if (row < n && i == 0) out[row] = sqrtf(y);
 }
 
 __global__ __launch_bounds__(64) void query_norm_kernel(const float *__restrict__ q, int nq, int d, float *__restrict__ out) {
@@ -413,7 +417,7 @@ static int flat_topk_v2(lance_hip_ctx *ctx, int metric, const float *x, const vo
     if (wide_mfma && !xb) wide_mfma = false;
     plane_guard.armed = wide_mfma && big_plane;
     if (!sy || !qn) return LANCE_HIP_ENOMEM;
-    if (n > 0) hipLaunchKernelGGL(cosine_rownorm_kernel, dim3((unsigned)cdiv((uint64_t)n * 16, 256)), dim3(256), 0, ctx->stream, x, n, d, sy, xb);
+    if (n > 0) hipLaunchKernelGGL(cosine_rownorm_kernel, dim3(grid_stride_blocks((uint64_t)n * 16)), dim3(256), 0, ctx->stream, x, n, d, sy, xb);
     hipLaunchKernelGGL(query_norm_kernel, dim3(cdiv(nq, 64)), dim3(64), 0, ctx->stream, q, nq, d, qn);
     a.row_sy = sy;
     wxb = xb; wxn2 = sy;      // (the cosine filter reads row_sy, not |x|^2)
@@ -566,7 +570,7 @@ __device__ __forceinline__ uint32_t kth_smallest_256(uint32_t v, int kk, uint32_
 template <int METRIC, bool H32 = false>
 __device__ __forceinline__ float ivfflat_dist_rt(const float *__restrict__ q, float qnorm, const float *__restrict__ row, int d) {
   if constexpr (METRIC == METRIC_COSINE) return H32 ? cosine_scalar32_rt(q, qnorm, row, d) : cosine_exact_rt(q, qnorm, row, d);
-  else return finish_metric<METRIC>(dist_exact_rt<METRIC, float, (H32 && METRIC == METRIC_DOT) ? 32 : 16>(q, row, d));
+  else return finish_metric<METRIC>(dist_exact_rt<METRIC, float, (H32 && METRIC == METRIC_DOT) ? 32 : 16, METRIC == METRIC_L2>(q, row, d));      // (L2: row - q, exact.cuh SWAP)
 }
 
 template <int D, int METRIC, bool H32 = false>   // D = 0: run-time dimension (H32 only there)
@@ -767,12 +771,12 @@ __global__ __launch_bounds__(64) void ivfflat_exact_kernel(IvfFlatArgs a, uint64
 __global__ __launch_bounds__(256) void gather_vectors_kernel(const float *__restrict__ x, const uint64_t *__restrict__ row_ids,
                                                              const uint32_t *__restrict__ perm, int64_t n_out, int d,
                                                              float *__restrict__ out, uint64_t *__restrict__ rid_out) {
-  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (g >= n_out * d) return;
-  const int64_t s = g / d;
-  const uint32_t r = perm[s];
-  out[g] = x[(int64_t)r * d + (g - s * d)];
-  if (g == s * d) rid_out[s] = row_ids ? row_ids[r] : (uint64_t)r;
+  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < n_out * d; g += (int64_t)gridDim.x * 256) {      // (grid.h: n_out * d reaches 2^32)
+    const int64_t s = g / d;
+    const uint32_t r = perm[s];
+    out[g] = x[(int64_t)r * d + (g - s * d)];
+    if (g == s * d) rid_out[s] = row_ids ? row_ids[r] : (uint64_t)r;
+  }
 }
 
 
@@ -935,7 +939,7 @@ extern "C" int lance_hip_ivfflat_create(lance_hip_ctx *ctx, int dtype, int metri
   r = as_f32(ctx, dtype, x, (size_t)n * d, "f16.x", &xf);
   if (r != LANCE_HIP_OK) return fail(r);
   if (ix->n > 0) {
-    hipLaunchKernelGGL(gather_vectors_kernel, dim3((unsigned)cdiv((uint64_t)ix->n * d, 256)), dim3(256), 0, ctx->stream, xf, row_ids, perm,
+    hipLaunchKernelGGL(gather_vectors_kernel, dim3(grid_stride_blocks((uint64_t)ix->n * d)), dim3(256), 0, ctx->stream, xf, row_ids, perm,
                        (int64_t)ix->n, (int)d, ix->vectors, ix->row_ids);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
       set_error("ivfflat_create: gather kernel failed");

@@ -278,8 +278,10 @@ __global__ __launch_bounds__(256) void flat_mfma_eval_kernel(FmArgs a, int d) {
   for (int i = threadIdx.x; i < c; i += 256) {
     const int64_t row = p.r0 + (int64_t)a.squeue[(int64_t)qi * FM_SQ_CAP + i];
     const uint64_t rid = p.row_ids ? p.row_ids[row] : (uint64_t)row;
-    // (q - x)^2 == (x - q)^2 and q*x == x*q bit for bit: the query is the f32 operand, the row is widened per element
-    const float v = finish_metric<METRIC>(dist_exact_rt<METRIC, TX>(qv, static_cast<const TX *>(p.x_native) + row * d, d));
+    // (q - x)^2 == (x - q)^2 and q*x == x*q bit for bit: the query is the f32 operand, the row is widened per element.  L2 takes the
+    // difference as x - q (SWAP): as the subtrahend a NaN element of the ROW comes back with its sign flipped, the row's distance is
+    // the negative NaN and sorts FIRST -- every NaN row of the column entered the pool (exact.cuh: dist_exact_rt)
+    const float v = finish_metric<METRIC>(dist_exact_rt<METRIC, TX, 16, METRIC == METRIC_L2>(qv, static_cast<const TX *>(p.x_native) + row * d, d));
     const uint32_t key = order_key(v);
     if (key < tk || (key == tk && rid <= tr)) {
       const uint32_t pos = atomicAdd(&p.cnt[qi], 1u);

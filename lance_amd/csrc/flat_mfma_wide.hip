@@ -316,7 +316,7 @@ __global__ __launch_bounds__(256) void flat_wide_eval_kernel(FwArgs a) {
     const uint64_t rid = p.row_ids ? p.row_ids[row] : (uint64_t)row;
     float v;
     if constexpr (METRIC == METRIC_COSINE) v = cosine_exact_rt<float>(qv, qnorm, p.x + row * d, d);
-    else v = finish_metric<METRIC>(dist_exact_rt<METRIC, float>(qv, p.x + row * d, d));
+    else v = finish_metric<METRIC>(dist_exact_rt<METRIC, float, 16, METRIC == METRIC_L2>(qv, p.x + row * d, d));      // (L2: x - q, flat_mfma.hip)
     const uint32_t key = order_key(v);
     if (key < tk || (key == tk && rid <= tr)) {
       const uint32_t pos = atomicAdd(&p.cnt[qi], 1u);
@@ -335,6 +335,7 @@ bool flat_mfma_wide_supported(int metric, int d, int nq, int64_t n, const float 
   if (off || !x || (metric != LANCE_HIP_L2 && metric != LANCE_HIP_DOT && metric != LANCE_HIP_COSINE)) return false;
   if (d % 16 != 0 || d < 32 || d > 4096 || nq < 128) return false;
   if ((uint64_t)n * (uint64_t)d * 2 > (16ull << 30)) return false;
+  if (!grid_fits(cdiv((uint64_t)n, 4), 256)) return false;      // fw_rows_prep_kernel: a wave per row, 2^26 rows are 2^32 threads (grid.h)
   return ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(q)) & 15) == 0;
 }
 

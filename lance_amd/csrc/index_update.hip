@@ -105,7 +105,7 @@ __global__ __launch_bounds__(256) void iu_remap_keys_kernel(const uint64_t *__re
 }
 // ---- host side
 
-static unsigned iu_grid(uint64_t items) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(cdiv(items, 256), 65536)); }
+static unsigned iu_grid(uint64_t items) { return grid_stride_blocks(items, 256, 65536); }
 
 // widest piece (16 / 8 / 4 / 1 bytes) that both strides, the row length and both base addresses allow
 static int iu_width(const void *src, const void *dst, int64_t src_stride, int64_t dst_stride, int row_bytes) {

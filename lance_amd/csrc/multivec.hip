@@ -59,13 +59,6 @@ struct MvArgs {
   uint32_t *flag;            // bit 0: a zero-length row, bit 1: decreasing offsets
 };
 
-// 1 - x as the reference's CPU subtraction leaves it: a NaN operand is handed on with its sign (the GPU's subtract negates the
-// operand on its way into the adder and would return it with the sign flipped; see finish_metric in exact.cuh)
-__device__ __forceinline__ float one_minus(float x) {
-  const float v = 1.0f - x;
-  return x != x ? x : v;
-}
-
 __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
@@ -217,7 +210,7 @@ __global__ __launch_bounds__(64 * MV_WAVES, 2) void mv_scan_fixed_kernel(MvArgs 
           else if constexpr (V == MV_DOT) v = finish_metric<METRIC_DOT>(dist_exact<D, METRIC_DOT>(a, y));
           else if constexpr (V == MV_DOT_H) v = finish_metric<METRIC_DOT>(dist_exact<D, METRIC_DOT, false, 32>(a, y));
           else if constexpr (V == MV_COS) v = cosine_exact_fixed<D>(a, qn, y, ysq[j]);
-          else v = 1.0f - dist_exact<D, METRIC_DOT, false, 32>(a, y) / (qn * ysq[j]);
+          else { const float xy = dist_exact<D, METRIC_DOT, false, 32>(a, y); v = cosine_finish(xy, xy / (qn * ysq[j])); }
           bk = max(bk, order_key(one_minus(v)));
         }
       }

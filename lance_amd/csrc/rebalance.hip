@@ -321,7 +321,7 @@ __global__ __launch_bounds__(256) void rb_pad_kernel(const uint8_t *__restrict__
   }
 }
 
-static unsigned rb_grid(uint64_t items) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(cdiv(items, 256), 65536)); }
+static unsigned rb_grid(uint64_t items) { return grid_stride_blocks(items, 256, 65536); }
 static uint32_t rb_order_key(float f) {
   uint32_t b;
   memcpy(&b, &f, 4);

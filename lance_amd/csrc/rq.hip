@@ -468,13 +468,13 @@ __global__ __launch_bounds__(256) void rq_gather_kernel(const uint8_t *__restric
                                                         const uint64_t *__restrict__ row_ids, const uint32_t *__restrict__ perm, int64_t n_out, int cb,
                                                         uint8_t *__restrict__ out, float *__restrict__ add_out, float *__restrict__ scale_out,
                                                         uint64_t *__restrict__ rid_out) {
-  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (g >= n_out * cb) return;
-  const int64_t s = g / cb;
-  const int c = (int)(g - s * cb);
-  const uint32_t r = perm[s];
-  out[g] = codes[(int64_t)r * cb + c];
-  if (c == 0) { add_out[s] = add[r]; scale_out[s] = scale[r]; rid_out[s] = row_ids ? row_ids[r] : (uint64_t)r; }
+  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < n_out * cb; g += (int64_t)gridDim.x * 256) {      // (grid.h)
+    const int64_t s = g / cb;
+    const int c = (int)(g - s * cb);
+    const uint32_t r = perm[s];
+    out[g] = codes[(int64_t)r * cb + c];
+    if (c == 0) { add_out[s] = add[r]; scale_out[s] = scale[r]; rid_out[s] = row_ids ? row_ids[r] : (uint64_t)r; }
+  }
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
@@ -670,7 +670,7 @@ extern "C" int lance_hip_ivfrq_create(lance_hip_ctx *ctx, int metric, uint32_t d
   float *scale_out = add_out + ix->n;
   ix->rq_add = add_out; ix->rq_scale = scale_out;
   if (ix->n > 0) {
-    hipLaunchKernelGGL(rq_gather_kernel, dim3((unsigned)cdiv((uint64_t)ix->n * cb, 256)), dim3(256), 0, ctx->stream, codes, add, scale, row_ids, perm,
+    hipLaunchKernelGGL(rq_gather_kernel, dim3(grid_stride_blocks((uint64_t)ix->n * cb)), dim3(256), 0, ctx->stream, codes, add, scale, row_ids, perm,
                        (int64_t)ix->n, (int)cb, ix->codes, add_out, scale_out, ix->row_ids);
   }
   if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {

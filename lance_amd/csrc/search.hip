@@ -790,7 +790,7 @@ __global__ __launch_bounds__(256) void refine_kernel(const float *__restrict__ q
         const float xyr = ((t[0] + t[2]) + (t[1] + t[3])) + 0.0f + 0.0f;
         const float ynr = ((u[0] + u[2]) + (u[1] + u[3])) + 0.0f + 0.0f;
         if (sub == 0 && i < P) {
-          key[i] = ok ? order_key(1.0f - xyr / qnorm / sqrtf(ynr)) : 0xFFFFFFFFu;
+          key[i] = ok ? order_key(cosine_finish(xyr, xyr / qnorm / sqrtf(ynr))) : 0xFFFFFFFFu;
           rid[i] = r; pos[i] = 0;
         }
       }
@@ -827,7 +827,7 @@ __global__ __launch_bounds__(256) void refine_kernel(const float *__restrict__ q
       if (i < c) {
         r = cand_rid[(int64_t)qi * keff + i];
         if (r >= n_raw) atomicOr(&flags[qi], FLAG_BADROW);
-        if (r < n_raw) kk = order_key(finish_metric<METRIC>(dist_exact_rt<METRIC, TR, (H32 && METRIC == METRIC_DOT) ? 32 : 16>(qv, raw + r * d, d)));
+        if (r < n_raw) kk = order_key(finish_metric<METRIC>(dist_exact_rt<METRIC, TR, (H32 && METRIC == METRIC_DOT) ? 32 : 16, METRIC == METRIC_L2>(qv, raw + r * d, d)));      // (L2: row - q, exact.cuh SWAP)
       }
       key[i] = kk; rid[i] = r; pos[i] = 0;
     }
@@ -1269,7 +1269,7 @@ const uint8_t *raw_compact_prepare(lance_hip_ctx *ctx, const lance_hip_index *ix
   bool ran = lh::memset_async(bad, 0, 4, ctx->stream) == hipSuccess;
   if (ran) {
     const int64_t n16 = (int64_t)(bytes / 16);
-    hipLaunchKernelGGL(raw_to_u8_kernel, dim3((unsigned)std::min<uint64_t>(cdiv((uint64_t)n16, 256), 1u << 20)), dim3(256), 0, ctx->stream,
+    hipLaunchKernelGGL(raw_to_u8_kernel, dim3(grid_stride_blocks((uint64_t)n16)), dim3(256), 0, ctx->stream,
                        static_cast<const f4 *>(ix->raw), n16, reinterpret_cast<uint4 *>(buf), bad);
     ran = hipGetLastError() == hipSuccess && hipMemcpyAsync(&bad_h, bad, 4, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
           hipStreamSynchronize(ctx->stream) == hipSuccess;

@@ -404,13 +404,13 @@ __global__ __launch_bounds__(64) void sq_exact_kernel(SqArgs a, uint64_t *__rest
 __global__ __launch_bounds__(256) void sq_gather_kernel(const uint8_t *__restrict__ codes, const uint64_t *__restrict__ row_ids,
                                                         const uint32_t *__restrict__ perm, int64_t n_out, int d, int ld,
                                                         uint8_t *__restrict__ out, uint64_t *__restrict__ rid_out) {
-  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (g >= n_out * ld) return;
-  const int64_t s = g / ld;
-  const int c = (int)(g - s * ld);
-  const uint32_t r = perm[s];
-  out[g] = c < d ? codes[(int64_t)r * d + c] : (uint8_t)0;
-  if (c == 0) rid_out[s] = row_ids ? row_ids[r] : (uint64_t)r;
+  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < n_out * ld; g += (int64_t)gridDim.x * 256) {      // (grid.h: n_out * ld reaches 2^32)
+    const int64_t s = g / ld;
+    const int c = (int)(g - s * ld);
+    const uint32_t r = perm[s];
+    out[g] = c < d ? codes[(int64_t)r * d + c] : (uint8_t)0;
+    if (c == 0) rid_out[s] = row_ids ? row_ids[r] : (uint64_t)r;
+  }
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
@@ -433,7 +433,7 @@ static float sq_r2(double lo, double hi) {
   return r * r;
 }
 
-static unsigned sq_grid(uint64_t count) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(cdiv(count, 256), 2048)); }
+static unsigned sq_grid(uint64_t count) { return grid_stride_blocks(count, 256, 2048); }
 
 // rows of `dtype` elements -> codes out[row * ldo + col]
 static int sq_encode_launch(lance_hip_ctx *ctx, int dtype, const void *x, uint64_t n, uint32_t d, double lo, double hi, int64_t ldo, uint8_t *out) {
@@ -665,7 +665,7 @@ extern "C" int lance_hip_ivfsq_create(lance_hip_ctx *ctx, int dtype, int metric,
   uint32_t *xx = reinterpret_cast<uint32_t *>(ix->codes + code_bytes);
   ix->sq_xx = xx;
   if (ix->n > 0) {
-    hipLaunchKernelGGL(sq_gather_kernel, dim3((unsigned)cdiv((uint64_t)ix->n * ld, 256)), dim3(256), 0, ctx->stream, codes, row_ids, perm,
+    hipLaunchKernelGGL(sq_gather_kernel, dim3(grid_stride_blocks((uint64_t)ix->n * ld)), dim3(256), 0, ctx->stream, codes, row_ids, perm,
                        (int64_t)ix->n, (int)d, (int)ld, ix->codes, ix->row_ids);
     hipLaunchKernelGGL(sq_norms_kernel, dim3((unsigned)cdiv(ix->n, 256)), dim3(256), 0, ctx->stream, ix->codes, (int64_t)ix->n, (int)ld, xx);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {

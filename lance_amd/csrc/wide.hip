@@ -270,7 +270,7 @@ __global__ __launch_bounds__(W_BS) void pairwise_wide_kernel(PairwiseArgs p, int
         const int r = idx >> 6, c = idx & 63;
         if (row0 + r < p.n && c < ct_n) {
           float v;
-          if constexpr (METRIC == METRIC_COSINE) v = 1.0f - res[r][c] / qn[c] / tsy[r];
+          if constexpr (METRIC == METRIC_COSINE) v = cosine_finish(res[r][c], res[r][c] / qn[c] / tsy[r]);
           else v = finish_metric<METRIC>(res[r][c]);
           const uint32_t key = order_key(v);
           const uint64_t rid = trid[r];

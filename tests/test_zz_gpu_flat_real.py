@@ -258,3 +258,23 @@ def test_routes_three_and_four_queries_on_the_single_pass_kernel():
 def test_routes_one_and_two_queries_on_the_batch_path():
     """LANCE_HIP_NO_FLAT_SMALL=1: the batch path answers the one- and two-query calls on the same data"""
     _child({"LANCE_HIP_NO_FLAT_SMALL": "1"}, "single_pass_real and not routes")
+
+
+# ---- B4: rows with a NaN element behind the batch filters -------------------------------------------------------------------------------
+# The reference's distance of such a row is the POSITIVE NaN (its CPU hands a NaN operand on with its sign) and sorts last.  The GPU's
+# subtract returns a NaN subtrahend with the sign bit set: `q - x` in the exact evaluation behind the matrix-core filters, and the `1 - x`
+# that ends a cosine distance, made it the negative NaN, which sorts FIRST (lance_amd/csrc/exact.cuh: dist_exact_rt's SWAP, cosine_finish).
+# 5,000 NaN rows are more than a query's pool of 4,096: ranked first they overflow it, and the repair pass then finds nothing.
+@pytest.mark.parametrize("kind,metric,d,nq,stage", [("f32", "l2", 128, 256, "flat_mfma"), ("f16", "l2", 128, 256, "flat_mfma"),
+                                                    ("f32", "l2", 256, 256, "flat_mfma_wide"), ("f32", "cosine", 256, 256, "flat_mfma_wide"),
+                                                    ("f32", "cosine", 256, 4, None), ("f32", "cosine", 128, 4, None), ("f32", "dot", 128, 256, "flat_mfma")])
+def test_nan_rows_sort_last_behind_a_query_batch(eng, oracle, kind, metric, d, nq, stage):
+    n = 40_000
+    x, q = (S.real_f16 if kind == "f16" else S.real_f32)(n, d, nq, 4000 + d)
+    x[3::8] = np.nan                                    # 5,000 rows, in every epoch of the scan
+    assert np.isnan(x.astype(f32)).all(axis=1).sum() == 5000
+    oi, od = oracle.flat_knn(_oracle_rows(x), _oracle_rows(q), 10, metric)
+    assert not np.isnan(od).any()
+    before = eng.timing_query("count:" + stage)[1] if stage else 0
+    _same(eng, _dev(x), _dev(q), nq, 10, metric, oi, od, tag=(kind, metric, d, nq))
+    assert stage is None or eng.timing_query("count:" + stage)[1] > before, f"the {stage} filter did not serve the call"
