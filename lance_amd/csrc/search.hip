@@ -893,7 +893,9 @@ __global__ __launch_bounds__(256) void refine_pair_kernel(const float *__restric
                 acc[e] += x0[e] * y[cc][0][e];
                 acc[4 + e] += x1[e] * y[cc][1][e];
               } else {
-                const float d0 = x0[e] - y[cc][0][e], d1 = x1[e] - y[cc][1][e];
+                // row - q, as dist_exact_rt's SWAP (exact.cuh): the same square, but a NaN element of the row keeps its sign as the minuend
+                // and the row's NaN distance sorts last, as the reference's does; q - row returned it negative and the row came FIRST
+                const float d0 = y[cc][0][e] - x0[e], d1 = y[cc][1][e] - x1[e];
                 acc[e] += d0 * d0;
                 acc[4 + e] += d1 * d1;
               }

@@ -186,6 +186,21 @@ class OracleDeviceIndex:
         i, d = self.o.search(_np(q).astype(f32), k, nprobes, refine=refine_factor, raw=raw if refine_factor else None)
         return torch.from_numpy(i.view(np.int64)), torch.from_numpy(d)
 
+    def search_candidates(self, q, keff, nprobes, exact=True, engine=None):
+        """ids and PQ distances of search(k = keff) and, aligned with them, every candidate's exact distance (+inf for an empty slot)"""
+        qn = _np(q).astype(f32).reshape(-1, self.o.centroids.shape[1])
+        i, d = self.o.search(qn, keff, nprobes)
+        ex = None
+        if exact:
+            raw = self._raw.numpy()
+            raw = raw if raw.dtype == np.float16 else raw.astype(f32)      # f16 rows select f16's own dot / cosine
+            ex = np.full(i.shape, np.inf, f32)
+            for r in range(i.shape[0]):
+                ok = i[r] != np.iinfo(np.uint64).max
+                if ok.any():
+                    ex[r, ok] = oracle.distance_batch(self.metric, qn[r], raw[i[r][ok].astype(np.int64)])
+            ex = torch.from_numpy(ex)
+        return torch.from_numpy(i.view(np.int64)), torch.from_numpy(d), ex
 
     def search_filtered(self, q, k, nprobes, allow, refine_factor=0):
         raw = None if self._raw is None else self._raw.numpy().astype(f32)

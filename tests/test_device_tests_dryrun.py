@@ -167,3 +167,24 @@ def test_dryrun_flat_real_special_values(fake, oracle, metric):
 def test_dryrun_flat_real_batch_path(fake, oracle, metric, d):
     import test_zz_gpu_flat_real as R
     R.test_batch_path_real_f32(fake, oracle, metric, d, nqs=(3,), ks=(10, 129))
+
+
+# ---- the exact refine on real-valued columns (tests/test_zz_gpu_refine_real.py): every case body on a reduced grid, without the
+# ---- stage counters (the stand-ins enqueue nothing)
+@pytest.mark.parametrize("arm,d,full", [("f32-l2-pair", 16, True), ("f32-dot-pair", 144, False), ("f32-dot-one", 24, False),
+                                        ("f32-cosine-narrow", 40, False), ("f32-cosine-wide", 256, False), ("f16-l2", 16, False),
+                                        ("f16-dot", 40, False), ("f16-cosine", 72, True), ("int8-l2", 16, False), ("int8-cosine", 40, False)])
+def test_dryrun_refine_real(fake, oracle, arm, d, full):
+    import test_zz_gpu_refine_real as R
+    R.case(fake, arm, d, counters=False, full=full)
+
+
+@pytest.mark.parametrize("kind,metric,d", [("f32", "l2", 144), ("f32", "cosine", 100), ("f16", "cosine", 72)])
+def test_dryrun_refine_real_spoiled(fake, oracle, kind, metric, d):
+    import test_zz_gpu_refine_real as R
+    R.spoiled_case(fake, kind, metric, d, counters=False)
+
+
+def test_dryrun_refine_real_sort(fake, oracle):
+    import test_zz_gpu_refine_real as R
+    R.sort_case(fake, counters=False)
