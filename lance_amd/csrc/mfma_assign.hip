@@ -1191,12 +1191,12 @@ __global__ __launch_bounds__(256) void coarse_select_kernel(float *__restrict__ 
 }
 
 // ---- fewer than ~1000 lists: sweep and select in ONE kernel, the surrogates never leave LDS ---------------------------------------
-// A 512-lane workgroup owns CF_ROWS = 32 queries (10,000 queries: 313 workgroups, two per CU fit).  Phase 1 stages their rows ONCE: as f32 (the
-// operand of the exact re-check) and split into bf16 hi / lo planes, all in LDS.  Phase 2: wave w sweeps the 32-centroid blocks w, w + 8, ..: per
+// A 1024-lane workgroup owns CF_ROWS = 32 queries (10,000 queries: 313 workgroups, two per CU fit).  Phase 1 stages their rows ONCE: as f32 (the
+// operand of the exact re-check) and split into bf16 hi / lo planes, all in LDS.  Phase 2: wave w sweeps the 32-centroid blocks w, w + 16, ..: per
 // k-step the A fragments (centroids) come straight from the prepared planes (<= 512 KB: they sit in L2), the B fragments (queries) from LDS, and the
 // same three MFMAs per block as ma_top3_kernel run.  The surrogates go to the LDS array sur[32][nlist ^ 64 + 4] (row stride = 4 mod 32 words: the
 // 16-byte writes of eight consecutive rows cover the 32 banks once); padding centroids are written as +inf.  After one barrier wave w selects for
-// rows w, w + 8, ..:
+// rows w and w + 16:
 //   T0   = the nprobes-th smallest of the 256 values "four smallest of every lane", taken by nprobes rounds of wave-wide minimum extraction
 //          (the lane that holds the minimum -- the lowest one on a tie -- pops it): these are distinct elements of the row, so at least nprobes
 //          distinct centroids have s <= T0.  The same T0 as coarse_select_kernel's network over the same 256 values, at ~20 instructions a probe;
@@ -1211,13 +1211,17 @@ __global__ __launch_bounds__(256) void coarse_select_kernel(float *__restrict__ 
 // answered by the same wave from exact distances to ALL centroids (reference order), written over the row's LDS array; it counts itself in
 // n_exact_rows.  Rows beyond nq are staged as zeros and never selected or written.
 constexpr int CF_ROWS = 32;
-constexpr int CF_WAVES = 8;
+constexpr int CF_WAVES = 16;                 // two rows per wave in phase 3 (eight waves answering four rows one after the other: 32.7 us at C2, sixteen: 28.5;
+                                             // what is left is VALU issue on the CUs that hold two workgroups, profiles/front_end_notes.txt); <= 64 VGPRs:
+                                             // two workgroups = 8 waves per SIMD
 constexpr uint32_t CF_MAX_LISTS = 960;       // d = 128: 16.5 KB of f32 rows + 17 KB of bf16 planes (later the candidate lists) + 32 x 964 x 4 B = 120.5 KB of
                                              // surrogates = 154 KB of the CU's 160 KB; 1024 lists would need 162 KB
 
 static size_t coarse_fused_lds(int d, uint32_t nlist) {
   const size_t n64 = (size_t)cdiv(nlist, MA_CT) * MA_CT;
-  const size_t planes = (size_t)2 * CF_ROWS * (d + 8) * 2, cands = (size_t)CF_WAVES * CS_CAP * 12;
+  // candidates: ONE 8-byte slot each -- the centroid id goes into the word that stays when the key arrives (16 KB for sixteen waves: inside the
+  // planes' 17 KB at d = 128, so the 960-list shape keeps its 157,696 B)
+  const size_t planes = (size_t)2 * CF_ROWS * (d + 8) * 2, cands = (size_t)CF_WAVES * CS_CAP * 8;
   return (size_t)CF_ROWS * (d + 4) * 4 + std::max(planes, cands) + (size_t)CF_ROWS * (n64 + 4) * 4;
 }
 
@@ -1239,7 +1243,7 @@ __device__ __forceinline__ float cf_wave_reduce(float v) {      // the minimum /
 }
 
 template <int KS, int METRIC>
-__global__ __launch_bounds__(64 * CF_WAVES, 4) void coarse_fused_kernel(const float *__restrict__ q, int nq, const uint16_t *__restrict__ chi,
+__global__ __launch_bounds__(64 * CF_WAVES, 8) void coarse_fused_kernel(const float *__restrict__ q, int nq, const uint16_t *__restrict__ chi,
                                                                        const uint16_t *__restrict__ clo, const float *__restrict__ cn /* [nlist ^ 64] */,
                                                                        const uint32_t *__restrict__ maxbits, const float *__restrict__ cent, int nlist,
                                                                        int nprobes, uint32_t *__restrict__ part_ids, float *__restrict__ dists,
@@ -1248,15 +1252,14 @@ __global__ __launch_bounds__(64 * CF_WAVES, 4) void coarse_fused_kernel(const fl
   constexpr int D = KS * 16;
   constexpr int XS = D + 4;          // f32 row stride of the staged queries
   constexpr int CS = D + 8;          // bf16 row stride of a query plane (16-byte skew: conflict-free ds_read_b128)
-  constexpr size_t PLANES = (size_t)2 * CF_ROWS * CS * 2, CANDS = (size_t)CF_WAVES * CS_CAP * 12;
+  constexpr size_t PLANES = (size_t)2 * CF_ROWS * CS * 2, CANDS = (size_t)CF_WAVES * CS_CAP * 8;
   const int n64 = (nlist + MA_CT - 1) / MA_CT * MA_CT;
   const int SP = n64 + 4;            // f32 row stride of the surrogates
   float *xs = reinterpret_cast<float *>(smem);                                            // [CF_ROWS][XS]
   uint16_t *xh = reinterpret_cast<uint16_t *>(xs + CF_ROWS * XS), *xl = xh + CF_ROWS * CS;      // [CF_ROWS][CS] each (phases 1 and 2)
-  unsigned long long *ck_all = reinterpret_cast<unsigned long long *>(xh);                // [CF_WAVES][CS_CAP] (key << 32) | centroid  (phase 3, same bytes)
-  uint32_t *cl_all = reinterpret_cast<uint32_t *>(ck_all + CF_WAVES * CS_CAP);            // [CF_WAVES][CS_CAP] candidate centroids
+  uint2 *ck_all = reinterpret_cast<uint2 *>(xh);      // [CF_WAVES][CS_CAP] {centroid, key}: the compaction writes x, the distance round y  (phase 3, same bytes)
   float *sur = reinterpret_cast<float *>(smem + (size_t)CF_ROWS * XS * 4 + (PLANES > CANDS ? PLANES : CANDS));      // [CF_ROWS][SP]
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, grp = lane >> 4;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), grp = lane >> 4;      // (the wave's number in a scalar register: 64 VGPRs is the budget)
   const int j = lane & 31, g = lane >> 5;
   const int64_t row0 = (int64_t)blockIdx.x * CF_ROWS;
 
@@ -1322,9 +1325,8 @@ __global__ __launch_bounds__(64 * CF_WAVES, 4) void coarse_fused_kernel(const fl
   }
   __syncthreads();      // the surrogates are complete; the bf16 planes are dead: their bytes hold the candidate lists from here on
 
-  // phase 3: one row at a time per wave
-  unsigned long long *ck = ck_all + wave * CS_CAP;
-  uint32_t *cl = cl_all + wave * CS_CAP;
+  // phase 3: two rows per wave, one after the other (sixteen waves: sixteen rows' chains in flight per workgroup)
+  uint2 *ck = ck_all + wave * CS_CAP;
   const float cmax2 = __uint_as_float(maxbits[0]);
   for (int r = wave; r < CF_ROWS; r += CF_WAVES) {
     const int64_t qi = row0 + r;
@@ -1379,7 +1381,7 @@ __global__ __launch_bounds__(64 * CF_WAVES, 4) void coarse_fused_kernel(const fl
           const unsigned long long mask = __ballot(take);
           if (take) {
             const uint32_t pos = cnt + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-            if (pos < (uint32_t)CS_CAP) cl[pos] = (uint32_t)i;
+            if (pos < (uint32_t)CS_CAP) ck[pos].x = (uint32_t)i;
           }
           cnt += (uint32_t)__popcll(mask);
         }
@@ -1422,23 +1424,24 @@ __global__ __launch_bounds__(64 * CF_WAVES, 4) void coarse_fused_kernel(const fl
       uint32_t cc[4];
       float dv[4];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) { const uint32_t ci = c0 + 4 * u + (uint32_t)grp; cc[u] = ci < cnt ? cl[ci] : cl[0]; }
+      for (int u = 0; u < 4; ++u) { const uint32_t ci = c0 + 4 * u + (uint32_t)grp; cc[u] = ci < cnt ? ck[ci].x : ck[0].x; }
 #pragma unroll
       for (int u = 0; u < 4; ++u) dv[u] = cs_group_distance<METRIC>(wrow, cent + (int64_t)cc[u] * D, D, lane);
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const uint32_t ci = c0 + 4 * u + (uint32_t)grp;
-        if (ci < cnt && (lane & 15) == 0) ck[ci] = ((unsigned long long)order_key(dv[u]) << 32) | cc[u];
+        if (ci < cnt && (lane & 15) == 0) ck[ci].y = order_key(dv[u]);
       }
     }
     __builtin_amdgcn_wave_barrier();
     // rank = number of smaller keys (unique: the centroid is part of the key); lane holds candidates lane and lane + 64
-    const unsigned long long k0 = (uint32_t)lane < cnt ? ck[lane] : ~0ull, k1 = 64u + (uint32_t)lane < cnt ? ck[64 + lane] : ~0ull;
+    auto key64 = [&](uint32_t i) { const uint2 t = ck[i]; return ((unsigned long long)t.y << 32) | t.x; };      // (key << 32) | centroid
+    const unsigned long long k0 = (uint32_t)lane < cnt ? key64((uint32_t)lane) : ~0ull, k1 = 64u + (uint32_t)lane < cnt ? key64(64u + (uint32_t)lane) : ~0ull;
     uint32_t rank0 = 0, rank1 = 0;
     for (uint32_t i = 0; i < cnt; i += 4) {      // four LDS reads in flight (all lanes read the same address: a broadcast)
       unsigned long long o[4];
 #pragma unroll
-      for (uint32_t u = 0; u < 4; ++u) o[u] = i + u < cnt ? ck[i + u] : ~0ull;      // (~0 is below no key)
+      for (uint32_t u = 0; u < 4; ++u) o[u] = i + u < cnt ? key64(i + u) : ~0ull;      // (~0 is below no key)
 #pragma unroll
       for (uint32_t u = 0; u < 4; ++u) {
         rank0 += o[u] < k0 ? 1u : 0u;
@@ -1453,7 +1456,7 @@ __global__ __launch_bounds__(64 * CF_WAVES, 4) void coarse_fused_kernel(const fl
       part_ids[qi * nprobes + rank1] = (uint32_t)k1;
       if (dists) dists[qi * nprobes + rank1] = key_to_float((uint32_t)(k1 >> 32));
     }
-    __builtin_amdgcn_wave_barrier();          // the next row reuses cl / ck
+    __builtin_amdgcn_wave_barrier();          // the next row reuses ck
   }
 }
 

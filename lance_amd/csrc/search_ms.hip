@@ -137,6 +137,10 @@ struct MsPrepArgs {
   int m = 0;
 };
 
+__device__ __forceinline__ void ms_prep_finish(const MsPrepArgs &p, uint32_t pairl, uint32_t q, float T, uint32_t list, float n2l, float vml, float qmul,
+                                               bool badl, uint32_t slot);
+
+// The fall-back of ms_prep_rows_kernel below: any d, any alignment (one 4-byte element per lane and load).
 constexpr int MS_PPW = 4;      // pairs per wave of the pre-pass: their loads are in flight together (one pair per wave was 100k waves of
                                // load -> reduce -> store latency: 0.057 ms at C2 against 0.021 for the integer scan's residual pass)
 __global__ __launch_bounds__(256) void ms_prep_kernel(MsPrepArgs p) {
@@ -191,7 +195,13 @@ __global__ __launch_bounds__(256) void ms_prep_kernel(MsPrepArgs p) {
   for (int t = 1; t < MS_PPW; ++t) if (lane == t) { n2l = n2[t]; vml = vmax[t]; qmul = qmu[t]; badl = bad[t]; pairl = pair[t]; }
   if (lane >= MS_PPW || g0 + (uint32_t)lane >= ng) return;
   const uint32_t q = pairl / (uint32_t)p.nprobes;
-  const float T = key_to_float(p.tbound[q]);     // class A: 0 < T < inf (dot: any finite T)
+  ms_prep_finish(p, pairl, q, key_to_float(p.tbound[q]), p.dot ? p.probes[pairl] : 0u, n2l, vml, qmul, badl, g0 + (uint32_t)lane);
+}
+
+// One pair's record from its reduced sums, for both pre-pass kernels: T = the query's bound (class A: 0 < T < inf; dot: any finite T), list = the
+// pair's partition (read under dot only), slot = the pair's place in the grouped order.
+__device__ __forceinline__ void ms_prep_finish(const MsPrepArgs &p, uint32_t pairl, uint32_t q, float T, uint32_t list, float n2l, float vml, float qmul,
+                                               bool badl, uint32_t slot) {
   const float sqd = sqrtf((float)p.d) + 1.0f;
   const float sig2 = p.sigma * p.sigma;
   float s, eu, lim, zsum;
@@ -219,7 +229,7 @@ __global__ __launch_bounds__(256) void ms_prep_kernel(MsPrepArgs p) {
     const float Tp = (Tq + G) + slack(G);       // ... in the shifted domain (> 0: T bounds a real distance, every distance is >= base - E): per QUERY
     s = MS_SE / Tp;
     // the pair's own slack: the rows it meets are those of ONE list, whose longest centred reconstruction bounds |q . c'| for them
-    const float Gp = fminf(G, qn * p.cmaxp[p.probes[pairl]] * 1.000001f);
+    const float Gp = fminf(G, qn * p.cmaxp[list] * 1.000001f);
     const float E = slack(Gp);
     eu = E * s * 1.1f + 3.0f;
     lim = Tq + E;                               // a row is kept when -(q . c')~ <= T - 1 + q . mu + E
@@ -234,7 +244,8 @@ __global__ __launch_bounds__(256) void ms_prep_kernel(MsPrepArgs p) {
     eu = E * s * 1.1f + 3.0f;
     lim = (T * 1.0000077f + E) - n2l;  // T (1 + 2^-17) + E - |r|^2; the cancellation's rounding sits inside the 2^-13 term
     zsum = (T * 1.0000077f + E) * s;
-    // (tests/magnitude_spec.py: ms_pair_ok_l2 mirrors this branch, lines 230-238, to place its sweep where `ok` flips: change both together)
+    // (tests/magnitude_spec.py: ms_pair_ok_l2 mirrors this branch, the nine lines from `s = MS_SE / T` to `ok`, to place its sweep where `ok` flips:
+    // change both together)
     ok = !badl && T > 0.0f && T < INFINITY && s > 0.0f && s < INFINITY && n2l < INFINITY && vml * p.sigma < 60000.0f &&
          eu <= MS_SLACK_CAP && fabsf(lim * sig2) < INFINITY && n2l * s < 1e30f;
   }
@@ -253,7 +264,99 @@ __global__ __launch_bounds__(256) void ms_prep_kernel(MsPrepArgs p) {
     p.ovf[1u + atomicAdd(&p.ovf[0], 1u)] = pairl;
   }
   o.w = __uint_as_float(pairl);
-  p.prm[g0 + (uint32_t)lane] = o;
+  p.prm[slot] = o;
+}
+
+// ---- the same pre-pass, whole rows per load (d = 64 / 128; q, centroids, mu and rh on the 16-byte grid) --------------------------------------
+// LPP = d / 8 lanes own a pair, eight consecutive elements each: two 16-byte loads of the query, two of the centroid, ONE 16-byte store of eight
+// halves (the kernel above: sixteen 4-byte loads and eight 2-byte stores per lane for four pairs).  A wave carries MS_RP passes of 64 / LPP pairs;
+// the pair ids of every pass are loaded first, then probes / tbound / query rows together, then the centroid rows -- three dependent trips per
+// WAVE -- and nothing is consumed before every load is issued.  |r|^2, q . mu, max |v| and the non-finite flag are reduced inside the lane group
+// by DPP row operations (a group never leaves its 16-lane row); lane t of a group finishes the group's pair of pass t, so the finishing math
+// runs once per wave.  The sums add the same d products in another order than the kernel above: inside the 2^-13 (|r|^2 + T) term of the
+// header, like any order of d additions.  rh is element-wise: bit-identical.
+constexpr int MS_RP = 4;       // passes per wave: 16 pairs (d = 128) / 32 pairs (d = 64); 100k pairs at d = 128 = 6,250 waves
+template <int CTRL>
+__device__ __forceinline__ int ms_dpp(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, false); }      // (every lane active, every source in the row)
+template <int CTRL>
+__device__ __forceinline__ float ms_dpp(float v) { return __builtin_bit_cast(float, ms_dpp<CTRL>(__builtin_bit_cast(int, v))); }
+template <int LPP, int CTRL>
+__device__ __forceinline__ void ms_group_step(float &n2, float &qmu, float &vmax, int &bad) {
+  n2 += ms_dpp<CTRL>(n2); qmu += ms_dpp<CTRL>(qmu); vmax = fmaxf(vmax, ms_dpp<CTRL>(vmax)); bad |= ms_dpp<CTRL>(bad);
+}
+
+template <int LPP, bool DOT>
+__global__ __launch_bounds__(256) void ms_prep_rows_kernel(MsPrepArgs p) {
+  static_assert(LPP == 8 || LPP == 16, "a pair's lanes are a half or the whole of a 16-lane DPP row");
+  constexpr int PPP = 64 / LPP, D = LPP * 8, PPW = PPP * MS_RP;      // pairs per pass, row length, pairs per wave
+  const uint32_t g0 = (blockIdx.x * 4u + (threadIdx.x >> 6)) * (uint32_t)PPW;
+  const uint32_t ng = p.pair_starts[p.nlist];
+  const int lane = threadIdx.x & 63, sub = lane & (LPP - 1), grp = lane / LPP;
+  if (blockIdx.x == 0 && threadIdx.x == 0) p.prm[p.nan_slot] = f4{__uint_as_float(0x7FC00000u), 0.0f, 0.0f, 0.0f};   // the record padded LDS slots load
+  if (g0 >= ng) return;
+  uint32_t pair[MS_RP];
+#pragma unroll
+  for (int t = 0; t < MS_RP; ++t) pair[t] = p.pair_idx[min(g0 + (uint32_t)(t * PPP + grp), ng - 1u)];      // surplus slots redo the last pair (results discarded)
+  // second trip: the pairs' lists, the bound of the pair this lane finishes, the query rows
+  uint32_t pairl = pair[0];
+#pragma unroll
+  for (int t = 1; t < MS_RP; ++t) if (sub == t) pairl = pair[t];
+  const uint32_t ql = pairl / (uint32_t)p.nprobes;
+  const uint32_t tkey = p.tbound[ql];
+  uint32_t list[MS_RP];
+#pragma unroll
+  for (int t = 0; t < MS_RP; ++t) list[t] = DOT ? 0u : p.probes[pair[t]];
+  const uint32_t listl = DOT ? p.probes[pairl] : 0u;
+  f4 qa[MS_RP], qb[MS_RP], ca[MS_RP], cb[MS_RP];
+#pragma unroll
+  for (int t = 0; t < MS_RP; ++t) {
+    const float *qv = p.q + (int64_t)(pair[t] / (uint32_t)p.nprobes) * D + 8 * sub;
+    qa[t] = load4(qv); qb[t] = load4(qv + 4);
+  }
+  // third trip: the centroid rows (grouped pairs share their list: the same lines) / dot: the mean codewords
+  f4 ma = {0.0f, 0.0f, 0.0f, 0.0f}, mb = ma;
+  if (DOT) { ma = load4(p.mu + 8 * sub); mb = load4(p.mu + 8 * sub + 4); }
+#pragma unroll
+  for (int t = 0; t < MS_RP; ++t) {
+    if (DOT) { ca[t] = f4{0.0f, 0.0f, 0.0f, 0.0f}; cb[t] = ca[t]; continue; }
+    const float *cv = p.centroids + (int64_t)list[t] * D + 8 * sub;
+    ca[t] = load4(cv); cb[t] = load4(cv + 4);
+  }
+  const float hs = DOT ? 0.5f * p.sigma : p.sigma;      // dot: the codebook plane holds -2 sigma c, the operand is sigma q / 2 (powers of two: exact)
+  float n2[MS_RP], vmax[MS_RP], qmu[MS_RP];
+  int bad[MS_RP];
+#pragma unroll
+  for (int t = 0; t < MS_RP; ++t) {
+    n2[t] = 0.0f; vmax[t] = 0.0f; qmu[t] = 0.0f; bad[t] = 0;
+    ms_h8 h;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float qe = e < 4 ? qa[t][e & 3] : qb[t][e & 3], ce = e < 4 ? ca[t][e & 3] : cb[t][e & 3], mue = e < 4 ? ma[e & 3] : mb[e & 3];
+      float v = DOT ? qe : qe - ce;      // v2.rs:316-332, the subtraction of the exact path (dot: no residual)
+      if (p.round_f16 && !DOT) v = __half2float(__float2half_rn(v));
+      n2[t] += v * v;
+      if (DOT) qmu[t] += v * mue;
+      vmax[t] = fmaxf(vmax[t], fabsf(v));
+      bad[t] |= !(fabsf(v) < INFINITY) ? 1 : 0;
+      h[e] = (_Float16)(v * hs);
+    }
+    const uint32_t g = g0 + (uint32_t)(t * PPP + grp);
+    if (g < ng) *reinterpret_cast<ms_h8 *>(p.rh + (int64_t)g * D + 8 * sub) = h;
+  }
+#pragma unroll
+  for (int t = 0; t < MS_RP; ++t) {
+    ms_group_step<LPP, 0xB1>(n2[t], qmu[t], vmax[t], bad[t]);      // quad_perm [1, 0, 3, 2]
+    ms_group_step<LPP, 0x4E>(n2[t], qmu[t], vmax[t], bad[t]);      // quad_perm [2, 3, 0, 1]
+    ms_group_step<LPP, 0x141>(n2[t], qmu[t], vmax[t], bad[t]);     // row_half_mirror: every lane holds the sums of its eight
+    if (LPP == 16) ms_group_step<LPP, 0x140>(n2[t], qmu[t], vmax[t], bad[t]);      // row_mirror: ... of its sixteen
+  }
+  // lane t of a group finishes the group's pair of pass t
+  float n2l = n2[0], vml = vmax[0], qmul = qmu[0]; int badl = bad[0];
+#pragma unroll
+  for (int t = 1; t < MS_RP; ++t) if (sub == t) { n2l = n2[t]; vml = vmax[t]; qmul = qmu[t]; badl = bad[t]; }
+  const uint32_t slot = g0 + (uint32_t)(sub * PPP + grp);
+  if (sub >= MS_RP || slot >= ng) return;
+  ms_prep_finish(p, pairl, ql, key_to_float(tkey), listl, n2l, vml, qmul, badl != 0, slot);
 }
 
 // ---- slices: (partition, <= MS3_PB of its pairs, <= rows-per-slice of its rows) -----------------------------------------------------------
@@ -1057,7 +1160,20 @@ int mscan_launch(lance_hip_ctx *ctx, const lance_hip_index *ix, const float *qs,
     pa.sigma = ix->ms->sigma; pa.rh = rh; pa.prm = prm; pa.qslack = qslack; pa.seg_cnt = seg_cnt; pa.qovf = qovf; pa.ovf = ovf;
     pa.nan_slot = nan_slot; pa.prm2 = prm2;
     pa.dot = ix->metric == LANCE_HIP_DOT ? 1 : 0; pa.cmax = ix->ms->cmax; pa.cmax_full = ix->ms->cmax_full; pa.cmaxp = ix->ms->cmaxp; pa.mu = ix->cb_mean; pa.m = (int)ix->m;
-    hipLaunchKernelGGL(ms_prep_kernel, dim3((unsigned)cdiv(npairs, 4 * MS_PPW)), dim3(256), 0, ctx->stream, pa);
+    // whole rows per load where every pointer the 16-byte accesses touch is on the 16-byte grid (a caller's query buffer need not be);
+    // LANCE_HIP_NO_MS_PREP_ROWS=1 (read once): the element-wise kernel for every batch, for A/B runs
+    static const bool no_rows = getenv("LANCE_HIP_NO_MS_PREP_ROWS") != nullptr && getenv("LANCE_HIP_NO_MS_PREP_ROWS")[0] == '1';
+    const uintptr_t ptrs = reinterpret_cast<uintptr_t>(qs) | reinterpret_cast<uintptr_t>(rh) | (pa.dot ? reinterpret_cast<uintptr_t>(pa.mu) : reinterpret_cast<uintptr_t>(pa.centroids));
+    if (!no_rows && (d == 64 || d == 128) && (ptrs & 15) == 0) {
+      ctx->count_stage("ms_prep_rows");      // count:ms_prep_rows -- which of the two pre-pass kernels ran
+      const int ppw = (64 / (d / 8)) * MS_RP;
+      const dim3 grid((unsigned)cdiv(npairs, (size_t)4 * ppw));
+      if (d == 128 && pa.dot) hipLaunchKernelGGL((ms_prep_rows_kernel<16, true>), grid, dim3(256), 0, ctx->stream, pa);
+      else if (d == 128) hipLaunchKernelGGL((ms_prep_rows_kernel<16, false>), grid, dim3(256), 0, ctx->stream, pa);
+      else if (pa.dot) hipLaunchKernelGGL((ms_prep_rows_kernel<8, true>), grid, dim3(256), 0, ctx->stream, pa);
+      else hipLaunchKernelGGL((ms_prep_rows_kernel<8, false>), grid, dim3(256), 0, ctx->stream, pa);
+    } else
+      hipLaunchKernelGGL(ms_prep_kernel, dim3((unsigned)cdiv(npairs, 4 * MS_PPW)), dim3(256), 0, ctx->stream, pa);
     const uint32_t rs_rows = (uint32_t)ms_rows_per_slice(), rs2_rows = (uint32_t)ms_rows_per_slice2();
     static const bool no_order = getenv("LANCE_HIP_MS_NOORDER") != nullptr;      // A/B: one work class = slices in (roughly) index order
     const uint32_t cls_rows = no_order ? 0x40000000u : rs_rows;

@@ -1117,11 +1117,12 @@ size_t qscan_lds_bytes(int d, int m) {   // dynamic part (the quantised LUT is s
 
 int qscan_group(lance_hip_ctx *ctx, const uint32_t *probes, uint32_t nq, uint32_t nprobes, int nlist, const uint32_t *tglobal,
                 uint32_t *keys, uint32_t *tbound, uint32_t *pair_starts, uint32_t *pair_idx, uint32_t *item_start4, int4 *desc4,
-                uint32_t max_items4, int G, int dot) {
+                uint32_t max_items4, int G, int dot, bool items) {
   const size_t npairs = (size_t)nq * nprobes;
   hipLaunchKernelGGL(q_tclass_keys_kernel, dim3((unsigned)cdiv(npairs, 256)), dim3(256), 0, ctx->stream, probes, (int64_t)npairs, (int)nprobes,
                      nlist, tglobal, keys, tbound, dot);
   LH_TRY(stable_group(ctx, keys, (int64_t)npairs, (int64_t)npairs, 2 * nlist, 1, pair_starts, pair_idx, (int64_t)npairs, nullptr));
+  if (!items) return LANCE_HIP_OK;      // the matrix-core main pass works from pair_starts / pair_idx alone
   hipLaunchKernelGGL(q_item_table_kernel, dim3(1), dim3(256), 0, ctx->stream, pair_starts, nlist, G, item_start4);
   hipLaunchKernelGGL(q_item_desc_kernel, dim3((unsigned)cdiv(max_items4, 256)), dim3(256), 0, ctx->stream, item_start4, pair_starts, nlist, G,
                      max_items4, desc4);
