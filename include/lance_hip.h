@@ -498,6 +498,18 @@ int lance_hip_ivfflat_search(lance_hip_ctx *ctx, const lance_hip_index *idx, con
  * selected rows are scored by the same distance function, so no filtered copy of the index is needed.      */
 int lance_hip_ivfflat_search_filtered(lance_hip_ctx *ctx, const lance_hip_index *idx, const void *q, uint32_t nq, uint32_t k,
                                       uint32_t nprobes, const uint8_t *allow_by_rowid, uint64_t n_allow, uint64_t *ids, float *dists);
+/* IVF_FLAT distance-range query (Query::lower_bound / upper_bound; FlatIndex::search, flat/index.rs:91-149): inside every
+ * probed partition only rows with lower <= d < upper are offered to the partition's k-heap, d being the distance the index's
+ * metric produces -- exact on this index type, so "every row within radius r" is decided on true distances.  The comparison
+ * is OrderedFloat's total order (a NaN distance lies above every bound and is never in range; -0.0 sorts below +0.0, and no
+ * metric here produces -0.0); an open end is -FLT_MAX / FLT_MAX (the reference's unwrap_or(f32::MIN) / unwrap_or(f32::MAX)).
+ * lower > upper is refused, lower == upper returns nothing.  The range is tested inside the scan kernels (bound pass, main
+ * pass, exact replay); k as in lance_hip_ivfflat_search.
+ * allow_by_rowid may be NULL (n_allow ignored): range alone; otherwise FlatIndex::search's RowIdMask branch with bounds
+ * (flat/index.rs:131-149).                                                                                                 */
+int lance_hip_ivfflat_search_range(lance_hip_ctx *ctx, const lance_hip_index *idx, const void *q, uint32_t nq, uint32_t k,
+                                   uint32_t nprobes, const uint8_t *allow_by_rowid, uint64_t n_allow,
+                                   float lower, float upper, uint64_t *ids, float *dists);
 
 /* ---- N6: 1-bit RaBitQ and IVF_RQ (lance-index/src/vector/bq/{builder,transform,storage}.rs, ivf.rs:281-326) ------------ */
 /* f32 columns, metric LANCE_HIP_L2 or LANCE_HIP_DOT (Cosine is refused), num_bits = 1, d a multiple of 8 up to

@@ -97,6 +97,9 @@ extern "C" {
         ids: *mut u64, dists: *mut f32) -> i32;
     pub fn lance_hip_ivfflat_search_filtered(ctx: *mut LanceHipCtx, idx: *const LanceHipIndex, q: *const c_void, nq: u32, k: u32,
         nprobes: u32, allow_by_rowid: *const u8, n_allow: u64, ids: *mut u64, dists: *mut f32) -> i32;
+    // Query::lower_bound / upper_bound on IVF_FLAT (flat/index.rs:91-149); allow_by_rowid may be null: the range alone
+    pub fn lance_hip_ivfflat_search_range(ctx: *mut LanceHipCtx, idx: *const LanceHipIndex, q: *const c_void, nq: u32, k: u32,
+        nprobes: u32, allow_by_rowid: *const u8, n_allow: u64, lower: f32, upper: f32, ids: *mut u64, dists: *mut f32) -> i32;
     // 8-bit scalar quantisation (sq.rs:43-89, 263-287) and the IVF_SQ sub-index (FlatIndex over ScalarQuantizationStorage,
     // sq/storage.rs:398-468); bounds_host = Range<f64> as [start, end] in host memory
     pub fn lance_hip_sq_bounds(ctx: *mut LanceHipCtx, dtype: i32, x: *const c_void, count: u64, bounds_host: *mut f64) -> i32;

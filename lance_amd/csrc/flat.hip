@@ -528,7 +528,17 @@ struct IvfFlatArgs {
   uint32_t *flags;               // [nq] 1 = the survivors of a boundary tie depend on the reference heap: replay
   const uint32_t *allow = nullptr;   // prefilter: one bit per storage position (flat/index.rs:129-165), NULL = none
   FlatPool pool;
+  // distance range (Query::lower_bound / upper_bound, flat/index.rs:98-113): has_range picks the RANGE instantiation of the
+  // three scan kernels; the bounds are order keys, so lo_key <= key < hi_key is OrderedFloat's total order (NaN above all)
+  int has_range = 0;
+  uint32_t lo_key = 0, hi_key = 0xFFFFFFFFu;
+  uint32_t *n_replay = nullptr;      // queries the exact kernel answered (lance_hip_search_stats)
 };
+
+// A (row, query) cell outside the range is a row that is not there: tested wherever row_allowed() removes a row, but per query,
+// on the key.  The three scan kernels take RANGE as a template parameter and test `if constexpr (RANGE)`: the RANGE = false
+// instantiations are, token for token, the kernels from before ranges existed.
+__device__ __forceinline__ bool ivfflat_in_range(uint32_t key, uint32_t lo_key, uint32_t hi_key) { return key >= lo_key && key < hi_key; }
 
 // k-th smallest (rank kk) of one u32 per lane of a 256-lane workgroup
 __device__ __forceinline__ uint32_t kth_smallest_256(uint32_t v, int kk, uint32_t *sorted, uint32_t *slot) {
@@ -573,7 +583,7 @@ __device__ __forceinline__ float ivfflat_dist_rt(const float *__restrict__ q, fl
   else return finish_metric<METRIC>(dist_exact_rt<METRIC, float, (H32 && METRIC == METRIC_DOT) ? 32 : 16, METRIC == METRIC_L2>(q, row, d));      // (L2: row - q, exact.cuh SWAP)
 }
 
-template <int D, int METRIC, bool H32 = false>   // D = 0: run-time dimension (H32 only there)
+template <int D, int METRIC, bool H32 = false, bool RANGE = false>   // D = 0: run-time dimension (H32 only there)
 __global__ __launch_bounds__(256) void ivfflat_kernel(IvfFlatArgs a) {
   static_assert(!H32 || D == 0, "the f16 orders run on the run-time-dimension kernel");
   extern __shared__ __attribute__((aligned(16))) float qt[];   // [d padded to 4]
@@ -608,6 +618,9 @@ __global__ __launch_bounds__(256) void ivfflat_kernel(IvfFlatArgs a) {
         v = ivfflat_dist_rt<METRIC, H32>(qt, qnorm, a.vec + (int64_t)row * a.d, a.d);
       }
       const uint32_t key = order_key(v);
+      if constexpr (RANGE) {
+        if (!ivfflat_in_range(key, a.lo_key, a.hi_key)) continue;      // neither a lane minimum nor a pool entry
+      }
       if (a.bound) {
         mn = min(mn, key);
       } else {
@@ -681,7 +694,7 @@ __global__ __launch_bounds__(256) void ivfflat_select_kernel(IvfFlatArgs a, uint
 // Exact replay of a flagged query: every probed partition through a max-heap of k with std BinaryHeap semantics
 // (push while len < k, else replace the root only if root.dist > dist), rows in scan order; distances by all 64
 // lanes, a ballot drops rows that cannot enter, lane 0 replays the rest; partition heaps are merged by (dist, rowid).
-template <int METRIC, bool H32 = false>
+template <int METRIC, bool H32 = false, bool RANGE = false>
 __global__ __launch_bounds__(64) void ivfflat_exact_kernel(IvfFlatArgs a, uint64_t *__restrict__ out_ids, float *__restrict__ out_dists) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int qi = blockIdx.x;
@@ -695,7 +708,7 @@ __global__ __launch_bounds__(64) void ivfflat_exact_kernel(IvfFlatArgs a, uint64
   uint32_t *hp = hk + k + 1;
   uint32_t *skey = hp + k + 1;
   __shared__ int s_hlen, s_tcnt;
-  if (lane == 0) { s_hlen = 0; s_tcnt = 0; }
+  if (lane == 0) { s_hlen = 0; s_tcnt = 0; atomicAdd(a.n_replay, 1u); }
   for (int t = lane; t < a.d; t += 64) qv[t] = a.q[(int64_t)qi * a.d + t];
   __syncthreads();
   float qnorm = 0.0f;
@@ -714,6 +727,7 @@ __global__ __launch_bounds__(64) void ivfflat_exact_kernel(IvfFlatArgs a, uint64
       if (row < np && row_allowed(a.allow, off + (uint32_t)row)) {
         key = order_key(ivfflat_dist_rt<METRIC, H32>(qv, qnorm, a.vec + (int64_t)(off + row) * a.d, a.d));
         cand = s_hlen < k || key < hk[0];
+        if constexpr (RANGE) cand = cand && ivfflat_in_range(key, a.lo_key, a.hi_key);
       }
       const uint64_t mask = __ballot(cand);
       skey[lane] = key;
@@ -785,7 +799,7 @@ __global__ __launch_bounds__(256) void gather_vectors_kernel(const float *__rest
 // partition with the stable counting sort -- stream through LDS tiles with their thresholds.  Rows are read once
 // per block instead of once per (query, probe) pair: the query-major kernel moved 40 GB through L2 per 2000-query
 // batch at C2, this one moves the 512 MB of vectors once.
-template <int D, int METRIC, int QT, bool BOUND>
+template <int D, int METRIC, int QT, bool BOUND, bool RANGE = false>
 __global__ __launch_bounds__(256) void ivfflat_pm_kernel(IvfFlatArgs a) {
   __shared__ __attribute__((aligned(16))) float tile[QT * D];
   __shared__ uint32_t tk[QT];
@@ -828,10 +842,13 @@ __global__ __launch_bounds__(256) void ivfflat_pm_kernel(IvfFlatArgs a) {
       if constexpr (BOUND) {
         // lane l of every block of this partition folds its row into lanemin[q][l]: 256 minima over distinct rows,
         // whose k-th smallest (ivfflat_kth_kernel) is the query's bound
-        if (valid) atomicMin(&a.lanemin[(int64_t)tq[c] * 256 + threadIdx.x], key);
+        bool fold = valid;
+        if constexpr (RANGE) fold = fold && ivfflat_in_range(key, a.lo_key, a.hi_key);
+        if (fold) atomicMin(&a.lanemin[(int64_t)tq[c] * 256 + threadIdx.x], key);
         continue;
       }
-      const bool pass = valid && key <= tk[c];       // ties with the bound are kept (the boundary-tie check needs them)
+      bool pass = valid && key <= tk[c];       // ties with the bound are kept (the boundary-tie check needs them)
+      if constexpr (RANGE) pass = pass && ivfflat_in_range(key, a.lo_key, a.hi_key);
       const uint64_t m = __ballot(pass);
       if (m) {
         const int qi = tq[c];
@@ -852,17 +869,22 @@ __global__ __launch_bounds__(256) void ivfflat_pm_kernel(IvfFlatArgs a) {
   }
 }
 
-template <int METRIC, bool BOUND>
-static bool launch_ivfflat_pm(lance_hip_ctx *ctx, const IvfFlatArgs &a, unsigned n_items) {
+template <int METRIC, bool BOUND, bool RANGE>
+static bool launch_ivfflat_pm_r(lance_hip_ctx *ctx, const IvfFlatArgs &a, unsigned n_items) {
   switch (a.d) {
-    case 8: hipLaunchKernelGGL((ivfflat_pm_kernel<8, METRIC, 256, BOUND>), dim3(n_items), dim3(256), 0, ctx->stream, a); return true;
-    case 16: hipLaunchKernelGGL((ivfflat_pm_kernel<16, METRIC, 256, BOUND>), dim3(n_items), dim3(256), 0, ctx->stream, a); return true;
-    case 32: hipLaunchKernelGGL((ivfflat_pm_kernel<32, METRIC, 256, BOUND>), dim3(n_items), dim3(256), 0, ctx->stream, a); return true;
-    case 64: hipLaunchKernelGGL((ivfflat_pm_kernel<64, METRIC, 64, BOUND>), dim3(n_items), dim3(256), 0, ctx->stream, a); return true;
-    case 96: hipLaunchKernelGGL((ivfflat_pm_kernel<96, METRIC, 64, BOUND>), dim3(n_items), dim3(256), 0, ctx->stream, a); return true;
-    case 128: hipLaunchKernelGGL((ivfflat_pm_kernel<128, METRIC, 64, BOUND>), dim3(n_items), dim3(256), 0, ctx->stream, a); return true;
+    case 8: hipLaunchKernelGGL((ivfflat_pm_kernel<8, METRIC, 256, BOUND, RANGE>), dim3(n_items), dim3(256), 0, ctx->stream, a); return true;
+    case 16: hipLaunchKernelGGL((ivfflat_pm_kernel<16, METRIC, 256, BOUND, RANGE>), dim3(n_items), dim3(256), 0, ctx->stream, a); return true;
+    case 32: hipLaunchKernelGGL((ivfflat_pm_kernel<32, METRIC, 256, BOUND, RANGE>), dim3(n_items), dim3(256), 0, ctx->stream, a); return true;
+    case 64: hipLaunchKernelGGL((ivfflat_pm_kernel<64, METRIC, 64, BOUND, RANGE>), dim3(n_items), dim3(256), 0, ctx->stream, a); return true;
+    case 96: hipLaunchKernelGGL((ivfflat_pm_kernel<96, METRIC, 64, BOUND, RANGE>), dim3(n_items), dim3(256), 0, ctx->stream, a); return true;
+    case 128: hipLaunchKernelGGL((ivfflat_pm_kernel<128, METRIC, 64, BOUND, RANGE>), dim3(n_items), dim3(256), 0, ctx->stream, a); return true;
     default: return false;
   }
+}
+
+template <int METRIC, bool BOUND>
+static bool launch_ivfflat_pm(lance_hip_ctx *ctx, const IvfFlatArgs &a, unsigned n_items) {
+  return a.has_range ? launch_ivfflat_pm_r<METRIC, BOUND, true>(ctx, a, n_items) : launch_ivfflat_pm_r<METRIC, BOUND, false>(ctx, a, n_items);
 }
 
 __global__ __launch_bounds__(256) void ivfflat_first_probe_kernel(const uint32_t *__restrict__ probes, int nq, int nprobes, uint32_t *__restrict__ keys,
@@ -881,25 +903,48 @@ __global__ __launch_bounds__(256) void ivfflat_kth_kernel(const uint32_t *__rest
   if (threadIdx.x == 0) tkey[blockIdx.x] = t;
 }
 
-template <int METRIC>
-static void launch_ivfflat(lance_hip_ctx *ctx, const IvfFlatArgs &a, unsigned grid, bool fixed, bool h32 = false) {
+template <int METRIC, bool RANGE>
+static void launch_ivfflat_r(lance_hip_ctx *ctx, const IvfFlatArgs &a, unsigned grid, bool fixed, bool h32) {
   const size_t lds = (size_t)((a.d + 3) & ~3) * 4;
   if constexpr (METRIC != METRIC_L2) if (h32) {   // f16 column under dot / cosine: the 32-lane orders, run-time dimension
-    hipLaunchKernelGGL((ivfflat_kernel<0, METRIC, true>), dim3(grid), dim3(256), lds, ctx->stream, a);
+    hipLaunchKernelGGL((ivfflat_kernel<0, METRIC, true, RANGE>), dim3(grid), dim3(256), lds, ctx->stream, a);
     return;
   }
   if constexpr (METRIC != METRIC_COSINE) if (fixed) {   // cosine: run-time dimension kernel only (cosine_fast has its own lane layout)
     switch (a.d) {
-      case 8: hipLaunchKernelGGL((ivfflat_kernel<8, METRIC>), dim3(grid), dim3(256), lds, ctx->stream, a); return;
-      case 16: hipLaunchKernelGGL((ivfflat_kernel<16, METRIC>), dim3(grid), dim3(256), lds, ctx->stream, a); return;
-      case 32: hipLaunchKernelGGL((ivfflat_kernel<32, METRIC>), dim3(grid), dim3(256), lds, ctx->stream, a); return;
-      case 64: hipLaunchKernelGGL((ivfflat_kernel<64, METRIC>), dim3(grid), dim3(256), lds, ctx->stream, a); return;
-      case 96: hipLaunchKernelGGL((ivfflat_kernel<96, METRIC>), dim3(grid), dim3(256), lds, ctx->stream, a); return;
-      case 128: hipLaunchKernelGGL((ivfflat_kernel<128, METRIC>), dim3(grid), dim3(256), lds, ctx->stream, a); return;
+      case 8: hipLaunchKernelGGL((ivfflat_kernel<8, METRIC, false, RANGE>), dim3(grid), dim3(256), lds, ctx->stream, a); return;
+      case 16: hipLaunchKernelGGL((ivfflat_kernel<16, METRIC, false, RANGE>), dim3(grid), dim3(256), lds, ctx->stream, a); return;
+      case 32: hipLaunchKernelGGL((ivfflat_kernel<32, METRIC, false, RANGE>), dim3(grid), dim3(256), lds, ctx->stream, a); return;
+      case 64: hipLaunchKernelGGL((ivfflat_kernel<64, METRIC, false, RANGE>), dim3(grid), dim3(256), lds, ctx->stream, a); return;
+      case 96: hipLaunchKernelGGL((ivfflat_kernel<96, METRIC, false, RANGE>), dim3(grid), dim3(256), lds, ctx->stream, a); return;
+      case 128: hipLaunchKernelGGL((ivfflat_kernel<128, METRIC, false, RANGE>), dim3(grid), dim3(256), lds, ctx->stream, a); return;
       default: break;
     }
   }
-  hipLaunchKernelGGL((ivfflat_kernel<0, METRIC>), dim3(grid), dim3(256), lds, ctx->stream, a);
+  hipLaunchKernelGGL((ivfflat_kernel<0, METRIC, false, RANGE>), dim3(grid), dim3(256), lds, ctx->stream, a);
+}
+
+template <int METRIC>
+static void launch_ivfflat(lance_hip_ctx *ctx, const IvfFlatArgs &a, unsigned grid, bool fixed, bool h32 = false) {
+  if (a.has_range) launch_ivfflat_r<METRIC, true>(ctx, a, grid, fixed, h32);
+  else launch_ivfflat_r<METRIC, false>(ctx, a, grid, fixed, h32);
+}
+
+template <bool RANGE>
+static void launch_ivfflat_exact(lance_hip_ctx *ctx, const IvfFlatArgs &a, int metric, bool h32, int nqc, size_t lds, uint64_t *oid, float *od) {
+  const bool cosine = metric == LANCE_HIP_COSINE;
+  if (h32 && cosine) hipLaunchKernelGGL((ivfflat_exact_kernel<METRIC_COSINE, true, RANGE>), dim3(nqc), dim3(64), lds, ctx->stream, a, oid, od);
+  else if (h32) hipLaunchKernelGGL((ivfflat_exact_kernel<METRIC_DOT, true, RANGE>), dim3(nqc), dim3(64), lds, ctx->stream, a, oid, od);
+  else if (metric == LANCE_HIP_DOT) hipLaunchKernelGGL((ivfflat_exact_kernel<METRIC_DOT, false, RANGE>), dim3(nqc), dim3(64), lds, ctx->stream, a, oid, od);
+  else if (cosine) hipLaunchKernelGGL((ivfflat_exact_kernel<METRIC_COSINE, false, RANGE>), dim3(nqc), dim3(64), lds, ctx->stream, a, oid, od);
+  else hipLaunchKernelGGL((ivfflat_exact_kernel<METRIC_L2, false, RANGE>), dim3(nqc), dim3(64), lds, ctx->stream, a, oid, od);
+}
+
+// f32::total_cmp order key of a bound on the host: exact.cuh order_key, whose __float_as_uint is device code
+static uint32_t host_order_key(float f) {
+  uint32_t b;
+  memcpy(&b, &f, 4);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 
 }  // namespace lh
@@ -975,9 +1020,11 @@ __global__ __launch_bounds__(256) void ivfflat_flag_all_kernel(int nq, uint32_t 
 }
 
 static int ivfflat_search_impl(lance_hip_ctx *ctx, const lance_hip_index *idx, const void *q, uint32_t nq, uint32_t k, uint32_t nprobes,
-                               const uint32_t *allow, uint64_t *ids, float *dists) {
+                               const uint32_t *allow, bool has_range, float lower, float upper, uint64_t *ids, float *dists) {
   LH_REQUIRE(ctx && idx && (nq == 0 || (q && ids && dists)), "ivfflat_search: NULL argument");
   LH_REQUIRE(idx->m == 0 && idx->vectors, "ivfflat_search: not an IVF_FLAT index");
+  // lower == upper is legal and selects nothing (flat/index.rs:98-105: lower <= d && d < upper)
+  LH_REQUIRE(!has_range || !(lower > upper), "ivfflat_search_range: lower bound %g is above the upper bound %g", (double)lower, (double)upper);
   // FlatIndex::search takes any k (flat/index.rs:82-177).  The threshold machinery of the fast kernels selects among one value per
   // lane (k <= 128); beyond that every query goes through the heap-emulating exact kernel, whose heap lives in LDS (k <= 4096)
   LH_REQUIRE(k > 0 && k <= 4096, "ivfflat_search: k=%u not supported (1..4096)", k);
@@ -1009,12 +1056,17 @@ static int ivfflat_search_impl(lance_hip_ctx *ctx, const lance_hip_index *idx, c
   IvfFlatArgs a;
   a.vec = idx->vectors; a.row_ids = idx->row_ids; a.part_offsets = idx->part_offsets; a.nprobes = (int)nprobes; a.d = d;
   a.allow = allow;
+  a.has_range = has_range ? 1 : 0;
+  if (has_range) { a.lo_key = host_order_key(lower); a.hi_key = host_order_key(upper); }
   FlatPool &pl = a.pool;
   constexpr int IVFFLAT_CAP = FLAT_CAP / 2;       // 2048 pool entries per query: (key, rowid, partition) sorted in 32 KiB of LDS
   pl.x = nullptr; pl.row_ids = nullptr; pl.r0 = pl.r1 = 0; pl.k = (int)k; pl.cap = IVFFLAT_CAP;
   a.ppart = ctx->scratch_t<uint32_t>("ivfflat.ppart", (size_t)qch * IVFFLAT_CAP);
-  a.flags = ctx->scratch_t<uint32_t>("ivfflat.flags", (size_t)qch);
+  a.flags = ctx->scratch_t<uint32_t>("ivfflat.flags", (size_t)qch + 1);     // + the replay counter of lance_hip_search_stats
   if (!a.ppart || !a.flags) return LANCE_HIP_ENOMEM;
+  a.n_replay = a.flags + qch;
+  LH_CHECK_HIP(lh::memset_async(a.n_replay, 0, 4, ctx->stream));
+  ctx->last_replay_counter = a.n_replay;
   pl.tkey = ctx->scratch_t<uint32_t>("flat2.tkey", qch);
   pl.trid = ctx->scratch_t<uint64_t>("flat2.trid", qch);
   pl.cnt = ctx->scratch_t<uint32_t>("flat2.cnt", qch);
@@ -1029,11 +1081,8 @@ static int ivfflat_search_impl(lance_hip_ctx *ctx, const lance_hip_index *idx, c
   auto finish = [&](int nqc, uint64_t *oid, float *od, bool select = true) {
     if (select) hipLaunchKernelGGL(ivfflat_select_kernel, dim3(nqc), dim3(256), sel_lds, ctx->stream, a, oid, od);
     ScopedTimer t(ctx, "ivfflat_exact");
-    if (h32 && cosine) hipLaunchKernelGGL((ivfflat_exact_kernel<METRIC_COSINE, true>), dim3(nqc), dim3(64), ex_lds, ctx->stream, a, oid, od);
-    else if (h32) hipLaunchKernelGGL((ivfflat_exact_kernel<METRIC_DOT, true>), dim3(nqc), dim3(64), ex_lds, ctx->stream, a, oid, od);
-    else if (idx->metric == LANCE_HIP_DOT) hipLaunchKernelGGL((ivfflat_exact_kernel<METRIC_DOT>), dim3(nqc), dim3(64), ex_lds, ctx->stream, a, oid, od);
-    else if (cosine) hipLaunchKernelGGL((ivfflat_exact_kernel<METRIC_COSINE>), dim3(nqc), dim3(64), ex_lds, ctx->stream, a, oid, od);
-    else hipLaunchKernelGGL((ivfflat_exact_kernel<METRIC_L2>), dim3(nqc), dim3(64), ex_lds, ctx->stream, a, oid, od);
+    if (has_range) launch_ivfflat_exact<true>(ctx, a, idx->metric, h32, nqc, ex_lds, oid, od);
+    else launch_ivfflat_exact<false>(ctx, a, idx->metric, h32, nqc, ex_lds, oid, od);
   };
   const bool pm = fixed && idx->n_flat_items > 0 &&     // partition-major for the fixed dimensions, query-major kernel otherwise
                   ((reinterpret_cast<uintptr_t>(qf) & 15) == 0);
@@ -1124,7 +1173,7 @@ static int ivfflat_search_impl(lance_hip_ctx *ctx, const lance_hip_index *idx, c
 extern "C" int lance_hip_ivfflat_search(lance_hip_ctx *ctx, const lance_hip_index *idx, const void *q, uint32_t nq, uint32_t k,
                                         uint32_t nprobes, uint64_t *ids, float *dists) {
   lh::CtxLock _ctx_lock(ctx);
-  return ivfflat_search_impl(ctx, idx, q, nq, k, nprobes, nullptr, ids, dists);
+  return ivfflat_search_impl(ctx, idx, q, nq, k, nprobes, nullptr, false, 0.0f, 0.0f, ids, dists);
 }
 
 extern "C" int lance_hip_ivfflat_search_filtered(lance_hip_ctx *ctx, const lance_hip_index *idx, const void *q, uint32_t nq, uint32_t k,
@@ -1136,7 +1185,19 @@ extern "C" int lance_hip_ivfflat_search_filtered(lance_hip_ctx *ctx, const lance
   LH_CHECK_HIP(hipSetDevice(ctx->device));
   const uint32_t *bits = nullptr;
   LH_TRY(build_allow_bits(ctx, idx->row_ids, idx->n, allow_by_rowid, n_allow, &bits));
-  return ivfflat_search_impl(ctx, idx, q, nq, k, nprobes, bits, ids, dists);
+  return ivfflat_search_impl(ctx, idx, q, nq, k, nprobes, bits, false, 0.0f, 0.0f, ids, dists);
+}
+
+extern "C" int lance_hip_ivfflat_search_range(lance_hip_ctx *ctx, const lance_hip_index *idx, const void *q, uint32_t nq, uint32_t k,
+                                              uint32_t nprobes, const uint8_t *allow_by_rowid, uint64_t n_allow, float lower, float upper,
+                                              uint64_t *ids, float *dists) {
+  lh::CtxLock _ctx_lock(ctx);
+  LH_REQUIRE(ctx && idx, "ivfflat_search_range: NULL argument");
+  LH_REQUIRE(idx->m == 0 && idx->vectors, "ivfflat_search_range: not an IVF_FLAT index");
+  LH_CHECK_HIP(hipSetDevice(ctx->device));
+  const uint32_t *bits = nullptr;     // allow_by_rowid == NULL: the range alone
+  if (allow_by_rowid) LH_TRY(build_allow_bits(ctx, idx->row_ids, idx->n, allow_by_rowid, n_allow, &bits));
+  return ivfflat_search_impl(ctx, idx, q, nq, k, nprobes, bits, true, lower, upper, ids, dists);
 }
 
 extern "C" int lance_hip_flat_topk(lance_hip_ctx *ctx, int dtype, int metric, const void *x, const uint64_t *row_ids,

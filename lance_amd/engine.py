@@ -824,15 +824,26 @@ class DeviceFlatIndex:
         check(self.engine.lib.lance_hip_index_save(self.engine.h, self.h, os.fspath(index_dir).encode(),
                                                    0 if loss is None else 1, 0.0 if loss is None else float(loss)))
 
-    def search(self, q, k, nprobes, allow=None):
+    def search(self, q, k, nprobes, allow=None, lower=None, upper=None):
         """allow: boolean array indexed by row id (a prefilter) -- tested inside the scan kernels
-        (lance_hip_ivfflat_search_filtered), no filtered copy of the index"""
+        (lance_hip_ivfflat_search_filtered), no filtered copy of the index.
+        lower / upper: distance range -- only rows with lower <= d < upper enter the per-partition heaps (flat/index.rs:91-149),
+        alone or combined with `allow` (lance_hip_ivfflat_search_range whenever either bound is given)."""
         d = self.centroids.shape[1]
         t = q if isinstance(q, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(q))
         q = t.to(self.data_dtype).to(_dev()).contiguous().reshape(-1, d)
         nq = q.shape[0]
         ids = torch.empty((nq, k), dtype=torch.int64, device=q.device)
         dists = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+        if lower is not None or upper is not None:
+            # the bounds are f32 values in the reference (Query::lower_bound: Option<f32>): round before use
+            lo = float(np.finfo(np.float32).min) if lower is None else float(np.float32(lower))
+            hi = float(np.finfo(np.float32).max) if upper is None else float(np.float32(upper))
+            a = _allow_bytes(allow)
+            torch.cuda.synchronize()
+            check(self.engine.lib.lance_hip_ivfflat_search_range(self.engine.h, self.h, _ptr(q), nq, k, nprobes, _ptr(a),
+                                                                 0 if a is None else a.numel(), lo, hi, _ptr(ids), _ptr(dists)))
+            return ids, dists
         if allow is not None:
             a = allow if isinstance(allow, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(allow, dtype=bool))
             a = a.to(torch.uint8).to(_dev()).contiguous()

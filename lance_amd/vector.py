@@ -381,6 +381,50 @@ def merge_indices(indices, raw=None):
     return indices[0]._wrap(merged, None)
 
 
+def _adaptive_nearest(run, q, d, k, nlist, nprobes, minimum_nprobes, maximum_nprobes, prefilter=None, shortcut=False):
+    """Adaptive probing above any sub-index (Query::minimum_nprobes / maximum_nprobes; ANNIvfSubIndexExec initial_search +
+    late_search, knn.rs:714-860), as IvfPqIndex.nearest documents it: every query searches its `minimum_nprobes` nearest
+    partitions; while some query holds fewer than k rows and partitions are left, those queries alone are searched again with
+    min(max, max(2 * n, n + 1)) partitions.  `nprobes=n` alone means minimum = maximum = n.
+    run(queries, nprobes) -> (ids int64 [n, k] with -1 = missing, distances f32 [n, k]) on the device: what `nearest` would
+    return for that many partitions, so a re-ranking search is judged after re-ranking.
+    shortcut: late_search's early exit (knn.rs:741-779) applies -- the caller passes True for a prefilter without a refine
+    factor or a range.  When the prefilter selects at most k rows, a query that has not found all of them gets the rest back
+    at distance +inf in ascending row id order (SortExec's tie order) and no further partition is searched.
+    -> (ids int64, distances f32) as numpy."""
+    min_np = nprobes if minimum_nprobes is None else minimum_nprobes
+    max_np = (min_np if minimum_nprobes is None else nlist) if maximum_nprobes is None else maximum_nprobes
+    max_np = max(min(max_np, nlist), min(min_np, nlist))
+    min_np = min(min_np, max_np)
+    ids, dists = run(q, min_np)
+    if max_np <= min_np:
+        return ids.cpu().numpy(), dists.cpu().numpy()
+    if shortcut and prefilter is not None:
+        allow_np = np.ascontiguousarray(prefilter.cpu().numpy() if isinstance(prefilter, torch.Tensor) else prefilter, dtype=bool)
+        mask_ids = np.flatnonzero(allow_np).astype(np.int64)
+        if mask_ids.size <= k:
+            ids_h, dists_h = ids.cpu().numpy().copy(), dists.cpu().numpy().copy()
+            for qi in range(ids_h.shape[0]):
+                found = ids_h[qi][ids_h[qi] != -1]
+                if found.size < k and found.size < mask_ids.size:
+                    rest = np.setdiff1d(mask_ids, found)
+                    ids_h[qi, found.size:found.size + rest.size] = rest
+                    dists_h[qi, found.size:found.size + rest.size] = np.inf
+            return ids_h, dists_h
+    qt = q if isinstance(q, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(q))
+    qt = qt.reshape(-1, d)
+    npb = min_np
+    while npb < max_np:
+        starved = torch.nonzero((ids == -1).any(dim=1)).reshape(-1)     # fewer than k rows found so far
+        if starved.numel() == 0:
+            break
+        npb = min(max_np, max(npb * 2, npb + 1))
+        si, sd = run(qt[starved.cpu()] if not qt.is_cuda else qt[starved], npb)
+        ids[starved] = si
+        dists[starved] = sd
+    return ids.cpu().numpy(), dists.cpu().numpy()
+
+
 class IvfPqIndex(_Maintenance):
     """An IVF_PQ index resident in HBM with the reference's query semantics."""
     _index_type = "IVF_PQ"
@@ -584,10 +628,27 @@ class IvfFlatIndex(_Maintenance):
     def search_device(self, q, k, nprobes):
         return self._ix.search(q, k, nprobes)
 
-    def nearest(self, q, k=10, nprobes=1, prefilter=None):
-        """prefilter: boolean array over row ids; the mask is tested inside the scan kernels (no copy of the index)"""
-        ids, dists = self._ix.search(q, k, nprobes) if prefilter is None else self._ix.search(q, k, nprobes, allow=prefilter)
-        return ids.cpu().numpy().view(np.uint64), dists.cpu().numpy()
+    def nearest(self, q, k=10, nprobes=1, prefilter=None, distance_range=None, minimum_nprobes=None, maximum_nprobes=None):
+        """-> (row ids uint64 [nq,k] (2^64 - 1 = missing), distances f32 [nq,k]) as numpy.
+        prefilter: boolean array over row ids; the mask is tested inside the scan kernels (no copy of the index).
+        distance_range: (lower, upper), either may be None -- rows with lower <= d < upper only (Query::lower_bound /
+        upper_bound, flat/index.rs:91-149), decided inside every probed partition on this index's exact distances
+        (lance_hip_ivfflat_search_range); with a prefilter both are tested in the scan kernels.
+        minimum_nprobes / maximum_nprobes: adaptive probing, as IvfPqIndex.nearest (_adaptive_nearest)."""
+        if distance_range is not None:
+            lo, hi = distance_range
+            if lo is None and hi is None:       # (None, None): the range entry point with both ends open
+                lo = float(np.finfo(np.float32).min)
+
+            def run(qq, npb):
+                return self._ix.search(qq, k, npb, allow=prefilter, lower=lo, upper=hi)
+        else:
+            def run(qq, npb):
+                return self._ix.search(qq, k, npb) if prefilter is None else self._ix.search(qq, k, npb, allow=prefilter)
+        cent = self._ix.centroids
+        ids, dists = _adaptive_nearest(run, q, cent.shape[1], k, cent.shape[0], nprobes, minimum_nprobes, maximum_nprobes,
+                                       prefilter=prefilter, shortcut=distance_range is None)
+        return ids.view(np.uint64), dists
 
     def prefiltered(self, allow):
         """A compacted copy of the index restricted to the selected rows (kept for callers that reuse one filter for many
@@ -646,8 +707,11 @@ class IvfSqIndex(_Maintenance):
     def search_device(self, q, k, nprobes, refine_factor=0):
         return self._ix.search(q, k, nprobes, refine_factor=refine_factor)
 
-    def nearest(self, q, k=10, nprobes=1, prefilter=None, refine_factor=None, distance_range=None):
-        """prefilter: boolean array over row ids; the mask is tested inside the scan kernels (no copy of the index)"""
+    def nearest(self, q, k=10, nprobes=1, prefilter=None, refine_factor=None, distance_range=None, minimum_nprobes=None,
+                maximum_nprobes=None):
+        """prefilter: boolean array over row ids; the mask is tested inside the scan kernels (no copy of the index).
+        minimum_nprobes / maximum_nprobes: adaptive probing, as IvfPqIndex.nearest (_adaptive_nearest); with a refine_factor a
+        query counts as satisfied by what re-ranking leaves it, and the shortcut for prefilters of at most k rows does not apply."""
         if distance_range is not None:
             raise NotImplementedError("IVF_SQ: distance_range is not supported by this engine")
         if refine_factor is not None:
@@ -656,10 +720,16 @@ class IvfSqIndex(_Maintenance):
             if self._ix._raw is None:
                 raise NotImplementedError("IVF_SQ: refine_factor needs the raw vectors (re-ranking scores the candidates against the column): attach them "
                                       "with set_raw(x), or build with create_index(..., keep_raw=True)")
-            ids, dists = self._ix.search(q, k, nprobes, allow=prefilter, refine_factor=int(refine_factor))
+
+            def run(qq, npb):
+                return self._ix.search(qq, k, npb, allow=prefilter, refine_factor=int(refine_factor))
         else:
-            ids, dists = self._ix.search(q, k, nprobes) if prefilter is None else self._ix.search(q, k, nprobes, allow=prefilter)
-        return ids.cpu().numpy().view(np.uint64), dists.cpu().numpy()
+            def run(qq, npb):
+                return self._ix.search(qq, k, npb) if prefilter is None else self._ix.search(qq, k, npb, allow=prefilter)
+        cent = self._ix.centroids
+        ids, dists = _adaptive_nearest(run, q, cent.shape[1], k, cent.shape[0], nprobes, minimum_nprobes, maximum_nprobes,
+                                       prefilter=prefilter, shortcut=refine_factor is None)
+        return ids.view(np.uint64), dists
 
     def set_raw(self, raw):
         """attach the column (indexed by row id; the ORIGINAL rows) for nearest(..., refine_factor=)"""
@@ -709,9 +779,12 @@ class IvfRqIndex:
     def search_device(self, q, k, nprobes, refine_factor=0):
         return self._ix.search(q, k, nprobes, refine_factor=refine_factor)
 
-    def nearest(self, q, k=10, nprobes=1, prefilter=None, refine_factor=None, distance_range=None):
+    def nearest(self, q, k=10, nprobes=1, prefilter=None, refine_factor=None, distance_range=None, minimum_nprobes=None,
+                maximum_nprobes=None):
         """prefilter: boolean array over row ids; the mask is tested inside the scan kernels, and every selected row takes the f32
-        distance (the reference's prefiltered FlatIndex::search never uses the quantised table)"""
+        distance (the reference's prefiltered FlatIndex::search never uses the quantised table).
+        minimum_nprobes / maximum_nprobes: adaptive probing, as IvfPqIndex.nearest (_adaptive_nearest); with a refine_factor a
+        query counts as satisfied by what re-ranking leaves it, and the shortcut for prefilters of at most k rows does not apply."""
         if distance_range is not None:
             raise NotImplementedError("IVF_RQ: distance_range is not supported by this engine")
         if refine_factor is not None:
@@ -720,10 +793,16 @@ class IvfRqIndex:
             if self._ix._raw is None:
                 raise NotImplementedError("IVF_RQ: refine_factor needs the raw vectors (re-ranking scores the candidates against the column): attach them "
                                       "with set_raw(x), or build with create_index(..., keep_raw=True)")
-            ids, dists = self._ix.search(q, k, nprobes, allow=prefilter, refine_factor=int(refine_factor))
+
+            def run(qq, npb):
+                return self._ix.search(qq, k, npb, allow=prefilter, refine_factor=int(refine_factor))
         else:
-            ids, dists = self._ix.search(q, k, nprobes) if prefilter is None else self._ix.search(q, k, nprobes, allow=prefilter)
-        return ids.cpu().numpy().view(np.uint64), dists.cpu().numpy()
+            def run(qq, npb):
+                return self._ix.search(qq, k, npb) if prefilter is None else self._ix.search(qq, k, npb, allow=prefilter)
+        cent = self._ix.centroids
+        ids, dists = _adaptive_nearest(run, q, cent.shape[1], k, cent.shape[0], nprobes, minimum_nprobes, maximum_nprobes,
+                                       prefilter=prefilter, shortcut=refine_factor is None)
+        return ids.view(np.uint64), dists
 
     def set_raw(self, raw):
         """attach the column (indexed by row id; the ORIGINAL rows) for nearest(..., refine_factor=)"""
