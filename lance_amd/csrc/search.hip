@@ -227,12 +227,28 @@ struct ScanArgs {
 // one LUT entry at a run-time sub-dimension.  lanes32: an f16 column under dot -- the table entries are dot products of f16
 // sub-vectors, dot_scalar::<f16, f32, 32> (dot.rs:91-102,138-161): 32 lane accumulators, which differs from the 16-lane form once
 // a sub-vector has more than 16 elements
+// A NaN L2 entry whose cause is a NaN the operands HOLD.  The entry is built from r - cw: the reference's CPU hands a NaN operand on with
+// its sign from either side, the GPU's subtract returns a NaN subtrahend -- the codeword -- with the sign bit set (exact.cuh:
+// dist_exact_rt), and f32::total_cmp then sorts every row that meets the entry FIRST instead of last.  The entry takes the sign of the
+// first NaN element the operands hold; a NaN the arithmetic makes (inf - inf) keeps the device's.  Off the fast path: one compare per entry.
+__device__ __forceinline__ float lut_nan_sign(const float *__restrict__ r, const float *__restrict__ cw, int sd, float v) {
+  for (int i = 0; i < sd; ++i) {
+    const float a = r[i], b = cw[i];
+    if (a != a) return copysignf(v, a);
+    if (b != b) return copysignf(v, b);
+  }
+  return v;
+}
+
 template <int METRIC>
 __device__ __forceinline__ float lut_entry_rt(const float *__restrict__ r, const float *__restrict__ cw, int sd, int lanes32) {
   if constexpr (METRIC == METRIC_DOT) {
     if (lanes32) return finish_metric<METRIC>(dist_exact_rt<METRIC, float, 32>(r, cw, sd));
+    return finish_metric<METRIC>(dist_exact_rt<METRIC>(r, cw, sd));
+  } else {
+    const float v = finish_metric<METRIC>(dist_exact_rt<METRIC>(r, cw, sd));
+    return v != v ? lut_nan_sign(r, cw, sd, v) : v;
   }
-  return finish_metric<METRIC>(dist_exact_rt<METRIC>(r, cw, sd));
 }
 
 struct ScanShared {
@@ -1307,6 +1323,8 @@ struct ExactArgs {
   uint32_t *n_fallback;  // statistics
 };
 
+constexpr size_t EXACT_STATIC_LDS = 16;      // s_hlen, s_tcnt below, padded to the dynamic region's alignment (.group_segment_fixed_size)
+
 template <int METRIC, int NBITS>
 __global__ __launch_bounds__(64) void ivfpq_exact_kernel(ExactArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1862,7 +1880,9 @@ static int ivfpq_search_enqueue_impl(lance_hip_ctx *ctx, const lance_hip_index *
     const int dpad = (d + 3) & ~3;
     const size_t lds = (size_t)dpad * 4 + (size_t)m * 256 * 4 + (size_t)keff * 12 + ((size_t)keff + 1) * 8 + 64 * 4 + 16 +
                        16 + (size_t)std::max<uint32_t>(200, keff) * 4 + (size_t)m * 16 + 16;
-    LH_REQUIRE(lds <= 160 * 1024, "search: exact kernel does not fit in LDS (m=%d, k*refine=%u)", m, keff);
+    // the kernel's two static ints take 16 bytes in front of the dynamic region (its 16-byte alignment): a request of 160 KiB - 8 was
+    // accepted here and refused by the queue (HSA_STATUS_ERROR_INVALID_ALLOCATION, group segment 163848 at d 64, M 32, k 5416)
+    LH_REQUIRE(lds + EXACT_STATIC_LDS <= 160 * 1024, "search: exact kernel does not fit in LDS (m=%d, k*refine=%u)", m, keff);
     ScopedTimer t(ctx, "ivfpq_exact");
     if (ix->nbits == 4) {
       if (scan_metric == LANCE_HIP_DOT) hipLaunchKernelGGL((ivfpq_exact_kernel<METRIC_DOT, 4>), dim3(nq), dim3(64), lds, ctx->stream, ea);

@@ -93,6 +93,18 @@ class OracleEngine:
         p, d = oracle.find_partitions(qn, cn, nprobes, metric)
         return torch.from_numpy(p.view(np.int32).copy()), torch.from_numpy(d)
 
+    def pq_scan_topk(self, q_residual, codebook, codes_transposed, row_ids, k, metric="l2", lower=None, upper=None):
+        """one partition: the table, distance_all (k_hint = k), the partition's heap and the final sort"""
+        cb = _np(codebook).astype(f32)
+        nb = 4 if cb.shape[1] == 16 else 8
+        sm = "l2" if metric == "cosine" else metric
+        ct = np.ascontiguousarray(_np(codes_transposed), np.uint8)
+        rid = np.ascontiguousarray(_np(row_ids)).view(np.uint64)
+        lut = oracle.build_lut(_np(q_residual).astype(f32).reshape(-1), cb, sm, nbits=nb)
+        d = oracle.pq_scan4(lut, ct, k, sm) if nb == 4 else oracle.pq_scan(lut, ct, sm)
+        i, d = oracle.sort_fetch(*oracle.heap_topk(d, rid, k, lower, upper), k)
+        return torch.from_numpy(i.view(np.int64)), torch.from_numpy(d)
+
     def flat_topk(self, x, q, k, metric="l2", row_ids=None):
         rid = None if row_ids is None else np.ascontiguousarray(_np(row_ids)).view(np.uint64)
         xn = np.ascontiguousarray(_np(x))

@@ -110,6 +110,29 @@ def test_dryrun_4bit(fake, oracle, metric):
         assert "pq_scan_topk" in str(e)
 
 
+# ---- the 4-bit scan's specification cases (tests/test_zz_gpu_pq4.py): every body on the stand-ins, without the stage counters and the LDS
+# ---- refusal (the stand-ins enqueue nothing and refuse nothing)
+def test_dryrun_pq4_cases(fake, oracle):
+    import pq4_spec as S
+    import test_zz_gpu_pq4 as Z
+    for c in S.CASES:
+        Z.case_body(fake, c.name)
+    for name in S.RANGE_CASES:
+        Z.case_body(fake, name, nbits=8)
+
+
+def test_dryrun_pq4_scan_grid(fake, oracle):
+    import test_zz_gpu_pq4 as Z
+    Z.scan_grid_body(fake, oracle, "dot-signs", keffs=(1, 129, 250, 5000))
+
+
+def test_dryrun_pq4_routes_and_adaptive_probing(fake, oracle):
+    import test_zz_gpu_pq4 as Z
+    Z.scan4_route_body(fake, 40, counters=False, searches=Z.SCAN4_SEARCHES[:2] + Z.SCAN4_SEARCHES[4:6])
+    Z.exact_route_body(fake, counters=False, searches=((129, 0), (60, 5)), nq=3)
+    Z.adaptive_body(fake)
+
+
 # ---- Float16 columns under dot / cosine (tests/test_zz_gpu_f16_metrics.py): the host layer and the tests' own expectations
 @pytest.mark.parametrize("d", [32, 56, 20])
 def test_dryrun_f16_dot_assign(fake, oracle, d):
