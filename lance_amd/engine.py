@@ -191,8 +191,9 @@ def _on_engine_device(fn):
 
 
 def _wrap_methods(cls, skip=()):
+    """_on_engine_device around the public methods cls itself defines (private helpers run inside one of those)"""
     for name, fn in list(vars(cls).items()):
-        if callable(fn) and not name.startswith("__") and name not in skip and not isinstance(fn, (classmethod, staticmethod)):
+        if callable(fn) and not name.startswith("_") and name not in skip and not isinstance(fn, (classmethod, staticmethod)):
             setattr(cls, name, _on_engine_device(fn))
     return cls
 
@@ -482,8 +483,7 @@ class Engine:
         out_d = torch.empty(k, dtype=torch.float32, device=q.device)
         cnt = C.c_uint32(0)
         has = lower is not None or upper is not None
-        lo = float(np.finfo(np.float32).min) if lower is None else float(lower)
-        hi = float(np.finfo(np.float32).max) if upper is None else float(upper)
+        lo, hi = _range_f32(lower, upper)
         torch.cuda.synchronize()
         check(self.lib.lance_hip_pq_scan_topk(self.h, dt, METRICS[metric], _ptr(q), q.numel(), _ptr(cb), m, nb, _ptr(ct),
                                               _ptr(rid), n_p, k, int(has), lo, hi, _ptr(out_i), _ptr(out_d), C.byref(cnt)))
@@ -756,8 +756,37 @@ def _export_rows(engine, handle, nlist, row_bytes, aux=False):
     return offs, rows, xx, rid
 
 
-class DeviceFlatIndex:
-    """Handle of a device-resident IVF_FLAT index (FlatIndex sub-index over the raw vectors of each partition)."""
+def _raw_column(raw, dtype):
+    t = raw if isinstance(raw, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(raw))
+    t = t.to(dtype).to(_dev()).contiguous()
+    if t.dim() != 2:
+        raise ValueError(f"raw vectors must be [rows][d], got shape {tuple(t.shape)}")
+    return t
+
+
+def _allow_bytes(allow):
+    """a prefilter (boolean array indexed by row id) -> uint8 device tensor; None stays None"""
+    if allow is None:
+        return None
+    a = allow if isinstance(allow, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(allow, dtype=bool))
+    return a.to(torch.uint8).to(_dev()).contiguous()
+
+
+def _range_f32(lower, upper):
+    """distance range -> (lo, hi) as the library takes them.  The bounds are f32 values in the reference (Query::lower_bound:
+    Option<f32>): they are rounded before use, and an open end is the largest finite f32 of its sign."""
+    lo = float(np.finfo(np.float32).min) if lower is None else float(np.float32(lower))
+    hi = float(np.finfo(np.float32).max) if upper is None else float(np.float32(upper))
+    return lo, hi
+
+
+# ---- the index handles ---------------------------------------------------------------------------------------------------------------
+# _DeviceHandle is what the four kinds share; _Maintainable adds merge / remap / split / join for the kinds whose storage can be appended
+# to (IVF_RQ's cannot); _CodeIndex is the search of the two kinds that scan codes and re-rank on the raw column (IVF_SQ, IVF_RQ).  A new
+# kind supplies its `create`, its table of search symbols and, to be maintainable, the `_ctor_args` hook.
+class _DeviceHandle:
+    """A device-resident index: the library handle `h`, the model tensors that must outlive it, the element type of queries and raw
+    vectors, and the raw column when one is attached (borrowed by the handle, kept alive here)."""
 
     def __init__(self, engine, handle, metric, centroids, data_dtype):
         self.engine = engine
@@ -765,6 +794,76 @@ class DeviceFlatIndex:
         self.metric = metric
         self.centroids = centroids
         self.data_dtype = data_dtype
+        self._raw = None
+
+    def _queries(self, q):
+        """-> (q as the [nq][d] device tensor of the index's element type, the tensor it was made from: the same storage when the
+        caller handed over a ready batch)"""
+        t = q if isinstance(q, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(q))
+        return t.to(self.data_dtype).to(_dev()).contiguous().reshape(-1, self.centroids.shape[1]), t
+
+    @staticmethod
+    def _outputs(q, k, out=None, rows=None):
+        """-> (ids int64, dists f32), [rows or len(q)][k] each, beside q: the caller's `out` or fresh tensors"""
+        if out is not None:
+            return out
+        rows = q.shape[0] if rows is None else rows
+        return torch.empty((rows, k), dtype=torch.int64, device=q.device), torch.empty((rows, k), dtype=torch.float32, device=q.device)
+
+    def _set_raw(self, t):
+        self._raw = t
+        check(self.engine.lib.lance_hip_index_set_raw(self.h, _ptr(t), t.shape[0]))
+
+    def save(self, index_dir, loss=None):
+        """HBM -> the file pair, in the layout merge_partitions writes (builder.rs:938-1079), through lance_hip_index_save."""
+        torch.cuda.synchronize()
+        check(self.engine.lib.lance_hip_index_save(self.engine.h, self.h, os.fspath(index_dir).encode(),
+                                                   0 if loss is None else 1, 0.0 if loss is None else float(loss)))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.engine.lib.lance_hip_index_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _Maintainable:
+    """merge / remap / split / join (lance_amd/csrc/index_update.hip): every call returns a NEW index of the same kind over the same
+    model and leaves its sources as they are.  The class supplies _ctor_args(handle, centroids=None, raw=None): the constructor
+    arguments of an index like this one over another handle, with other centroids and, where the kind attaches one, a raw column."""
+
+    @classmethod
+    def merge(cls, indices, raw=None):
+        """For every partition the rows of indices[0], then those of indices[1], ... (lance_hip_index_merge) -> a new index; the
+        sources must share the model bit for bit (centroids, codebook, quantiser bounds).  raw: the vectors for refine, indexed by
+        row id, attached by IVF_PQ (the sources' attachments are not inherited); the other kinds accept and ignore it."""
+        first = indices[0]
+        return cls(*first._ctor_args(_merge_handles(first.engine, indices), raw=raw))
+
+    def remap(self, old_ids, new_ids):
+        """lance_hip_index_remap with a mapping already sorted by old id -> a new index"""
+        return type(self)(*self._ctor_args(_remap_handle(self.engine, self.h, old_ids, new_ids)))
+
+    def split(self, part, centroids2, raw):
+        """lance_hip_index_split -> a new index with nlist + 1 partitions (c1 = centroids2[0] replaces centroid `part`, c2 is appended);
+        no raw vectors attached"""
+        return type(self)(*self._ctor_args(*_rebalance_handle(self.engine, self.h, self.centroids, part, raw, centroids2)))
+
+    def join(self, part, raw):
+        """lance_hip_index_join -> a new index without partition `part`: its rows go to their nearest neighbours"""
+        return type(self)(*self._ctor_args(*_rebalance_handle(self.engine, self.h, self.centroids, part, raw)))
+
+
+class DeviceFlatIndex(_Maintainable, _DeviceHandle):
+    """Handle of a device-resident IVF_FLAT index (FlatIndex sub-index over the raw vectors of each partition)."""
+
+    def _ctor_args(self, handle, centroids=None, raw=None):
+        return self.engine, handle, self.metric, self.centroids if centroids is None else centroids, self.data_dtype
 
     @classmethod
     def create(cls, engine, metric, centroids, x, part_ids, row_ids=None):
@@ -792,108 +891,68 @@ class DeviceFlatIndex:
         check(engine.lib.lance_hip_index_load(engine.h, os.fspath(index_dir).encode(), dt, C.byref(h)))
         return cls(engine, h, c.metric, to_device(c.centroids, torch.float16 if c.dtype == "float16" else torch.float32), ddt)
 
-    @classmethod
-    def merge(cls, indices, raw=None):
-        """For every partition the rows of indices[0], then those of indices[1], ... (lance_hip_index_merge) -> a new index; the
-        sources stay as they are.  raw is accepted for symmetry with DeviceIndex.merge and ignored (no refine on this kind)."""
-        first = indices[0]
-        return cls(first.engine, _merge_handles(first.engine, indices), first.metric, first.centroids, first.data_dtype)
-
-    def remap(self, old_ids, new_ids):
-        """lance_hip_index_remap with a mapping already sorted by old id -> a new index"""
-        return type(self)(self.engine, _remap_handle(self.engine, self.h, old_ids, new_ids), self.metric, self.centroids, self.data_dtype)
-
-    def split(self, part, centroids2, raw):
-        """lance_hip_index_split -> a new index with nlist + 1 partitions (c1 = centroids2[0] replaces centroid `part`, c2 is appended)"""
-        h, cent = _rebalance_handle(self.engine, self.h, self.centroids, part, raw, centroids2)
-        return type(self)(self.engine, h, self.metric, cent, self.data_dtype)
-
-    def join(self, part, raw):
-        """lance_hip_index_join -> a new index without partition `part`: its rows go to their nearest neighbours"""
-        h, cent = _rebalance_handle(self.engine, self.h, self.centroids, part, raw)
-        return type(self)(self.engine, h, self.metric, cent, self.data_dtype)
-
     def export_rows(self):
         """-> (part_offsets u32[nlist + 1], vectors f32 [n, d], row_ids u64[n]) in stored order"""
         nlist, d = self.centroids.shape
         offs, rows, _, rid = _export_rows(self.engine, self.h, nlist, 4 * d)
         return offs, rows.view(np.float32), rid
 
-    def save(self, index_dir, loss=None):
-        torch.cuda.synchronize()
-        check(self.engine.lib.lance_hip_index_save(self.engine.h, self.h, os.fspath(index_dir).encode(),
-                                                   0 if loss is None else 1, 0.0 if loss is None else float(loss)))
-
     def search(self, q, k, nprobes, allow=None, lower=None, upper=None):
         """allow: boolean array indexed by row id (a prefilter) -- tested inside the scan kernels
         (lance_hip_ivfflat_search_filtered), no filtered copy of the index.
         lower / upper: distance range -- only rows with lower <= d < upper enter the per-partition heaps (flat/index.rs:91-149),
         alone or combined with `allow` (lance_hip_ivfflat_search_range whenever either bound is given)."""
-        d = self.centroids.shape[1]
-        t = q if isinstance(q, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(q))
-        q = t.to(self.data_dtype).to(_dev()).contiguous().reshape(-1, d)
-        nq = q.shape[0]
-        ids = torch.empty((nq, k), dtype=torch.int64, device=q.device)
-        dists = torch.empty((nq, k), dtype=torch.float32, device=q.device)
-        if lower is not None or upper is not None:
-            # the bounds are f32 values in the reference (Query::lower_bound: Option<f32>): round before use
-            lo = float(np.finfo(np.float32).min) if lower is None else float(np.float32(lower))
-            hi = float(np.finfo(np.float32).max) if upper is None else float(np.float32(upper))
-            a = _allow_bytes(allow)
-            torch.cuda.synchronize()
-            check(self.engine.lib.lance_hip_ivfflat_search_range(self.engine.h, self.h, _ptr(q), nq, k, nprobes, _ptr(a),
-                                                                 0 if a is None else a.numel(), lo, hi, _ptr(ids), _ptr(dists)))
-            return ids, dists
-        if allow is not None:
-            a = allow if isinstance(allow, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(allow, dtype=bool))
-            a = a.to(torch.uint8).to(_dev()).contiguous()
-            torch.cuda.synchronize()
-            check(self.engine.lib.lance_hip_ivfflat_search_filtered(self.engine.h, self.h, _ptr(q), nq, k, nprobes, _ptr(a), a.numel(),
-                                                                    _ptr(ids), _ptr(dists)))
-            return ids, dists
+        q, _ = self._queries(q)
+        ids, dists = self._outputs(q, k)
+        a = _allow_bytes(allow)
+        lib, args = self.engine.lib, (self.engine.h, self.h, _ptr(q), q.shape[0], k, nprobes)
         torch.cuda.synchronize()
-        check(self.engine.lib.lance_hip_ivfflat_search(self.engine.h, self.h, _ptr(q), nq, k, nprobes, _ptr(ids), _ptr(dists)))
+        if lower is not None or upper is not None:
+            check(lib.lance_hip_ivfflat_search_range(*args, _ptr(a), 0 if a is None else a.numel(), *_range_f32(lower, upper),
+                                                     _ptr(ids), _ptr(dists)))
+        elif a is not None:
+            check(lib.lance_hip_ivfflat_search_filtered(*args, _ptr(a), a.numel(), _ptr(ids), _ptr(dists)))
+        else:
+            check(lib.lance_hip_ivfflat_search(*args, _ptr(ids), _ptr(dists)))
         return ids, dists
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.engine.lib.lance_hip_index_destroy(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+class _CodeIndex(_DeviceHandle):
+    """The two kinds that scan quantised codes and can re-rank on the raw column: IVF_SQ and IVF_RQ."""
+    _SEARCH = None      # the library's (search, search_filtered, search_refine) of the kind
+
+    def set_raw(self, raw):
+        """the column for refine_factor searches, indexed by row id, in the element type of the queries (borrowed by the handle,
+        kept alive here).  For a cosine index: the ORIGINAL rows, not the normalised ones the codes were made from"""
+        self._set_raw(_raw_column(raw, self.data_dtype))
+
+    def search(self, q, k, nprobes, allow=None, refine_factor=0):
+        """allow: boolean array indexed by row id (a prefilter), tested inside the scan kernels (search_filtered); for IVF_RQ every
+        selected row then takes the f32 distance, as the reference's prefiltered FlatIndex::search does.
+        refine_factor > 0: the k * refine_factor best by the quantised distance are re-scored against the raw vectors (set_raw) with
+        the query as given and the k best by the exact distance are returned (search_refine)"""
+        plain, filtered, refine = (getattr(self.engine.lib, name) for name in self._SEARCH)
+        q, _ = self._queries(q)
+        ids, dists = self._outputs(q, k)
+        a = _allow_bytes(allow)
+        args = (self.engine.h, self.h, _ptr(q), q.shape[0], k, nprobes)
+        torch.cuda.synchronize()
+        if refine_factor:
+            check(refine(*args, refine_factor, _ptr(a), 0 if a is None else a.numel(), _ptr(ids), _ptr(dists)))
+        elif a is not None:
+            check(filtered(*args, _ptr(a), a.numel(), _ptr(ids), _ptr(dists)))
+        else:
+            check(plain(*args, _ptr(ids), _ptr(dists)))
+        return ids, dists
 
 
-
-def _raw_column(raw, dtype):
-    t = raw if isinstance(raw, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(raw))
-    t = t.to(dtype).to(_dev()).contiguous()
-    if t.dim() != 2:
-        raise ValueError(f"raw vectors must be [rows][d], got shape {tuple(t.shape)}")
-    return t
-
-
-def _allow_bytes(allow):
-    if allow is None:
-        return None
-    a = allow if isinstance(allow, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(allow, dtype=bool))
-    return a.to(torch.uint8).to(_dev()).contiguous()
-
-
-class DeviceRqIndex:
+class DeviceRqIndex(_CodeIndex):
     """Handle of a device-resident IVF_RQ index (FlatIndex sub-index over the 1-bit RaBitQ codes and factors of each partition)."""
+    _SEARCH = ("lance_hip_ivfrq_search", "lance_hip_ivfrq_search_filtered", "lance_hip_ivfrq_search_refine")
 
     def __init__(self, engine, handle, metric, centroids, rotation):
-        self.engine = engine
-        self.h = handle
-        self.metric = metric
-        self.centroids = centroids
+        super().__init__(engine, handle, metric, centroids, torch.float32)
         self.rotation = rotation
-        self.data_dtype = torch.float32
-        self._raw = None
 
     @classmethod
     def create(cls, engine, metric, centroids, rotation, codes, add, scale, part_ids, row_ids=None):
@@ -915,64 +974,23 @@ class DeviceRqIndex:
                                                 _ptr(scale), _ptr(part), _ptr(rid), n, C.byref(h)))
         return cls(engine, h, metric, cent, rot)
 
+    def _queries(self, q):
+        return _rq_f32(q, "queries").reshape(-1, self.centroids.shape[1]), q
+
     def save(self, index_dir, loss=None):
         raise NotImplementedError("IVF_RQ index files are not supported (IVF_PQ and IVF_FLAT are)")
 
-    def set_raw(self, raw):
-        """the column for refine_factor searches, indexed by row id (float32; borrowed by the handle, kept alive here)"""
-        self._raw = _raw_column(raw, self.data_dtype)
-        check(self.engine.lib.lance_hip_index_set_raw(self.h, _ptr(self._raw), self._raw.shape[0]))
 
-    def search(self, q, k, nprobes, allow=None, refine_factor=0):
-        """allow: boolean array indexed by row id (a prefilter), tested inside the scan kernels (lance_hip_ivfrq_search_filtered): every
-        selected row then takes the f32 distance, as the reference's prefiltered FlatIndex::search does.
-        refine_factor > 0: the k * refine_factor best by the RQ estimate are re-scored against the raw vectors (set_raw) and the k
-        best by the exact distance are returned (lance_hip_ivfrq_search_refine)"""
-        d = self.centroids.shape[1]
-        q = _rq_f32(q, "queries").reshape(-1, d)
-        nq = q.shape[0]
-        ids = torch.empty((nq, k), dtype=torch.int64, device=q.device)
-        dists = torch.empty((nq, k), dtype=torch.float32, device=q.device)
-        if refine_factor:
-            a = _allow_bytes(allow)
-            torch.cuda.synchronize()
-            check(self.engine.lib.lance_hip_ivfrq_search_refine(self.engine.h, self.h, _ptr(q), nq, k, nprobes, refine_factor, _ptr(a),
-                                                                0 if a is None else a.numel(), _ptr(ids), _ptr(dists)))
-            return ids, dists
-        if allow is not None:
-            a = allow if isinstance(allow, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(allow, dtype=bool))
-            a = a.to(torch.uint8).to(_dev()).contiguous()
-            torch.cuda.synchronize()
-            check(self.engine.lib.lance_hip_ivfrq_search_filtered(self.engine.h, self.h, _ptr(q), nq, k, nprobes, _ptr(a), a.numel(),
-                                                                  _ptr(ids), _ptr(dists)))
-            return ids, dists
-        torch.cuda.synchronize()
-        check(self.engine.lib.lance_hip_ivfrq_search(self.engine.h, self.h, _ptr(q), nq, k, nprobes, _ptr(ids), _ptr(dists)))
-        return ids, dists
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.engine.lib.lance_hip_index_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class DeviceSqIndex:
+class DeviceSqIndex(_Maintainable, _CodeIndex):
     """Handle of a device-resident IVF_SQ index (FlatIndex sub-index over the 8-bit scalar-quantised codes of each partition)."""
+    _SEARCH = ("lance_hip_ivfsq_search", "lance_hip_ivfsq_search_filtered", "lance_hip_ivfsq_search_refine")
 
     def __init__(self, engine, handle, metric, centroids, data_dtype, bounds):
-        self.engine = engine
-        self.h = handle
-        self.metric = metric
-        self.centroids = centroids
-        self.data_dtype = data_dtype
+        super().__init__(engine, handle, metric, centroids, data_dtype)
         self.bounds = bounds
-        self._raw = None
+
+    def _ctor_args(self, handle, centroids=None, raw=None):
+        return self.engine, handle, self.metric, self.centroids if centroids is None else centroids, self.data_dtype, self.bounds
 
     @classmethod
     def create(cls, engine, metric, centroids, codes, part_ids, bounds, row_ids=None):
@@ -990,27 +1008,6 @@ class DeviceSqIndex:
                                                 _ptr(rid), n, b, C.byref(h)))
         return cls(engine, h, metric, cent, cent.dtype, (float(bounds[0]), float(bounds[1])))
 
-    @classmethod
-    def merge(cls, indices, raw=None):
-        """as DeviceFlatIndex.merge; the sources must share the quantiser's bounds bit for bit"""
-        first = indices[0]
-        return cls(first.engine, _merge_handles(first.engine, indices), first.metric, first.centroids, first.data_dtype, first.bounds)
-
-    def remap(self, old_ids, new_ids):
-        """lance_hip_index_remap with a mapping already sorted by old id -> a new index"""
-        return type(self)(self.engine, _remap_handle(self.engine, self.h, old_ids, new_ids), self.metric, self.centroids, self.data_dtype,
-                          self.bounds)
-
-    def split(self, part, centroids2, raw):
-        """lance_hip_index_split -> a new index with nlist + 1 partitions (c1 = centroids2[0] replaces centroid `part`, c2 is appended)"""
-        h, cent = _rebalance_handle(self.engine, self.h, self.centroids, part, raw, centroids2)
-        return type(self)(self.engine, h, self.metric, cent, self.data_dtype, self.bounds)
-
-    def join(self, part, raw):
-        """lance_hip_index_join -> a new index without partition `part`: its rows go to their nearest neighbours"""
-        h, cent = _rebalance_handle(self.engine, self.h, self.centroids, part, raw)
-        return type(self)(self.engine, h, self.metric, cent, self.data_dtype, self.bounds)
-
     def export_rows(self):
         """-> (part_offsets u32[nlist + 1], codes u8 [n, d], sums of squared codes u32[n], row_ids u64[n]) in stored order"""
         nlist, d = self.centroids.shape
@@ -1019,64 +1016,18 @@ class DeviceSqIndex:
     def save(self, index_dir, loss=None):
         raise NotImplementedError("IVF_SQ index files are not supported (IVF_PQ and IVF_FLAT are)")
 
-    def set_raw(self, raw):
-        """the column for refine_factor searches, indexed by row id, in the column's element type (borrowed by the handle, kept
-        alive here).  For a cosine index: the ORIGINAL rows, not the normalised ones the codes were made from"""
-        self._raw = _raw_column(raw, self.data_dtype)
-        check(self.engine.lib.lance_hip_index_set_raw(self.h, _ptr(self._raw), self._raw.shape[0]))
 
-    def search(self, q, k, nprobes, allow=None, refine_factor=0):
-        """allow: boolean array indexed by row id (a prefilter), tested inside the scan kernels (lance_hip_ivfsq_search_filtered).
-        refine_factor > 0: the k * refine_factor best by the SQ distance are re-scored against the raw vectors (set_raw) with the
-        query as given and the k best by the exact distance are returned (lance_hip_ivfsq_search_refine)"""
-        d = self.centroids.shape[1]
-        t = q if isinstance(q, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(q))
-        q = t.to(self.data_dtype).to(_dev()).contiguous().reshape(-1, d)
-        nq = q.shape[0]
-        ids = torch.empty((nq, k), dtype=torch.int64, device=q.device)
-        dists = torch.empty((nq, k), dtype=torch.float32, device=q.device)
-        if refine_factor:
-            a = _allow_bytes(allow)
-            torch.cuda.synchronize()
-            check(self.engine.lib.lance_hip_ivfsq_search_refine(self.engine.h, self.h, _ptr(q), nq, k, nprobes, refine_factor, _ptr(a),
-                                                                0 if a is None else a.numel(), _ptr(ids), _ptr(dists)))
-            return ids, dists
-        if allow is not None:
-            a = allow if isinstance(allow, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(allow, dtype=bool))
-            a = a.to(torch.uint8).to(_dev()).contiguous()
-            torch.cuda.synchronize()
-            check(self.engine.lib.lance_hip_ivfsq_search_filtered(self.engine.h, self.h, _ptr(q), nq, k, nprobes, _ptr(a), a.numel(),
-                                                                  _ptr(ids), _ptr(dists)))
-            return ids, dists
-        torch.cuda.synchronize()
-        check(self.engine.lib.lance_hip_ivfsq_search(self.engine.h, self.h, _ptr(q), nq, k, nprobes, _ptr(ids), _ptr(dists)))
-        return ids, dists
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.engine.lib.lance_hip_index_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class DeviceIndex:
+class DeviceIndex(_Maintainable, _DeviceHandle):
     """Handle of a device-resident IVF_PQ index (lance_hip_index)."""
 
     def __init__(self, engine, handle, metric, centroids, codebook, raw=None, data_dtype=None):
-        self.data_dtype = data_dtype if data_dtype is not None else centroids.dtype   # element type of queries / raw vectors
-        self.engine = engine
-        self.h = handle
-        self.metric = metric
-        self.centroids = centroids
+        super().__init__(engine, handle, metric, centroids, data_dtype if data_dtype is not None else centroids.dtype)
         self.codebook = codebook
-        self._raw = None
         if raw is not None:
             self.set_raw(raw)
+
+    def _ctor_args(self, handle, centroids=None, raw=None):
+        return self.engine, handle, self.metric, self.centroids if centroids is None else centroids, self.codebook, raw, self.data_dtype
 
     @classmethod
     def create(cls, engine, metric, centroids, codebook, part_ids, codes, row_ids=None, raw=None, dtype=None):
@@ -1131,28 +1082,12 @@ class DeviceIndex:
         check(engine.lib.lance_hip_index_load_lists(engine.h, os.fspath(index_dir).encode(), dt, mod, rem, C.byref(h)))
         return cls(engine, h, c.metric, to_device(c.centroids, mdt), to_device(c.codebook, mdt), raw, ddt)
 
-    @classmethod
-    def merge(cls, indices, raw=None):
-        """For every partition the rows of indices[0], then those of indices[1], ... (lance_hip_index_merge) -> a new index; the
-        sources stay as they are.  raw: the vectors for refine, indexed by row id (the sources' attachments are not inherited)."""
-        first = indices[0]
-        return cls(first.engine, _merge_handles(first.engine, indices), first.metric, first.centroids, first.codebook, raw, first.data_dtype)
-
     def remap(self, old_ids, new_ids, raw=None):
-        """lance_hip_index_remap with a mapping already sorted by old id -> a new index"""
-        return type(self)(self.engine, _remap_handle(self.engine, self.h, old_ids, new_ids), self.metric, self.centroids, self.codebook, raw,
-                          self.data_dtype)
-
-    def split(self, part, centroids2, raw):
-        """lance_hip_index_split -> a new index with nlist + 1 partitions (c1 = centroids2[0] replaces centroid `part`, c2 is appended);
-        no raw vectors attached"""
-        h, cent = _rebalance_handle(self.engine, self.h, self.centroids, part, raw, centroids2)
-        return type(self)(self.engine, h, self.metric, cent, self.codebook, None, self.data_dtype)
-
-    def join(self, part, raw):
-        """lance_hip_index_join -> a new index without partition `part`: its rows go to their nearest neighbours"""
-        h, cent = _rebalance_handle(self.engine, self.h, self.centroids, part, raw)
-        return type(self)(self.engine, h, self.metric, cent, self.codebook, None, self.data_dtype)
+        """as the other kinds' remap; raw: the vectors for refine, attached to the new index"""
+        out = super().remap(old_ids, new_ids)
+        if raw is not None:
+            out.set_raw(raw)
+        return out
 
     def export_rows(self):
         """-> (part_offsets u32[nlist + 1], codes u8 [n, code bytes] row-major, row_ids u64[n]) in stored order"""
@@ -1160,16 +1095,9 @@ class DeviceIndex:
         offs, rows, _, rid = _export_rows(self.engine, self.h, self.centroids.shape[0], m if _nbits(self.codebook) == 8 else m // 2)
         return offs, rows, rid
 
-    def save(self, index_dir, loss=None):
-        """HBM -> the file pair, in the layout merge_partitions writes (builder.rs:938-1079), through lance_hip_index_save."""
-        torch.cuda.synchronize()
-        check(self.engine.lib.lance_hip_index_save(self.engine.h, self.h, os.fspath(index_dir).encode(),
-                                                   0 if loss is None else 1, 0.0 if loss is None else float(loss)))
-
     def set_raw(self, raw):
         t = raw if isinstance(raw, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(raw))
-        self._raw = t.to(self.data_dtype).to(_dev()).contiguous()
-        check(self.engine.lib.lance_hip_index_set_raw(self.h, _ptr(self._raw), self._raw.shape[0]))
+        self._set_raw(t.to(self.data_dtype).to(_dev()).contiguous())         # (any shape: the library takes the row count)
 
     def prewarm(self):
         """Index::prewarm (ivf/v2.rs:349-352, dataset.py prewarm_index): build the per-index search constants now."""
@@ -1203,15 +1131,9 @@ class DeviceIndex:
     def search(self, q, k, nprobes, refine_factor=0, out=None, sync=True, engine=None):
         """engine: another Engine (own stream + scratch arena) on the same GPU to run this batch on -- the index is read-only
         during searches, so batches enqueued through different engines overlap on the device (sync=False)."""
-        d = self.centroids.shape[1]
-        t = q if isinstance(q, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(q))
-        q = t.to(self.data_dtype).to(_dev()).contiguous().reshape(-1, d)
+        q, t = self._queries(q)
         nq = q.shape[0]
-        if out is None:
-            ids = torch.empty((nq, k), dtype=torch.int64, device=q.device)
-            dists = torch.empty((nq, k), dtype=torch.float32, device=q.device)
-        else:
-            ids, dists = out
+        ids, dists = self._outputs(q, k, out)
         eng = engine if engine is not None else self.engine
         fn = eng.lib.lance_hip_ivfpq_search if sync else eng.lib.lance_hip_ivfpq_search_async
         if sync and nq > 1 and nq * max(1, nprobes) > self.MAX_PAIRS_PER_CALL:
@@ -1223,13 +1145,11 @@ class DeviceIndex:
                 b = min(nq, a + step)
                 check(fn(eng.h, self.h, _ptr(q[a:b]), b - a, k, nprobes, refine_factor, _ptr(ids[a:b]), _ptr(dists[a:b])))
             return ids, dists
-        if sync:
+        if sync or (not eng.use_torch_stream and (q.data_ptr() != t.data_ptr() or out is None)):
+            # asynchronous: only when the batch was converted / moved / allocated by torch kernels on torch's stream -- they must
+            # finish before the engine's own stream reads them.  reshape() always makes a new tensor OBJECT, so the test is on the
+            # storage: a caller that hands over ready device tensors of the index's element type (and `out`) pays nothing
             _torch_inputs_ready()
-        elif not eng.use_torch_stream and (q.data_ptr() != t.data_ptr() or out is None):
-            # the batch was converted / moved / allocated by torch kernels on torch's stream: they must finish before the
-            # engine's own stream reads them.  reshape() always makes a new tensor OBJECT, so the test is on the storage: a
-            # caller that hands over ready device tensors of the index's element type (and `out`) pays nothing
-            torch.cuda.current_stream().synchronize()
         check(fn(eng.h, self.h, _ptr(q), nq, k, nprobes, refine_factor, _ptr(ids), _ptr(dists)))
         return ids, dists
 
@@ -1237,19 +1157,11 @@ class DeviceIndex:
         """Search under a row-id prefilter (lance_hip_ivfpq_search_filtered): `allow` = boolean array indexed by row id.  The
         mask is tested inside the scan kernels; no filtered copy of the index is built.  out = (ids, dists) device tensors to
         write into (a caller that keeps its query / output buffers gets the captured-graph path from its second call)."""
-        d = self.centroids.shape[1]
-        t = q if isinstance(q, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(q))
-        q = t.to(self.data_dtype).to(_dev()).contiguous().reshape(-1, d)
-        a = allow if isinstance(allow, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(allow, dtype=bool))
-        a = a.to(torch.uint8).to(_dev()).contiguous()
-        nq = q.shape[0]
-        if out is None:
-            ids = torch.empty((nq, k), dtype=torch.int64, device=q.device)
-            dists = torch.empty((nq, k), dtype=torch.float32, device=q.device)
-        else:
-            ids, dists = out
+        q, _ = self._queries(q)
+        a = _allow_bytes(allow)
+        ids, dists = self._outputs(q, k, out)
         _torch_inputs_ready()
-        check(self.engine.lib.lance_hip_ivfpq_search_filtered(self.engine.h, self.h, _ptr(q), nq, k, nprobes, refine_factor, _ptr(a),
+        check(self.engine.lib.lance_hip_ivfpq_search_filtered(self.engine.h, self.h, _ptr(q), q.shape[0], k, nprobes, refine_factor, _ptr(a),
                                                               a.numel(), _ptr(ids), _ptr(dists)))
         return ids, dists
 
@@ -1265,17 +1177,11 @@ class DeviceIndex:
         if int(k) < 1 or int(overfetch) < 1:
             raise ValueError(f"k={k}, overfetch={overfetch}: both must be at least 1")
         check_multivector_ann_sizes(int(k) * int(overfetch), k_out)
-        d = self.centroids.shape[1]
-        t = q if isinstance(q, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(q))
-        q = t.to(self.data_dtype).to(_dev()).contiguous().reshape(-1, d)
+        q, _ = self._queries(q)
         if q.shape[0] != int(off[-1]):
             raise ValueError(f"q holds {q.shape[0]} vectors, q_offsets end at {int(off[-1])}")
-        a = None
-        if allow is not None:
-            a = allow if isinstance(allow, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(allow, dtype=bool))
-            a = a.to(torch.uint8).to(_dev()).contiguous()
-        ids = torch.empty((B, k_out), dtype=torch.int64, device=q.device)
-        dists = torch.empty((B, k_out), dtype=torch.float32, device=q.device)
+        a = _allow_bytes(allow)
+        ids, dists = self._outputs(q, k_out, rows=B)
         _torch_inputs_ready()
         check(self.engine.lib.lance_hip_ivfpq_multivec_search(self.engine.h, self.h, _ptr(q), off.ctypes.data_as(C.c_void_p), B, int(k),
                                                               min(int(nprobes), self.centroids.shape[0]), int(overfetch), k_out, _ptr(a),
@@ -1287,16 +1193,12 @@ class DeviceIndex:
         (dist, rowid) order and, aligned with them, each one's exact distance to the query (lance_hip_ivfpq_search_candidates) -- the
         local half of a list-sharded search with refine (lance_amd/dist.py: search_list_sharded)."""
         eng = engine or self.engine
-        d = self.centroids.shape[1]
-        t = q if isinstance(q, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(q))
-        q = t.to(self.data_dtype).to(_dev()).contiguous().reshape(-1, d)
-        nq = q.shape[0]
-        ids = torch.empty((nq, keff), dtype=torch.int64, device=q.device)
-        pq = torch.empty((nq, keff), dtype=torch.float32, device=q.device)
-        ex = torch.empty((nq, keff), dtype=torch.float32, device=q.device) if exact else None
+        q, _ = self._queries(q)
+        ids, pq = self._outputs(q, keff)
+        ex = torch.empty_like(pq) if exact else None
         _torch_inputs_ready()
-        check(eng.lib.lance_hip_ivfpq_search_candidates(eng.h, self.h, _ptr(q), nq, keff, min(nprobes, self.centroids.shape[0]), _ptr(ids), _ptr(pq),
-                                                        _ptr(ex) if exact else None))
+        check(eng.lib.lance_hip_ivfpq_search_candidates(eng.h, self.h, _ptr(q), q.shape[0], keff, min(nprobes, self.centroids.shape[0]),
+                                                        _ptr(ids), _ptr(pq), _ptr(ex)))
         return ids, pq, ex
 
     def search_range(self, q, k, nprobes, lower=None, upper=None, refine_factor=0, allow=None, out=None):
@@ -1305,12 +1207,10 @@ class DeviceIndex:
         k * refine_factor candidates come back re-ranked from the device and the range is applied to them here.
         allow: boolean array indexed by row id -- the range combined with a row-id prefilter, tested inside the scan
         kernels (lance_hip_ivfpq_search_filtered_range; flat/index.rs:131-149)."""
+        lo, hi = _range_f32(lower, upper)
         if refine_factor and refine_factor > 0:
             keff = k * refine_factor
             ci, cd = self.search_range(q, keff, nprobes, lower, upper, refine_factor=-1, allow=allow)       # -1: re-rank, keep all
-            # the bounds are f32 values in the reference (Query::lower_bound: Option<f32>): round before comparing
-            lo = float(np.finfo(np.float32).min) if lower is None else float(np.float32(lower))
-            hi = float(np.finfo(np.float32).max) if upper is None else float(np.float32(upper))
             ok = (ci >= 0) & (cd >= lo) & (cd < hi)
             # first k in-range entries of every row, order kept (the device returned them sorted by (distance, row id))
             rank = torch.cumsum(ok.to(torch.int64), dim=1) - 1
@@ -1321,43 +1221,22 @@ class DeviceIndex:
             ids[rows[take], rank[take]] = ci[take]
             dists[rows[take], rank[take]] = cd[take]
             return ids, dists
-        d = self.centroids.shape[1]
-        t = q if isinstance(q, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(q))
-        q = t.to(self.data_dtype).to(_dev()).contiguous().reshape(-1, d)
-        nq = q.shape[0]
-        if out is None:
-            ids = torch.empty((nq, k), dtype=torch.int64, device=q.device)
-            dists = torch.empty((nq, k), dtype=torch.float32, device=q.device)
-        else:
-            ids, dists = out
-        lo = float(np.finfo(np.float32).min) if lower is None else float(np.float32(lower))
-        hi = float(np.finfo(np.float32).max) if upper is None else float(np.float32(upper))
-        if allow is not None:
-            a = allow if isinstance(allow, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(allow, dtype=bool))
-            a = a.to(torch.uint8).to(_dev()).contiguous()
-            _torch_inputs_ready()
-            check(self.engine.lib.lance_hip_ivfpq_search_filtered_range(self.engine.h, self.h, _ptr(q), nq, k, nprobes,
-                                                                        1 if refine_factor == -1 else 0, _ptr(a), a.numel(), lo, hi,
-                                                                        _ptr(ids), _ptr(dists)))
-            return ids, dists
+        q, _ = self._queries(q)
+        ids, dists = self._outputs(q, k, out)
+        a = _allow_bytes(allow)
+        args = (self.engine.h, self.h, _ptr(q), q.shape[0], k, nprobes, 1 if refine_factor == -1 else 0)
         _torch_inputs_ready()
-        check(self.engine.lib.lance_hip_ivfpq_search_range(self.engine.h, self.h, _ptr(q), nq, k, nprobes, 1 if refine_factor == -1 else 0,
-                                                           lo, hi, _ptr(ids), _ptr(dists)))
+        if a is not None:
+            check(self.engine.lib.lance_hip_ivfpq_search_filtered_range(*args, _ptr(a), a.numel(), lo, hi, _ptr(ids), _ptr(dists)))
+        else:
+            check(self.engine.lib.lance_hip_ivfpq_search_range(*args, lo, hi, _ptr(ids), _ptr(dists)))
         return ids, dists
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.engine.lib.lance_hip_index_destroy(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-_wrap_methods(DeviceFlatIndex, skip=("close",))
-_wrap_methods(DeviceSqIndex, skip=("close", "save"))
-_wrap_methods(DeviceRqIndex, skip=("close", "save"))
-_wrap_methods(DeviceIndex, skip=("close",))
+_wrap_methods(_DeviceHandle, skip=("close",))       # (_wrap_methods sees a class's own methods only: the bases are wrapped here)
+_wrap_methods(_Maintainable)
+_wrap_methods(_CodeIndex)
+_wrap_methods(DeviceFlatIndex)
+_wrap_methods(DeviceSqIndex, skip=("save",))
+_wrap_methods(DeviceRqIndex, skip=("save",))
+_wrap_methods(DeviceIndex)

@@ -193,7 +193,15 @@ def should_join(sizes, target):
     return best
 
 
-class _Maintenance:
+class _IvfIndex:
+    """An index wrapper: `_ix` is the device index it speaks for."""
+
+    @property
+    def centroids(self):
+        return self._ix.centroids.cpu().numpy()
+
+
+class _Maintenance(_IvfIndex):
     """append / remap / delete of an index wrapper (lance_hip_index_merge / _remap): every call returns a NEW index and leaves this one
     as it is -- both are resident until the caller drops one.  By default append and remap take the reference's no-split / no-join
     branch of optimize_indices and remap (rust/lance/src/index/vector/ivf.rs:355-560, builder.rs:256-359); with rebalance=True they
@@ -425,6 +433,43 @@ def _adaptive_nearest(run, q, d, k, nlist, nprobes, minimum_nprobes, maximum_npr
     return ids.cpu().numpy(), dists.cpu().numpy()
 
 
+def _refined_nearest(name, ix, q, k, nprobes, prefilter, refine_factor, distance_range, minimum_nprobes, maximum_nprobes):
+    """`nearest` of the kinds that scan codes and re-rank on the raw column (name = "IVF_SQ" | "IVF_RQ") over the device index ix"""
+    if distance_range is not None:
+        raise NotImplementedError(f"{name}: distance_range is not supported by this engine")
+    if refine_factor is not None:
+        if refine_factor < 1:
+            raise ValueError("Refine factor can not be zero")
+        if ix._raw is None:
+            raise NotImplementedError(f"{name}: refine_factor needs the raw vectors (re-ranking scores the candidates against the column): attach them "
+                                      "with set_raw(x), or build with create_index(..., keep_raw=True)")
+
+        def run(qq, npb):
+            return ix.search(qq, k, npb, allow=prefilter, refine_factor=int(refine_factor))
+    else:
+        def run(qq, npb):
+            return ix.search(qq, k, npb) if prefilter is None else ix.search(qq, k, npb, allow=prefilter)
+    ids, dists = _adaptive_nearest(run, q, ix.centroids.shape[1], k, ix.centroids.shape[0], nprobes, minimum_nprobes, maximum_nprobes,
+                                   prefilter=prefilter, shortcut=refine_factor is None)
+    return ids.view(np.uint64), dists
+
+
+def _masked_part_ids(allow, part, row_ids=None):
+    """The partition ids `part` with -1 (LANCE_HIP_NONE: such rows are dropped by the create calls) for every row that `allow`
+    (bool over row ids) does not select.  row_ids: the id of each row, None = its position."""
+    allow_t = to_device(np.ascontiguousarray(allow, dtype=bool)) if not isinstance(allow, torch.Tensor) else allow.to(part.device)
+    ids = torch.arange(part.numel(), device=part.device) if row_ids is None else row_ids
+    inside = ids < allow_t.numel()
+    sel = torch.zeros_like(inside)
+    sel[inside] = allow_t[ids[inside]]
+    return torch.where(sel, part, torch.full_like(part, -1))
+
+
+def _element_type_name(ix):
+    """the `dtype` argument of DeviceIndex.create for the element type of ix's queries and raw vectors"""
+    return {torch.float16: "float16", torch.int8: "int8"}.get(ix.data_dtype, "float32")
+
+
 class IvfPqIndex(_Maintenance):
     """An IVF_PQ index resident in HBM with the reference's query semantics."""
     _index_type = "IVF_PQ"
@@ -435,10 +480,6 @@ class IvfPqIndex(_Maintenance):
         self.stats = stats
         self.part_ids = part_ids   # shuffle-buffer columns (device), kept for hand-off to Lance
         self.codes = codes
-
-    @property
-    def centroids(self):
-        return self._ix.centroids.cpu().numpy()
 
     @property
     def codebook(self):
@@ -459,8 +500,7 @@ class IvfPqIndex(_Maintenance):
     def _delta(self, x_new, row_ids):
         ix = self._ix
         part, codes = _transform_rows(ix.engine, "IVF_PQ", self.params.metric, x_new, ix.centroids, codebook=ix.codebook)
-        dtype = {torch.float16: "float16", torch.int8: "int8"}.get(ix.data_dtype, "float32")
-        return DeviceIndex.create(ix.engine, ix.metric, ix.centroids, ix.codebook, part, codes, row_ids, dtype=dtype)
+        return DeviceIndex.create(ix.engine, ix.metric, ix.centroids, ix.codebook, part, codes, row_ids, dtype=_element_type_name(ix))
 
     def shuffle_buffers(self):
         """(row_id u64, __ivf_part_id u32, __pq_code u8[M]) as numpy -- the artefact the reference's
@@ -492,11 +532,6 @@ class IvfPqIndex(_Maintenance):
         for prefilters that select at most k rows (the unfound selected rows come back at distance +inf) is reproduced for
         searches without a refine factor."""
         rf = 0 if refine_factor is None else refine_factor
-        nlist = self.params.num_partitions
-        min_np = nprobes if minimum_nprobes is None else minimum_nprobes
-        max_np = (min_np if minimum_nprobes is None else nlist) if maximum_nprobes is None else maximum_nprobes
-        max_np = max(min(max_np, nlist), min(min_np, nlist))
-        min_np = min(min_np, max_np)
 
         def run(qq, npb):
             if distance_range is not None:      # late_search extends range queries too (knn.rs:714-860)
@@ -506,34 +541,8 @@ class IvfPqIndex(_Maintenance):
                 return self._ix.search(qq, k, npb, rf)
             return self._ix.search_filtered(qq, k, npb, prefilter, rf)
 
-        ids, dists = run(q, min_np)
-        if max_np > min_np and prefilter is not None and not rf and distance_range is None:
-            # late_search's shortcut (knn.rs:741-779): when the prefilter selects no more than k rows, a query that has not
-            # found all of them yet gets the rest back with distance +inf instead of searching further partitions
-            allow_np = np.ascontiguousarray(prefilter.cpu().numpy() if isinstance(prefilter, torch.Tensor) else prefilter, dtype=bool)
-            mask_ids = np.flatnonzero(allow_np).astype(np.int64)
-            if mask_ids.size <= k:
-                ids_h, dists_h = ids.cpu().numpy().copy(), dists.cpu().numpy().copy()
-                for qi in range(ids_h.shape[0]):
-                    found = ids_h[qi][ids_h[qi] >= 0]
-                    if found.size < k and found.size < mask_ids.size:
-                        rest = np.setdiff1d(mask_ids, found)          # ascending row ids: SortExec's tie order at +inf
-                        ids_h[qi, found.size:found.size + rest.size] = rest
-                        dists_h[qi, found.size:found.size + rest.size] = np.inf
-                return ids_h, dists_h
-        if max_np > min_np:
-            qt = q if isinstance(q, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(q))
-            qt = qt.reshape(-1, self._ix.centroids.shape[1])
-            npb = min_np
-            while npb < max_np:
-                starved = torch.nonzero((ids < 0).any(dim=1)).reshape(-1)     # fewer than k rows found so far
-                if starved.numel() == 0:
-                    break
-                npb = min(max_np, max(npb * 2, npb + 1))
-                si, sd = run(qt[starved.cpu()] if not qt.is_cuda else qt[starved], npb)
-                ids[starved] = si
-                dists[starved] = sd
-        return ids.cpu().numpy(), dists.cpu().numpy()
+        return _adaptive_nearest(run, q, self._ix.centroids.shape[1], k, self.params.num_partitions, nprobes, minimum_nprobes,
+                                 maximum_nprobes, prefilter=prefilter, shortcut=(not rf and distance_range is None))
 
     def _storage_rows(self):
         """(part ids int32 [n], row-major codes u8 [n, code bytes], row ids int64 [n] | None) on the device, in an order
@@ -571,15 +580,9 @@ class IvfPqIndex(_Maintenance):
             # (lance_hip_ivfpq_search_filtered, search.hip pq4_masked_row): hand back a view that carries the mask into every search.
             return _MaskedIndexView(self, allow)
         part, codes, rid = self._storage_rows()
-        allow_t = to_device(np.ascontiguousarray(allow, dtype=bool)) if not isinstance(allow, torch.Tensor) else allow.to(part.device)
-        ids = torch.arange(part.numel(), device=part.device) if rid is None else rid
-        inside = ids < allow_t.numel()
-        sel = torch.zeros_like(inside)
-        sel[inside] = allow_t[ids[inside]]
-        masked = torch.where(sel, part, torch.full_like(part, -1))          # -1 = LANCE_HIP_NONE: dropped by index_create
+        masked = _masked_part_ids(allow, part, rid)
         ix = self._ix
-        dtype = {torch.float16: "float16", torch.int8: "int8"}.get(ix.data_dtype, "float32")
-        sub = DeviceIndex.create(ix.engine, ix.metric, ix.centroids, ix.codebook, masked, codes, rid, raw=ix._raw, dtype=dtype)
+        sub = DeviceIndex.create(ix.engine, ix.metric, ix.centroids, ix.codebook, masked, codes, rid, raw=ix._raw, dtype=_element_type_name(ix))
         return IvfPqIndex(sub, self.params, self.stats, masked, codes if rid is None else None)
 
     def search_device(self, q, k, nprobes, refine_factor=0, out=None, sync=True, engine=None):
@@ -610,10 +613,6 @@ class IvfFlatIndex(_Maintenance):
         self.params = params
         self.stats = stats
         self.part_ids = part_ids
-
-    @property
-    def centroids(self):
-        return self._ix.centroids.cpu().numpy()
 
     def _wrap(self, dev_index, rows_offered):
         out = IvfFlatIndex(dev_index, self.params, self.stats, None)
@@ -657,13 +656,7 @@ class IvfFlatIndex(_Maintenance):
         from .engine import DeviceFlatIndex
         if self.part_ids is None or getattr(self, "_x", None) is None:
             raise NotImplementedError("prefilter needs the index's vectors and partition ids (an index built by create_index)")
-        part = self.part_ids
-        allow_t = to_device(np.ascontiguousarray(allow, dtype=bool)) if not isinstance(allow, torch.Tensor) else allow.to(part.device)
-        ids = torch.arange(part.numel(), device=part.device)
-        inside = ids < allow_t.numel()
-        sel = torch.zeros_like(inside)
-        sel[inside] = allow_t[ids[inside]]
-        masked = torch.where(sel, part, torch.full_like(part, -1))
+        masked = _masked_part_ids(allow, self.part_ids)
         sub = DeviceFlatIndex.create(self._ix.engine, self._ix.metric, self._ix.centroids, self._x, masked)
         out = IvfFlatIndex(sub, self.params, self.stats, masked)
         out._x = self._x
@@ -684,10 +677,6 @@ class IvfSqIndex(_Maintenance):
         self.stats = stats
         self.part_ids = part_ids
         self._codes = codes
-
-    @property
-    def centroids(self):
-        return self._ix.centroids.cpu().numpy()
 
     @property
     def bounds(self):
@@ -712,24 +701,7 @@ class IvfSqIndex(_Maintenance):
         """prefilter: boolean array over row ids; the mask is tested inside the scan kernels (no copy of the index).
         minimum_nprobes / maximum_nprobes: adaptive probing, as IvfPqIndex.nearest (_adaptive_nearest); with a refine_factor a
         query counts as satisfied by what re-ranking leaves it, and the shortcut for prefilters of at most k rows does not apply."""
-        if distance_range is not None:
-            raise NotImplementedError("IVF_SQ: distance_range is not supported by this engine")
-        if refine_factor is not None:
-            if refine_factor < 1:
-                raise ValueError("Refine factor can not be zero")
-            if self._ix._raw is None:
-                raise NotImplementedError("IVF_SQ: refine_factor needs the raw vectors (re-ranking scores the candidates against the column): attach them "
-                                      "with set_raw(x), or build with create_index(..., keep_raw=True)")
-
-            def run(qq, npb):
-                return self._ix.search(qq, k, npb, allow=prefilter, refine_factor=int(refine_factor))
-        else:
-            def run(qq, npb):
-                return self._ix.search(qq, k, npb) if prefilter is None else self._ix.search(qq, k, npb, allow=prefilter)
-        cent = self._ix.centroids
-        ids, dists = _adaptive_nearest(run, q, cent.shape[1], k, cent.shape[0], nprobes, minimum_nprobes, maximum_nprobes,
-                                       prefilter=prefilter, shortcut=refine_factor is None)
-        return ids.view(np.uint64), dists
+        return _refined_nearest("IVF_SQ", self._ix, q, k, nprobes, prefilter, refine_factor, distance_range, minimum_nprobes, maximum_nprobes)
 
     def set_raw(self, raw):
         """attach the column (indexed by row id; the ORIGINAL rows) for nearest(..., refine_factor=)"""
@@ -741,13 +713,7 @@ class IvfSqIndex(_Maintenance):
         exactly as the prefilter branch of FlatIndex::search does (flat/index.rs:129-165)."""
         if self.part_ids is None or self._codes is None:
             raise NotImplementedError("prefilter needs the index's codes and partition ids (an index built by create_index with keep_raw)")
-        part = self.part_ids
-        allow_t = to_device(np.ascontiguousarray(allow, dtype=bool)) if not isinstance(allow, torch.Tensor) else allow.to(part.device)
-        ids = torch.arange(part.numel(), device=part.device)
-        inside = ids < allow_t.numel()
-        sel = torch.zeros_like(inside)
-        sel[inside] = allow_t[ids[inside]]
-        masked = torch.where(sel, part, torch.full_like(part, -1))
+        masked = _masked_part_ids(allow, self.part_ids)
         sub = DeviceSqIndex.create(self._ix.engine, self._ix.metric, self._ix.centroids, self._codes, masked, self._ix.bounds)
         return IvfSqIndex(sub, self.params, self.stats, masked, self._codes)
 
@@ -755,7 +721,7 @@ class IvfSqIndex(_Maintenance):
         raise NotImplementedError("IVF_SQ index files are not supported (IVF_PQ and IVF_FLAT are)")
 
 
-class IvfRqIndex:
+class IvfRqIndex(_IvfIndex):
     """IVF_RQ: IVF partitions over 1-bit RaBitQ codes (lance-index/src/vector/bq): d / 8 code bytes and two f32 factors per row, the
     residual rotated by a matrix that is part of the model.  Resident in HBM; nearest(refine_factor=) re-ranks k * refine_factor
     candidates (up to 768) on the raw vectors; no index files, distance ranges or maintenance (the reference's RabitQ storage has no
@@ -766,10 +732,6 @@ class IvfRqIndex:
         self.params = params
         self.stats = stats
         self.part_ids = part_ids
-
-    @property
-    def centroids(self):
-        return self._ix.centroids.cpu().numpy()
 
     @property
     def rotation(self):
@@ -785,24 +747,7 @@ class IvfRqIndex:
         distance (the reference's prefiltered FlatIndex::search never uses the quantised table).
         minimum_nprobes / maximum_nprobes: adaptive probing, as IvfPqIndex.nearest (_adaptive_nearest); with a refine_factor a
         query counts as satisfied by what re-ranking leaves it, and the shortcut for prefilters of at most k rows does not apply."""
-        if distance_range is not None:
-            raise NotImplementedError("IVF_RQ: distance_range is not supported by this engine")
-        if refine_factor is not None:
-            if refine_factor < 1:
-                raise ValueError("Refine factor can not be zero")
-            if self._ix._raw is None:
-                raise NotImplementedError("IVF_RQ: refine_factor needs the raw vectors (re-ranking scores the candidates against the column): attach them "
-                                      "with set_raw(x), or build with create_index(..., keep_raw=True)")
-
-            def run(qq, npb):
-                return self._ix.search(qq, k, npb, allow=prefilter, refine_factor=int(refine_factor))
-        else:
-            def run(qq, npb):
-                return self._ix.search(qq, k, npb) if prefilter is None else self._ix.search(qq, k, npb, allow=prefilter)
-        cent = self._ix.centroids
-        ids, dists = _adaptive_nearest(run, q, cent.shape[1], k, cent.shape[0], nprobes, minimum_nprobes, maximum_nprobes,
-                                       prefilter=prefilter, shortcut=refine_factor is None)
-        return ids.view(np.uint64), dists
+        return _refined_nearest("IVF_RQ", self._ix, q, k, nprobes, prefilter, refine_factor, distance_range, minimum_nprobes, maximum_nprobes)
 
     def set_raw(self, raw):
         """attach the column (indexed by row id; the ORIGINAL rows) for nearest(..., refine_factor=)"""
