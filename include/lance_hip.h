@@ -431,6 +431,17 @@ int lance_hip_search_stats(lance_hip_ctx *ctx, uint32_t *n_exact_replays_host);
 int lance_hip_flat_topk(lance_hip_ctx *ctx, int dtype, int metric, const void *x, const uint64_t *row_ids,
                         uint64_t n, uint32_t d, const void *q, uint32_t nq, uint32_t k, uint64_t *ids,
                         float *dists);
+/* The same scan under a distance range (Scanner::flat_knn's LanceFilterExec(_distance >= lower AND _distance < upper) between
+ * KNNVectorDistanceExec and SortExec.fetch(k), scanner.rs:3336-3412): the k smallest IN-RANGE rows, not the in-range part of the k
+ * smallest.  A row is in range iff lower <= d < upper in the TOTAL order on f32 (IEEE 754 totalOrder: -NaN < -inf < .. < -0 < +0 < ..
+ * < +inf < +NaN), d being the distance lance_hip_flat_topk returns for that (row, query), bit for bit.  has_lower / has_upper == 0:
+ * that bound is NOT TESTED (the value is ignored) -- unlike lance_hip_ivfflat_search_range, whose open ends are -FLT_MAX / FLT_MAX:
+ * (lower, none) keeps +inf and positive-NaN distances, (none, upper) keeps the negative NaN of an L2 row with a NaN element.
+ * lower above upper: LANCE_HIP_EINVAL; lower == upper: nothing.  Missing slots: id UINT64_MAX, distance +inf.  Same limits on k,
+ * dtypes and metrics as lance_hip_flat_topk, which is this entry with both bounds absent.                                        */
+int lance_hip_flat_topk_range(lance_hip_ctx *ctx, int dtype, int metric, const void *x, const uint64_t *row_ids,
+                              uint64_t n, uint32_t d, const void *q, uint32_t nq, uint32_t k, int has_lower, float lower,
+                              int has_upper, float upper, uint64_t *ids, float *dists);
 
 /* ---- flat KNN over a MULTIVECTOR column (Arrow List<FixedSizeList<T, d>>: one bag of vectors per row) ------------------
  * values  [offsets[n_rows]][d]: the flattened child array, LANCE_HIP_F32 or LANCE_HIP_F16 (int8 / uint8 columns: LANCE_HIP_EINVAL);
@@ -447,6 +458,11 @@ int lance_hip_multivec_distance(lance_hip_ctx *ctx, int dtype, int metric, const
 int lance_hip_flat_multivec_topk(lance_hip_ctx *ctx, int dtype, int metric, const void *values, const uint64_t *offsets,
                                  const uint64_t *row_ids, uint64_t n_rows, uint32_t d, const void *q, uint32_t nqv,
                                  uint32_t k, uint64_t *ids, float *dists);
+/* ... under a distance range: the semantics of lance_hip_flat_topk_range on the rows' multivector distances */
+int lance_hip_flat_multivec_topk_range(lance_hip_ctx *ctx, int dtype, int metric, const void *values, const uint64_t *offsets,
+                                       const uint64_t *row_ids, uint64_t n_rows, uint32_t d, const void *q, uint32_t nqv,
+                                       uint32_t k, int has_lower, float lower, int has_upper, float upper, uint64_t *ids,
+                                       float *dists);
 
 /* ---- multivector ANN: per-query-vector candidate lists joined by row id and scored with XTR-style imputation ----------
  * (Scanner::multivec_ann, scanner.rs:3471-3552; MultivectorScoringExec, knn.rs:1132-1329).  The index is an ordinary IVF_PQ index

@@ -11,6 +11,11 @@
 // (~k ln(n/k) per query).  Row ranges are split across workgroups; a merge kernel takes
 // the final (dist, rowid) order -- a total order, so the result equals the reference's
 // SortExec exactly, ties included.
+//
+// Distance ranges (lance_hip_flat_topk_range; Scanner::flat_knn's LanceFilterExec(_distance >= lower AND _distance < upper) between the
+// distance node and the sort, scanner.rs:3336-3412): the k smallest IN-RANGE rows, compared on the order keys (the total
+// order on f32).  Every route answers them -- flat_topk_impl dispatches exactly as the un-ranged call does: the upper bound is the
+// threshold the v2 routes start from, the lower bound the LOWER instantiation of their filters, the v1 kernels test both (RANGE).
 #include <algorithm>
 #include <cstdlib>
 
@@ -34,6 +39,7 @@ struct FlatArgs {
   int64_t rows_per_split;
   uint32_t *lkeys;  // [nsplit][nq][k]
   uint64_t *lrids;
+  uint32_t lo_key = 0, hi_last = 0xFFFFFFFFu;   // RANGE kernels: a row enters a list only when lo_key <= key <= hi_last (= hi_key - 1)
 };
 
 __device__ __forceinline__ void flat_insert(uint32_t *lk, uint64_t *lr, int k, int &cnt, uint32_t key, uint64_t rid,
@@ -52,7 +58,9 @@ __device__ __forceinline__ void flat_insert(uint32_t *lk, uint64_t *lr, int k, i
   if (cnt == k) { wkey = lk[k - 1]; wrid = lr[k - 1]; }
 }
 
-template <int D, int METRIC, int TR>
+// RANGE: a (row, query) cell outside the distance range is a row that is not there.  The `cnt < k` arm below inserts
+// whatever the key, so both bounds are tested on the key ahead of the insert; RANGE = false is the kernel from before ranges existed.
+template <int D, int METRIC, int TR, bool RANGE = false>
 __global__ __launch_bounds__(256) void flat_scan_kernel(FlatArgs p) {
   __shared__ __attribute__((aligned(16))) float tile[TR * D];
   __shared__ uint64_t trid[TR];
@@ -88,6 +96,9 @@ __global__ __launch_bounds__(256) void flat_scan_kernel(FlatArgs p) {
       for (int r = 0; r < tr; ++r) {
         const float v = finish_metric<METRIC>(dist_exact<D, METRIC, NEG>(a, &tile[r * D]));
         const uint32_t key = order_key(v);
+        if constexpr (RANGE) {
+          if (key < p.lo_key || key > p.hi_last) continue;
+        }
         if (key < wkey || cnt < p.k || (key == wkey && trid[r] < wrid)) flat_insert(lk, lr, p.k, cnt, key, trid[r], wkey, wrid);
       }
     }
@@ -99,7 +110,7 @@ __global__ __launch_bounds__(256) void flat_scan_kernel(FlatArgs p) {
 // generic dimension: query read through global/L1 per row (correctness fallback)
 // H32: f16 column (operands arrive widened) -- dot products / norms in the 32-lane order (dot.rs:91-102, norm_l2.rs:60-85) and
 // the scalar cosine of the Cosine trait default (cosine.rs:171-179)
-template <int METRIC, bool H32 = false>
+template <int METRIC, bool H32 = false, bool RANGE = false>
 __global__ __launch_bounds__(256) void flat_scan_generic_kernel(FlatArgs p, int tr_max) {
   extern __shared__ __attribute__((aligned(16))) char fsm[];
   uint64_t *trid = reinterpret_cast<uint64_t *>(fsm);
@@ -129,6 +140,9 @@ __global__ __launch_bounds__(256) void flat_scan_generic_kernel(FlatArgs p, int 
         if constexpr (METRIC == METRIC_COSINE) v = H32 ? cosine_scalar32_rt(qv, qnorm, &tile[r * p.d], p.d) : cosine_exact_rt(qv, qnorm, &tile[r * p.d], p.d);
         else v = finish_metric<METRIC>(dist_exact_rt<METRIC, float, (H32 && METRIC == METRIC_DOT) ? 32 : 16, METRIC == METRIC_L2>(qv, &tile[r * p.d], p.d));      // (L2: row - q, exact.cuh SWAP)
         const uint32_t key = order_key(v);
+        if constexpr (RANGE) {
+          if (key < p.lo_key || key > p.hi_last) continue;
+        }
         if (key < wkey || cnt < p.k || (key == wkey && trid[r] < wrid)) flat_insert(lk, lr, p.k, cnt, key, trid[r], wkey, wrid);
       }
     }
@@ -189,7 +203,14 @@ __global__ __launch_bounds__(256) void flat_merge_kernel(const uint32_t *__restr
 // (possible only for adversarial row orders) is detected and repaired by re-running the scan with the
 // tightened T, which strictly decreases each round.
 
-template <int D, int METRIC, int QT, int BS, typename TX>
+//
+// Distance ranges.  The UPPER bound is the threshold every query starts from: T = (hi_key - 1, ~0) instead of
+// (0xFFFFFFFF, ~0).  The select kernel tightens T only when the pool holds k rows, and the pool only ever holds rows at or under T, so
+// T is the k-th smallest pair of a subset of the IN-RANGE rows or the start value: never below the k-th in-range pair, and no kernel
+// changes for `upper`.  The LOWER bound is the template parameter LOWER of the filters: a cell whose key is below lo_key is not
+// appended -- a row that is not there -- so the pools hold in-range rows only and the argument above stands.
+
+template <int D, int METRIC, int QT, int BS, typename TX, bool LOWER = false>
 __global__ __launch_bounds__(BS) void flat_filter_kernel(FlatPool p) {
   __shared__ __attribute__((aligned(16))) float tile[QT * D];
   __shared__ uint32_t tk[QT];
@@ -228,6 +249,7 @@ __global__ __launch_bounds__(BS) void flat_filter_kernel(FlatPool p) {
       const uint32_t key = order_key(v);
       const uint32_t t = tk[c];
       bool pass = valid && key <= t;
+      if constexpr (LOWER) pass = pass && key >= p.lo_key;
       if (pass && key == t) pass = rid <= tr[c];
       const uint64_t m = __ballot(pass);
       if (m) {
@@ -295,11 +317,12 @@ __global__ __launch_bounds__(256) void flat_select_kernel(FlatPool p, int last, 
   }
 }
 
-__global__ void flat_pool_reset_kernel(FlatPool p, int reset_t) {
+// start_key: 0xFFFFFFFF, or hi_key - 1 under an upper bound (the largest key still in range)
+__global__ void flat_pool_reset_kernel(FlatPool p, int reset_t, uint32_t start_key) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < p.nq) {
     p.cnt[i] = 0;
-    if (reset_t) { p.tkey[i] = 0xFFFFFFFFu; p.trid[i] = ~0ull; }
+    if (reset_t) { p.tkey[i] = start_key; p.trid[i] = ~0ull; }
   }
   if (i == 0) *p.overflow = 0;
 }
@@ -357,7 +380,12 @@ static void launch_flat_filter(lance_hip_ctx *ctx, const FlatPool &a, int metric
   const dim3 grid(rblocks, 1, z);
   auto go = [&](auto tag) {
     using TX = decltype(tag);
-    if (metric == METRIC_DOT)
+    if (a.has_lower) {
+      if (metric == METRIC_DOT)
+        hipLaunchKernelGGL((flat_filter_kernel<D, METRIC_DOT, QT, BS, TX, true>), grid, dim3(BS), 0, ctx->stream, a);
+      else
+        hipLaunchKernelGGL((flat_filter_kernel<D, METRIC_L2, QT, BS, TX, true>), grid, dim3(BS), 0, ctx->stream, a);
+    } else if (metric == METRIC_DOT)
       hipLaunchKernelGGL((flat_filter_kernel<D, METRIC_DOT, QT, BS, TX>), grid, dim3(BS), 0, ctx->stream, a);
     else
       hipLaunchKernelGGL((flat_filter_kernel<D, METRIC_L2, QT, BS, TX>), grid, dim3(BS), 0, ctx->stream, a);
@@ -368,6 +396,9 @@ static void launch_flat_filter(lance_hip_ctx *ctx, const FlatPool &a, int metric
 }
 
 constexpr int FLAT_CAP = 4096;      // pool entries per query
+// LOWER on the matrix cores: how flat_topk_v2 sizes those epochs (tests/flat_range_spec.py: sized_schedule is the same rule)
+constexpr int64_t FLAT_LO_FIRST_ROWS = 2048;    // the first sized epoch: as many rows as a queue holds, so it cannot overflow one
+constexpr int64_t FLAT_LO_MIN_ROWS = 16384;     // an epoch shorter than this (more than one pair in sixteen undecided) is not worth queueing
 constexpr int FLAT_QCHUNK = 2048;   // queries per pass over the rows (pool = 2048 x 4096 x 12 B = 100 MB)
 
 static bool flat_fixed_dim(uint32_t d) { return d == 8 || d == 16 || d == 32 || d == 64 || d == 96 || d == 128; }
@@ -380,9 +411,10 @@ static bool flat_v2_supported(int metric, uint32_t d, uint32_t k) {
 
 // x: the rows as f32, or NULL when flat_reads_native() said the kernels take the column (x_native, x_dtype) as it is
 static int flat_topk_v2(lance_hip_ctx *ctx, int metric, const float *x, const void *x_native, int x_dtype, const uint64_t *row_ids, int64_t n,
-                        int d, const float *q, int nq, int k, uint64_t *ids, float *dists) {
+                        int d, const float *q, int nq, int k, const FlatRange &rg, uint64_t *ids, float *dists) {
   const int qch = std::min(nq, FLAT_QCHUNK);
   FlatPool a;
+  a.has_lower = rg.has_lower ? 1 : 0; a.lo_key = rg.has_lower ? rg.lo_key : 0u;
   a.x = x; a.x_native = x ? static_cast<const void *>(x) : x_native; a.x_dtype = x ? LANCE_HIP_F32 : x_dtype;
   a.row_ids = row_ids; a.k = k; a.cap = FLAT_CAP;
   a.tkey = ctx->scratch_t<uint32_t>("flat2.tkey", qch);
@@ -392,6 +424,10 @@ static int flat_topk_v2(lance_hip_ctx *ctx, int metric, const float *x, const vo
   a.prids = ctx->scratch_t<uint64_t>("flat2.prids", (size_t)qch * FLAT_CAP);
   a.overflow = ctx->scratch_t<uint32_t>("flat2.ovf", 1);
   if (!a.tkey || !a.trid || !a.cnt || !a.pkeys || !a.prids || !a.overflow) return LANCE_HIP_ENOMEM;
+  if (a.has_lower) {
+    a.qfill = ctx->scratch_t<uint32_t>("flat2.qfill", 1);
+    if (!a.qfill) return LANCE_HIP_ENOMEM;
+  }
   const int64_t growth = std::max<int64_t>(2, FLAT_CAP / (16 * (int64_t)k));
   const bool fixed = metric != LANCE_HIP_COSINE && flat_fixed_dim((uint32_t)d) &&
                      (((reinterpret_cast<uintptr_t>(a.x_native) | reinterpret_cast<uintptr_t>(q)) & 15) == 0);
@@ -446,7 +482,7 @@ static int flat_topk_v2(lance_hip_ctx *ctx, int metric, const float *x, const vo
     a.nq = std::min(qch, nq - qc0);
     uint64_t *oid = ids + (int64_t)qc0 * k;
     float *od = dists + (int64_t)qc0 * k;
-    hipLaunchKernelGGL(flat_pool_reset_kernel, dim3(cdiv(a.nq, 256)), dim3(256), 0, ctx->stream, a, 1);
+    hipLaunchKernelGGL(flat_pool_reset_kernel, dim3(cdiv(a.nq, 256)), dim3(256), 0, ctx->stream, a, 1, rg.start_key());      // (every chunk starts from the bound)
     // query batches: after the first epoch (which gives every query a threshold) the epochs run on the matrix cores
     const bool use_mfma = fixed && flat_mfma_supported(metric, d, a.nq, a.x_native, a.q);
     const uint16_t *qhi = nullptr, *qlo = nullptr;
@@ -457,6 +493,13 @@ static int flat_topk_v2(lance_hip_ctx *ctx, int metric, const float *x, const vo
     const float *wqn2 = nullptr;
     if (use_wide) LH_TRY(flat_mfma_wide_prepare_queries(ctx, a.q, a.nq, d, &wqb, &wqn2));
     int64_t seen = 0;
+    // LOWER on the matrix cores.  The surrogate cannot decide the pairs within its guard band of `lower`: they are queued
+    // and dropped by the exact evaluation, and unlike the pairs under T their number per epoch grows with the epoch, not with k.  So
+    // these epochs are sized by what the queues took: the first one is short, every one leaves its fullest queue's count in qfill, and
+    // the next is as long as fills the queues by half.  A band so dense that an epoch would fall under 16,384 rows (about one row in
+    // sixteen undecided) is not worth queueing pair by pair: the rest of the chunk goes to the exact filter in its usual epochs.
+    bool mc_mfma = use_mfma, mc_wide = use_wide;
+    int64_t lo_rows = FLAT_LO_FIRST_ROWS;
     if (n == 0) {
       a.r0 = a.r1 = 0;
       hipLaunchKernelGGL(flat_select_kernel, dim3(a.nq), dim3(256), sel_lds, ctx->stream, a, 1, oid, od);
@@ -466,14 +509,30 @@ static int flat_topk_v2(lance_hip_ctx *ctx, int metric, const float *x, const vo
       a.r0 = seen;
       a.r1 = std::min<int64_t>(n, seen + std::max<int64_t>(want, 1));
       if (n - a.r1 < (a.r1 - a.r0) / 4) a.r1 = n;            // do not leave a small tail epoch
+      const bool sized = a.has_lower && (mc_mfma || mc_wide) && seen > 0 && seen >= k;
+      if (sized) {
+        if (a.r1 - a.r0 > lo_rows) a.r1 = a.r0 + lo_rows;
+        LH_CHECK_HIP(lh::memset_async(a.qfill, 0, 4, ctx->stream));
+      }
       {
         ScopedTimer t(ctx, "flat_scan");
-        if (use_mfma && seen > 0 && seen >= k) LH_TRY(launch_flat_filter_mfma(ctx, a, d, metric, qhi, qlo, qn2));
-        else if (use_wide && seen > 0 && seen >= k) LH_TRY(launch_flat_filter_mfma_wide(ctx, a, d, metric, wxb, wxn2, wqb, wqn2));
+        if (mc_mfma && seen > 0 && seen >= k) LH_TRY(launch_flat_filter_mfma(ctx, a, d, metric, qhi, qlo, qn2));
+        else if (mc_wide && seen > 0 && seen >= k) LH_TRY(launch_flat_filter_mfma_wide(ctx, a, d, metric, wxb, wxn2, wqb, wqn2));
         else filter(a);
       }
       seen = a.r1;
       hipLaunchKernelGGL(flat_select_kernel, dim3(a.nq), dim3(256), sel_lds, ctx->stream, a, seen == n ? 1 : 0, oid, od);
+      if (sized && seen < n) {
+        uint32_t fill = 0;
+        LH_CHECK_HIP(hipMemcpyAsync(&fill, a.qfill, 4, hipMemcpyDeviceToHost, ctx->stream));
+        LH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+        const int64_t next = (a.r1 - a.r0) * (FLAT_MC_QUEUE_CAP / 2) / std::max<int64_t>(fill, 1);
+        if (next < FLAT_LO_MIN_ROWS) {
+          mc_mfma = mc_wide = false;
+          ctx->count_stage("flat_lower_fallback");      // tests assert that the matrix cores, not this, answered their fixtures
+        }
+        else lo_rows = std::min<int64_t>(next, (int64_t)1 << 24);
+      }
     }
     // overflow repair: rows <= T (T only ever tightens) are re-collected from scratch until every pool fits
     for (int round = 0; round < 64; ++round) {
@@ -482,7 +541,8 @@ static int flat_topk_v2(lance_hip_ctx *ctx, int metric, const float *x, const vo
       LH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
       if (!ovf) break;
       LH_REQUIRE(round < 63, "flat_topk: candidate pool did not converge");
-      hipLaunchKernelGGL(flat_pool_reset_kernel, dim3(cdiv(a.nq, 256)), dim3(256), 0, ctx->stream, a, 0);
+      ctx->count_stage("flat_repair");      // tests and scripts/flat_range_probe.py assert that a shape did NOT come here
+      hipLaunchKernelGGL(flat_pool_reset_kernel, dim3(cdiv(a.nq, 256)), dim3(256), 0, ctx->stream, a, 0, 0xFFFFFFFFu);
       a.r0 = 0; a.r1 = n;
       filter(a);
       hipLaunchKernelGGL(flat_select_kernel, dim3(a.nq), dim3(256), sel_lds, ctx->stream, a, 1, oid, od);
@@ -493,9 +553,14 @@ static int flat_topk_v2(lance_hip_ctx *ctx, int metric, const float *x, const vo
 }
 
 template <int D>
-static void launch_flat_fixed(lance_hip_ctx *ctx, const FlatArgs &a, int metric, dim3 grid) {
+static void launch_flat_fixed(lance_hip_ctx *ctx, const FlatArgs &a, int metric, dim3 grid, bool ranged) {
   constexpr int TR = (8192 / D) > 256 ? 256 : (8192 / D);
-  if (metric == METRIC_DOT)
+  if (ranged) {
+    if (metric == METRIC_DOT)
+      hipLaunchKernelGGL((flat_scan_kernel<D, METRIC_DOT, TR, true>), grid, dim3(256), 0, ctx->stream, a);
+    else
+      hipLaunchKernelGGL((flat_scan_kernel<D, METRIC_L2, TR, true>), grid, dim3(256), 0, ctx->stream, a);
+  } else if (metric == METRIC_DOT)
     hipLaunchKernelGGL((flat_scan_kernel<D, METRIC_DOT, TR>), grid, dim3(256), 0, ctx->stream, a);
   else
     hipLaunchKernelGGL((flat_scan_kernel<D, METRIC_L2, TR>), grid, dim3(256), 0, ctx->stream, a);
@@ -940,13 +1005,6 @@ static void launch_ivfflat_exact(lance_hip_ctx *ctx, const IvfFlatArgs &a, int m
   else hipLaunchKernelGGL((ivfflat_exact_kernel<METRIC_L2, false, RANGE>), dim3(nqc), dim3(64), lds, ctx->stream, a, oid, od);
 }
 
-// f32::total_cmp order key of a bound on the host: exact.cuh order_key, whose __float_as_uint is device code
-static uint32_t host_order_key(float f) {
-  uint32_t b;
-  memcpy(&b, &f, 4);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
 }  // namespace lh
 
 using namespace lh;
@@ -1139,7 +1197,7 @@ static int ivfflat_search_impl(lance_hip_ctx *ctx, const lance_hip_index *idx, c
     pl.q = a.q; pl.nq = nqc;
     uint64_t *oid = ids + (int64_t)qc0 * k;
     float *od = dists + (int64_t)qc0 * k;
-    hipLaunchKernelGGL(flat_pool_reset_kernel, dim3(cdiv(nqc, 256)), dim3(256), 0, ctx->stream, pl, 1);
+    hipLaunchKernelGGL(flat_pool_reset_kernel, dim3(cdiv(nqc, 256)), dim3(256), 0, ctx->stream, pl, 1, 0xFFFFFFFFu);
     grouped = false;
     if (big_k) {     // every query flagged: the exact kernel answers all of them
       hipLaunchKernelGGL(ivfflat_flag_all_kernel, dim3(cdiv(nqc, 256)), dim3(256), 0, ctx->stream, nqc, a.flags);
@@ -1160,7 +1218,7 @@ static int ivfflat_search_impl(lance_hip_ctx *ctx, const lance_hip_index *idx, c
         finish(nqc, oid, od, false);
         break;
       }
-      hipLaunchKernelGGL(flat_pool_reset_kernel, dim3(cdiv(nqc, 256)), dim3(256), 0, ctx->stream, pl, 0);
+      hipLaunchKernelGGL(flat_pool_reset_kernel, dim3(cdiv(nqc, 256)), dim3(256), 0, ctx->stream, pl, 0, 0xFFFFFFFFu);
       scan(0, nqc);
       finish(nqc, oid, od);
     }
@@ -1200,16 +1258,31 @@ extern "C" int lance_hip_ivfflat_search_range(lance_hip_ctx *ctx, const lance_hi
   return ivfflat_search_impl(ctx, idx, q, nq, k, nprobes, bits, true, lower, upper, ids, dists);
 }
 
-extern "C" int lance_hip_flat_topk(lance_hip_ctx *ctx, int dtype, int metric, const void *x, const uint64_t *row_ids,
-                                   uint64_t n, uint32_t d, const void *q, uint32_t nq, uint32_t k, uint64_t *ids,
-                                   float *dists) {
-  lh::CtxLock _ctx_lock(ctx);
-  LH_REQUIRE(ctx && (n == 0 || x) && (nq == 0 || (q && ids && dists)), "flat_topk: NULL argument");
-  LH_TRY(check_dtype(dtype, "flat_topk"));
-  LH_REQUIRE(metric == LANCE_HIP_L2 || metric == LANCE_HIP_DOT || metric == LANCE_HIP_COSINE, "flat_topk: bad metric %d", metric);
-  LH_REQUIRE(k > 0 && k <= 1024, "flat_topk: k=%u not supported (1..1024)", k);
+// an empty answer: every slot id ~0, distance +inf (the fill of flat_select_kernel / flat_merge_kernel)
+__global__ void flat_fill_empty_kernel(uint64_t *__restrict__ ids, float *__restrict__ dists, int64_t count) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (int64_t)gridDim.x * 256) { ids[i] = ~0ull; dists[i] = INFINITY; }
+}
+
+// lance_hip_flat_topk and lance_hip_flat_topk_range: one implementation, every route answers a range.  `what` names the
+// entry in error messages; an un-ranged call (rg.any() == false) launches the kernels it launched before ranges existed.
+static int flat_topk_impl(const char *what, lance_hip_ctx *ctx, int dtype, int metric, const void *x, const uint64_t *row_ids, uint64_t n,
+                          uint32_t d, const void *q, uint32_t nq, uint32_t k, const lh::FlatRange &rg, uint64_t *ids, float *dists) {
+  LH_REQUIRE(ctx && (n == 0 || x) && (nq == 0 || (q && ids && dists)), "%s: NULL argument", what);
+  LH_TRY(check_dtype(dtype, what));
+  LH_REQUIRE(metric == LANCE_HIP_L2 || metric == LANCE_HIP_DOT || metric == LANCE_HIP_COSINE, "%s: bad metric %d", what, metric);
+  LH_REQUIRE(k > 0 && k <= 1024, "%s: k=%u not supported (1..1024)", what, k);
+  // lower == upper is legal and selects nothing (lower <= d && d < upper); the comparison is the total order on f32 (order keys)
+  LH_REQUIRE(!(rg.has_lower && rg.has_upper) || rg.lo_key <= rg.hi_key, "%s: lower bound %g is above the upper bound %g", what,
+             (double)key_to_float_host(rg.lo_key), (double)key_to_float_host(rg.hi_key));
   LH_CHECK_HIP(hipSetDevice(ctx->device));
   if (nq == 0) return LANCE_HIP_OK;
+  if (rg.empty()) {      // nothing lies in [lower, upper): no scan
+    const int64_t cnt = (int64_t)nq * k;
+    hipLaunchKernelGGL(flat_fill_empty_kernel, dim3((unsigned)std::min<int64_t>(cdiv((uint64_t)cnt, 256), 1024)), dim3(256), 0, ctx->stream, ids, dists, cnt);
+    LH_CHECK_HIP(hipGetLastError());
+    LH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    return LANCE_HIP_OK;
+  }
   // f16 columns under dot / cosine: half::f16's own distance functions (32-lane dot_scalar / norm_l2_impl, scalar cosine;
   // dot.rs:91-102, norm_l2.rs:60-85, cosine.rs:171-179) -- the run-time-dimension kernel below carries those orders
   const bool h32 = dtype == LANCE_HIP_F16 && metric != LANCE_HIP_L2;
@@ -1217,7 +1290,7 @@ extern "C" int lance_hip_flat_topk(lance_hip_ctx *ctx, int dtype, int metric, co
     const float *qs2;
     LH_TRY(as_f32(ctx, dtype, q, (size_t)nq * d, "f16.q", &qs2));
     bool done = false;
-    LH_TRY(flat_topk_small(ctx, metric, dtype, x, row_ids, n, d, qs2, nq, k, ids, dists, &done));
+    LH_TRY(flat_topk_small(ctx, metric, dtype, x, row_ids, n, d, qs2, nq, k, rg, ids, dists, &done));
     if (done) return LANCE_HIP_OK;
   }
   if (!h32 && flat_v2_supported(metric, d, k) && !getenv("LANCE_HIP_FLAT_V1")) {
@@ -1229,7 +1302,7 @@ extern "C" int lance_hip_flat_topk(lance_hip_ctx *ctx, int dtype, int metric, co
     const bool native = dtype != LANCE_HIP_F32 && metric != LANCE_HIP_COSINE && flat_fixed_dim(d) && ((size_t)d * esz) % 16 == 0 &&
                         ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(qf2)) & 15) == 0 && !getenv("LANCE_HIP_NO_NATIVE_FLAT");
     if (!native) LH_TRY(as_f32(ctx, dtype, x, (size_t)n * d, "f16.x", &xf2));
-    return flat_topk_v2(ctx, metric, xf2, x, dtype, row_ids, (int64_t)n, (int)d, qf2, (int)nq, (int)k, ids, dists);
+    return flat_topk_v2(ctx, metric, xf2, x, dtype, row_ids, (int64_t)n, (int)d, qf2, (int)nq, (int)k, rg, ids, dists);
   }
   const int qblocks = (int)cdiv(nq, 256);
   int nsplit = (int)cdiv(2ull * ctx->num_cus, qblocks);
@@ -1242,6 +1315,9 @@ extern "C" int lance_hip_flat_topk(lance_hip_ctx *ctx, int dtype, int metric, co
   a.x = xf; a.row_ids = row_ids; a.n = (int64_t)n; a.d = (int)d;
   a.q = qf; a.nq = (int)nq; a.k = (int)k; a.nsplit = nsplit;
   a.rows_per_split = (int64_t)cdiv(n > 0 ? n : 1, nsplit);
+  const bool ranged = rg.any();
+  if (rg.has_lower) a.lo_key = rg.lo_key;
+  a.hi_last = rg.start_key();
   a.lkeys = ctx->scratch_t<uint32_t>("flat.lkeys", (size_t)nsplit * nq * k);
   a.lrids = ctx->scratch_t<uint64_t>("flat.lrids", (size_t)nsplit * nq * k);
   if (!a.lkeys || !a.lrids) return LANCE_HIP_ENOMEM;
@@ -1249,18 +1325,29 @@ extern "C" int lance_hip_flat_topk(lance_hip_ctx *ctx, int dtype, int metric, co
   {
     ScopedTimer t(ctx, "flat_scan");
     switch ((metric == LANCE_HIP_COSINE || h32) ? 0u : d) {
-      case 8: launch_flat_fixed<8>(ctx, a, metric, grid); break;
-      case 16: launch_flat_fixed<16>(ctx, a, metric, grid); break;
-      case 32: launch_flat_fixed<32>(ctx, a, metric, grid); break;
-      case 64: launch_flat_fixed<64>(ctx, a, metric, grid); break;
-      case 96: launch_flat_fixed<96>(ctx, a, metric, grid); break;
-      case 128: launch_flat_fixed<128>(ctx, a, metric, grid); break;
+      case 8: launch_flat_fixed<8>(ctx, a, metric, grid, ranged); break;
+      case 16: launch_flat_fixed<16>(ctx, a, metric, grid, ranged); break;
+      case 32: launch_flat_fixed<32>(ctx, a, metric, grid, ranged); break;
+      case 64: launch_flat_fixed<64>(ctx, a, metric, grid, ranged); break;
+      case 96: launch_flat_fixed<96>(ctx, a, metric, grid, ranged); break;
+      case 128: launch_flat_fixed<128>(ctx, a, metric, grid, ranged); break;
       default: {
         int tr = (int)(8192 / d);
         tr = std::max(1, std::min(tr, 256));
         const size_t lds = (size_t)tr * 8 + (size_t)tr * d * 4;
         LH_REQUIRE(lds <= 160 * 1024, "flat_topk: dimension %u too large", d);
-        if (h32 && metric == LANCE_HIP_COSINE)
+        if (ranged) {
+          if (h32 && metric == LANCE_HIP_COSINE)
+            hipLaunchKernelGGL((flat_scan_generic_kernel<METRIC_COSINE, true, true>), grid, dim3(256), lds, ctx->stream, a, tr);
+          else if (h32)
+            hipLaunchKernelGGL((flat_scan_generic_kernel<METRIC_DOT, true, true>), grid, dim3(256), lds, ctx->stream, a, tr);
+          else if (metric == LANCE_HIP_COSINE)
+            hipLaunchKernelGGL((flat_scan_generic_kernel<METRIC_COSINE, false, true>), grid, dim3(256), lds, ctx->stream, a, tr);
+          else if (metric == LANCE_HIP_DOT)
+            hipLaunchKernelGGL((flat_scan_generic_kernel<METRIC_DOT, false, true>), grid, dim3(256), lds, ctx->stream, a, tr);
+          else
+            hipLaunchKernelGGL((flat_scan_generic_kernel<METRIC_L2, false, true>), grid, dim3(256), lds, ctx->stream, a, tr);
+        } else if (h32 && metric == LANCE_HIP_COSINE)
           hipLaunchKernelGGL((flat_scan_generic_kernel<METRIC_COSINE, true>), grid, dim3(256), lds, ctx->stream, a, tr);
         else if (h32)
           hipLaunchKernelGGL((flat_scan_generic_kernel<METRIC_DOT, true>), grid, dim3(256), lds, ctx->stream, a, tr);
@@ -1280,4 +1367,19 @@ extern "C" int lance_hip_flat_topk(lance_hip_ctx *ctx, int dtype, int metric, co
   LH_CHECK_HIP(hipGetLastError());
   LH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
   return LANCE_HIP_OK;
+}
+
+extern "C" int lance_hip_flat_topk(lance_hip_ctx *ctx, int dtype, int metric, const void *x, const uint64_t *row_ids,
+                                   uint64_t n, uint32_t d, const void *q, uint32_t nq, uint32_t k, uint64_t *ids,
+                                   float *dists) {
+  lh::CtxLock _ctx_lock(ctx);
+  return flat_topk_impl("flat_topk", ctx, dtype, metric, x, row_ids, n, d, q, nq, k, lh::FlatRange{}, ids, dists);
+}
+
+extern "C" int lance_hip_flat_topk_range(lance_hip_ctx *ctx, int dtype, int metric, const void *x, const uint64_t *row_ids,
+                                         uint64_t n, uint32_t d, const void *q, uint32_t nq, uint32_t k, int has_lower, float lower,
+                                         int has_upper, float upper, uint64_t *ids, float *dists) {
+  lh::CtxLock _ctx_lock(ctx);
+  return flat_topk_impl("flat_topk_range", ctx, dtype, metric, x, row_ids, n, d, q, nq, k, lh::flat_range(has_lower, lower, has_upper, upper),
+                        ids, dists);
 }

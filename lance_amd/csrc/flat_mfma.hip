@@ -20,6 +20,17 @@
 // queued rows exactly (one lane per row, all lanes busy) and appends to the pool under the exact (key, rowid) test -- the inline
 // version ran a 128-dimension exact distance with two dependent global loads on one active lane while the wave's MFMA stream
 // stood still.  A queue that overflows raises the pool-overflow flag: the caller's repair loop rescans with the exact kernels.
+//
+// Distance ranges.  The upper bound needs nothing here: it is the threshold the queries start from.  With a LOWER bound
+// (template parameter LOWER) the one-sided test would queue every row nearer than `lower` -- about half the column per query when the
+// bound sits at the median, against a queue of FM_SQ_CAP -- only for the exact evaluation to drop it, the queues would overflow and
+// the repair loop would rescan with the exact kernel.  So the filter gets the mirrored reject with the same guard band: the surrogate
+// is within E of the exact distance, hence a pair with s + E < lower has d < lower and is not queued.  In the fast-reject form the
+// pair's quantity becomes max(s_up, s_lo) with s_lo = -(s + E - lower) = fma(-mul, x.q, lq - xlo) (xlo = |x|^2 (1 + 2^-12), dot:
+// 1 + 2^-12 |x|^2; lq = lower - |q|^2 (1 + 2^-12), dot: lower - 2^-12 |q|^2 - 2^-22, staged beside tq): one more packed fma per two
+// pairs and one v_max per pair, still one running minimum per lane and no branch unless a pair can pass BOTH sides.  A lower bound
+// that is not finite rejects nothing here (lq = -inf).  Rows and queries outside the margin's validity (odd / tiny / qodd) are queued
+// as before; flat_mfma_eval_kernel applies lo_key to every queued pair.  LOWER = false is the kernel from before ranges existed.
 #include <algorithm>
 #include <cstdlib>
 
@@ -71,7 +82,7 @@ struct FmArgs {
   uint32_t *squeue;            // [nq][FM_SQ_CAP] row numbers whose surrogate distance passed
 };
 
-constexpr int FM_SQ_CAP = 2048;
+constexpr int FM_SQ_CAP = FLAT_MC_QUEUE_CAP;
 // The margin E = 2^-12 (|x|^2 + |q|^2) is a RELATIVE bound: it holds while no square, product or sum sits in the denormal range and
 // nothing overflows.  As in mfma_assign.hip / xform_fused.hip / pq_mfma.hip a pair whose E is not above 2^-100 is not filtered at all
 // (E <= 2^-100 needs both 2^-12 |x|^2 and 2^-12 |q|^2 <= 2^-100: that is what is tested), nor is one whose |x|^2 or |q|^2 is not below
@@ -79,7 +90,7 @@ constexpr int FM_SQ_CAP = 2048;
 constexpr float FM_E_TINY = 7.888609052210118e-31f;      // 2^-100
 constexpr float FM_NORM_HUGE = 8.507059173023462e37f;    // 2^126
 
-template <int KS, int METRIC, typename TX>
+template <int KS, int METRIC, typename TX, bool LOWER = false>
 __global__ __launch_bounds__(256, LH_FM_WAVES) void flat_filter_mfma_kernel(FmArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const FlatPool &p = a.p;
@@ -90,6 +101,7 @@ __global__ __launch_bounds__(256, LH_FM_WAVES) void flat_filter_mfma_kernel(FmAr
   float *tqs = reinterpret_cast<float *>(smem + (size_t)2 * 2 * FM_QT * CS * 2);   // [2][FM_QT] threshold + query part of E
   float *qns = tqs + 2 * FM_QT;                                                     // [2][FM_QT] |q|^2
   uint32_t *qodd = reinterpret_cast<uint32_t *>(qns + 2 * FM_QT);                   // [2] the tile holds a query whose |q|^2 is not below 2^126
+  float *lqs = reinterpret_cast<float *>(qodd + 4);                                 // [2][FM_QT] LOWER: lower bound + query part of E (the launcher adds the bytes)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int j = lane & 31, g = lane >> 5;
   const int64_t row0 = p.r0 + (int64_t)blockIdx.x * FM_ROWS;
@@ -122,6 +134,8 @@ __global__ __launch_bounds__(256, LH_FM_WAVES) void flat_filter_mfma_kernel(FmAr
   const bool rvalid = row < p.r1;
   // per-lane constant of the test  s - E <= T  <=>  (|q|^2 (1 - 2^-12) + T)'s partner: xk = |x|^2 (1 - 2^-12)
   const float xk = METRIC == METRIC_DOT ? -0.000244140625f * xn2 : xn2 - 0.000244140625f * xn2;
+  // ... and of the mirrored test  s + E >= lower: xlo = |x|^2 (1 + 2^-12)   (dot: 1 + 2^-12 |x|^2)
+  [[maybe_unused]] const float xlo = METRIC == METRIC_DOT ? 1.0f + 0.000244140625f * xn2 : xn2 + 0.000244140625f * xn2;
 
   // rows outside the range where the margin holds (see FM_E_TINY): odd -- every query takes the row; tiny -- every query whose own
   // 2^-12 |q|^2 is not above 2^-100 takes it, the others keep the filter (their |q|^2 carries the margin)
@@ -132,7 +146,7 @@ __global__ __launch_bounds__(256, LH_FM_WAVES) void flat_filter_mfma_kernel(FmAr
   constexpr int NCH = FM_QT * D / 8;
   constexpr int CH = (NCH + 255) / 256;
   uint4 ph[CH], pl[CH];
-  float ptq = 0.0f, pqn = 0.0f;
+  float ptq = 0.0f, pqn = 0.0f, plq = 0.0f;
   auto fetch = [&](int t) {
     const int q0 = t * FM_QT;
 #pragma unroll
@@ -147,7 +161,7 @@ __global__ __launch_bounds__(256, LH_FM_WAVES) void flat_filter_mfma_kernel(FmAr
     }
     if (threadIdx.x < FM_QT) {
       const int qi = q0 + threadIdx.x;
-      ptq = -INFINITY; pqn = 0.0f;
+      ptq = -INFINITY; pqn = 0.0f; plq = -INFINITY;
       if (qi < p.nq) {
         const uint32_t tk = p.tkey[qi];
         const float qn = a.qn[qi];
@@ -158,6 +172,14 @@ __global__ __launch_bounds__(256, LH_FM_WAVES) void flat_filter_mfma_kernel(FmAr
         // |q|^2 at the top of the range or a NaN (T - |q|^2 is a NaN once it overflowed, xk + |q|^2 may overflow below it, the
         // products may be inf - inf): every row passes, through the slow path (qodd)
         if (!(qn < FM_NORM_HUGE)) ptq = INFINITY;
+        if constexpr (LOWER) {
+          // s_lo = lq - xlo + mul x.q > 0  <=>  s + E < lower.  Only a finite bound rejects here; padded queries keep lq = -inf (their
+          // tq = -inf already fails them), a query outside the margin's range is passed by `special`
+          const float lower = key_to_float(p.lo_key);
+          plq = -INFINITY;
+          if (fabsf(lower) < INFINITY && qn < FM_NORM_HUGE)
+            plq = METRIC == METRIC_DOT ? lower - 0.000244140625f * qn - 4.7683716e-7f : lower - (qn + 0.000244140625f * qn);
+        }
       }
     }
   };
@@ -174,6 +196,7 @@ __global__ __launch_bounds__(256, LH_FM_WAVES) void flat_filter_mfma_kernel(FmAr
     }
     if (threadIdx.x < FM_QT) {      // (wave 0, whole)
       tqs[buf * FM_QT + threadIdx.x] = ptq; qns[buf * FM_QT + threadIdx.x] = pqn;
+      if constexpr (LOWER) lqs[buf * FM_QT + threadIdx.x] = plq;
       const bool any_odd = __any(!(pqn < FM_NORM_HUGE));
       if (threadIdx.x == 0) qodd[buf] = any_odd ? 1u : 0u;
     }
@@ -208,11 +231,14 @@ __global__ __launch_bounds__(256, LH_FM_WAVES) void flat_filter_mfma_kernel(FmAr
     }
     const int q0 = t * FM_QT;
     const float *tqb = tqs + buf * FM_QT, *qnb = qns + buf * FM_QT;
+    [[maybe_unused]] const float *lqb = lqs + buf * FM_QT;
     // fast reject: minimum over the lane's 32 pairs of  s = xk - 2 x.q - tq'  (dot: xk + 1 - x.q - tq'), two pairs per packed op.
     // A NaN s is ignored by the minimum and fails `<=` in the slow path alike (as `sp <= tq` did).
     const f2 mul2 = METRIC == METRIC_DOT ? f2{-1.0f, -1.0f} : f2{-2.0f, -2.0f};
     const float xk1 = METRIC == METRIC_DOT ? 1.0f + xk : xk;
     const f2 xk2 = {xk1, xk1};
+    [[maybe_unused]] const f2 mul2n = -mul2;
+    [[maybe_unused]] const f2 xlo2 = {xlo, xlo};
     float mn = INFINITY;
 #pragma unroll
     for (int blk = 0; blk < 2; ++blk) {
@@ -224,8 +250,18 @@ __global__ __launch_bounds__(256, LH_FM_WAVES) void flat_filter_mfma_kernel(FmAr
         const f2 d23 = blk ? f2{acc1[vq * 4 + 2], acc1[vq * 4 + 3]} : f2{acc0[vq * 4 + 2], acc0[vq * 4 + 3]};
         const f2 s01 = __builtin_elementwise_fma(mul2, d01, xk2 - f2{tq4.x, tq4.y});
         const f2 s23 = __builtin_elementwise_fma(mul2, d23, xk2 - f2{tq4.z, tq4.w});
+        if constexpr (LOWER) {
+          // both sides folded: a pair can pass only if max(s_up, s_lo) <= 0.  fmaxf drops a NaN operand, which only widens the branch
+          // condition; the walk below tests each side on its own
+          const f4 lq4 = *reinterpret_cast<const f4 *>(lqb + ib);
+          const f2 l01 = __builtin_elementwise_fma(mul2n, d01, f2{lq4.x, lq4.y} - xlo2);
+          const f2 l23 = __builtin_elementwise_fma(mul2n, d23, f2{lq4.z, lq4.w} - xlo2);
+          mn = __builtin_fminf(mn, __builtin_fminf(__builtin_fmaxf(s01.x, l01.x), __builtin_fmaxf(s01.y, l01.y)));
+          mn = __builtin_fminf(mn, __builtin_fminf(__builtin_fmaxf(s23.x, l23.x), __builtin_fmaxf(s23.y, l23.y)));
+        } else {
         mn = __builtin_fminf(mn, __builtin_fminf(s01.x, s01.y));
         mn = __builtin_fminf(mn, __builtin_fminf(s23.x, s23.y));
+        }
       }
     }
     // Every pair the round-2 test `fma(-2, x.q, xk) <= tq` passed still passes: for finite operands the two forms differ by
@@ -246,6 +282,7 @@ __global__ __launch_bounds__(256, LH_FM_WAVES) void flat_filter_mfma_kernel(FmAr
             const float sv = __builtin_fmaf(mul2.x, dot, xk1 - tq4[e]);
             const int qi = q0 + ib + e;   // padded queries (qi >= nq) carry tq' = -inf: sv is +inf or a NaN, `<=` fails
             bool pass = sv <= 0.0f;
+            if constexpr (LOWER) pass = pass && !(__builtin_fmaf(mul2n.x, dot, lqb[ib + e] - xlo) > 0.0f);      // (a NaN rejects nothing)
             if (special) {                // ... but a row or query outside the margin's range passes without looking at sv: check qi
               const float qn = qnb[ib + e];
               pass = qi < p.nq && (pass || odd || !(qn < FM_NORM_HUGE) || (tiny && !(0.000244140625f * qn > FM_E_TINY)));
@@ -264,12 +301,15 @@ __global__ __launch_bounds__(256, LH_FM_WAVES) void flat_filter_mfma_kernel(FmAr
 }
 
 // exact evaluation of the queued (query, row) pairs: one workgroup per query, one lane per queued row
-template <int METRIC, typename TX>
+template <int METRIC, typename TX, bool LOWER = false>
 __global__ __launch_bounds__(256) void flat_mfma_eval_kernel(FmArgs a, int d) {
   const FlatPool &p = a.p;
   const int qi = blockIdx.x;
   const uint32_t raw = a.scnt[qi];
   if (raw == 0) return;
+  if constexpr (LOWER) {
+    if (p.qfill && threadIdx.x == 0) atomicMax(p.qfill, raw);      // flat_topk_v2 sizes the next epoch by the fullest queue
+  }
   if (raw > (uint32_t)FM_SQ_CAP && threadIdx.x == 0) atomicOr(p.overflow, 1u);   // rows were lost: the caller's repair loop rescans
   const int c = (int)min(raw, (uint32_t)FM_SQ_CAP);
   const uint32_t tk = p.tkey[qi];
@@ -283,6 +323,9 @@ __global__ __launch_bounds__(256) void flat_mfma_eval_kernel(FmArgs a, int d) {
     // the negative NaN and sorts FIRST -- every NaN row of the column entered the pool (exact.cuh: dist_exact_rt)
     const float v = finish_metric<METRIC>(dist_exact_rt<METRIC, TX, 16, METRIC == METRIC_L2>(qv, static_cast<const TX *>(p.x_native) + row * d, d));
     const uint32_t key = order_key(v);
+    if constexpr (LOWER) {
+      if (key < p.lo_key) continue;      // below the range: a row that is not there
+    }
     if (key < tk || (key == tk && rid <= tr)) {
       const uint32_t pos = atomicAdd(&p.cnt[qi], 1u);
       if (pos < (uint32_t)p.cap) {
@@ -313,9 +356,13 @@ template <int KS>
 static void fm_launch_ks(lance_hip_ctx *ctx, const FmArgs &a, int metric, dim3 grid) {
   constexpr int D = KS * 16;
   const size_t lds = std::max((size_t)FM_ROWS * (D + 4) * 4, (size_t)2 * 2 * FM_QT * (D + 8) * 2 + (size_t)4 * FM_QT * 4 + 16);
+  const size_t lds_lo = lds + (size_t)2 * FM_QT * 4;      // LOWER: lqs behind qodd
   auto go = [&](auto tag) {
     using TX = decltype(tag);
-    if (metric == METRIC_DOT) hipLaunchKernelGGL((flat_filter_mfma_kernel<KS, METRIC_DOT, TX>), grid, dim3(256), lds, ctx->stream, a);
+    if (a.p.has_lower) {
+      if (metric == METRIC_DOT) hipLaunchKernelGGL((flat_filter_mfma_kernel<KS, METRIC_DOT, TX, true>), grid, dim3(256), lds_lo, ctx->stream, a);
+      else hipLaunchKernelGGL((flat_filter_mfma_kernel<KS, METRIC_L2, TX, true>), grid, dim3(256), lds_lo, ctx->stream, a);
+    } else if (metric == METRIC_DOT) hipLaunchKernelGGL((flat_filter_mfma_kernel<KS, METRIC_DOT, TX>), grid, dim3(256), lds, ctx->stream, a);
     else hipLaunchKernelGGL((flat_filter_mfma_kernel<KS, METRIC_L2, TX>), grid, dim3(256), lds, ctx->stream, a);
   };
   if (a.p.x_dtype == LANCE_HIP_F16) go(__half());
@@ -326,7 +373,10 @@ static void fm_launch_ks(lance_hip_ctx *ctx, const FmArgs &a, int metric, dim3 g
 static void fm_launch_eval(lance_hip_ctx *ctx, const FmArgs &a, int metric, int d) {
   auto go = [&](auto tag) {
     using TX = decltype(tag);
-    if (metric == METRIC_DOT) hipLaunchKernelGGL((flat_mfma_eval_kernel<METRIC_DOT, TX>), dim3(a.p.nq), dim3(256), 0, ctx->stream, a, d);
+    if (a.p.has_lower) {
+      if (metric == METRIC_DOT) hipLaunchKernelGGL((flat_mfma_eval_kernel<METRIC_DOT, TX, true>), dim3(a.p.nq), dim3(256), 0, ctx->stream, a, d);
+      else hipLaunchKernelGGL((flat_mfma_eval_kernel<METRIC_L2, TX, true>), dim3(a.p.nq), dim3(256), 0, ctx->stream, a, d);
+    } else if (metric == METRIC_DOT) hipLaunchKernelGGL((flat_mfma_eval_kernel<METRIC_DOT, TX>), dim3(a.p.nq), dim3(256), 0, ctx->stream, a, d);
     else hipLaunchKernelGGL((flat_mfma_eval_kernel<METRIC_L2, TX>), dim3(a.p.nq), dim3(256), 0, ctx->stream, a, d);
   };
   if (a.p.x_dtype == LANCE_HIP_F16) go(__half());

@@ -31,6 +31,17 @@
 // widens: a pair that passes is decided by the exact arithmetic, a pair with true distance <= T cannot fail.  Rows or queries with
 // non-finite / zero norms take the permissive comparison (everything of theirs is handed to the exact evaluation; a queue that
 // overflows raises the pool-overflow flag and the caller's repair loop rescans with the exact kernel).
+//
+// Distance ranges.  The upper bound is the threshold the queries start from: nothing changes here.  With a LOWER bound
+// (template parameter LOWER) the filter also drops the pairs its surrogate PROVES to lie under the bound -- without that every row nearer
+// than `lower` is queued, the queues (FW_SQ_CAP) overflow and the repair loop rescans with the exact kernel.  The margins are symmetric
+// (|s~ - d| <= E), so the mirrored tests are
+//   L2      |x|^2 (1 + EW) + |q|^2 (1 + EW) - 2 x~.q~ < lower            reject
+//   dot     1 - x~.q~ + EW (|x|^2 + |q|^2) + 2^-22 < lower               reject
+//   cosine  (1 + EWC - lower) |q| |x| - x~.q~ < 0                          reject
+// each as sl = (the left side - lower) negated, so that a pair can pass only if max(sv, sl) <= 0: one more fma and one v_max per pair in
+// the fold, still one minimum per lane.  A bound that is not finite, and a degenerate row or query, reject nothing; the eval kernel
+// applies lo_key to every queued pair.  LOWER = false is the kernel from before ranges existed.
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
@@ -50,7 +61,7 @@ typedef float fw_f32x16 __attribute__((ext_vector_type(16)));
 // Measured at C3's shape (1000 queries x 1M x 1536, filter ms per call; gpurun r05n / r05r / r05t): BR x BQ = 2 x 2 (144 VGPRs, three waves
 // per SIMD) 7.7; 4 x 2 (236 VGPRs, two waves) 7.7; 2 x 1 (104 VGPRs, four waves) 9.3; 2 x 2 with 128-element stages (176 VGPRs, two waves) 14.3.
 // elements of d per stage: template parameter KT (64 / 128); LDS row stride KT + 8 bf16 elements (144 / 272 bytes: conflict-free ds_read_b128)
-constexpr int FW_SQ_CAP = 2048;       // queued rows per query and epoch
+constexpr int FW_SQ_CAP = FLAT_MC_QUEUE_CAP;       // queued rows per query and epoch
 constexpr float FW_EW = 0.0084f;      // > 2^-7 + 2^-16 + 4096 * 2^-23 = 0.00832 (first written as 0.0045 = one operand's roundoff: the CPU spec test caught it)
 constexpr float FW_EWC = 0.0085f;
 // The margins are RELATIVE bounds: they hold while no square, product or sum sits in the denormal range and nothing overflows.  As in
@@ -99,6 +110,14 @@ __global__ __launch_bounds__(64) void fw_query_prep_kernel(const float *__restri
   if (threadIdx.x == 0) qn2[i] = s;
 }
 
+// LOWER: the mirrored quantity of one pair, > 0 <=> the surrogate proves d < lower (header).  lq is the query's term (lqs), xh the row's.
+template <int METRIC>
+__device__ __forceinline__ float fw_lower_side(float dot, float xk, float xh, float lq) {
+  if constexpr (METRIC == METRIC_COSINE) return __builtin_fmaf(-lq, xk, dot);      // x~.q~ - (1 + EWC - lower) |q| |x|
+  else if constexpr (METRIC == METRIC_DOT) return dot - (lq + xh);                 // x~.q~ - (1 - lower + EW (|x|^2 + |q|^2) + 2^-22)
+  else return __builtin_fmaf(2.0f, dot, -(lq + xh));                               // 2 x~.q~ - ((|x|^2 + |q|^2)(1 + EW) - lower)
+}
+
 struct FwArgs {
   FlatPool p;
   const uint16_t *xb;          // [n][d] bf16 rows (ALL rows of the call: indexed by absolute row)
@@ -117,13 +136,14 @@ struct FwArgs {
 // stage of matrix work is all that covers their latency, and the SQ counters show the waves stalled or parked 83 % of the time
 // (profiles/r05q_*).  KT = 128 -- twice the work behind every load, half the barriers per MFMA, but 176 VGPRs = two waves per SIMD and 70 KB
 // of LDS -- measured 1.9 x SLOWER than KT = 64 (gpurun r05r: 14.3 vs 7.6 ms at C3's shape): occupancy is what hides the latency here.
-template <int METRIC, int BR, int KT, int BQ = 2>
+template <int METRIC, int BR, int KT, int BQ = 2, bool LOWER = false>
 __global__ __launch_bounds__(256, 2) void flat_filter_mfma_wide_kernel(FwArgs a) {
   constexpr int FW_KT = KT, FW_LS = KT + 8, HK = KT / 2, NU = KT / 16;      // a staging thread moves HK elements = NU 16-byte pieces of a row
   constexpr int FW_TM = 64 * BR, FW_TN = 64 * BQ;
   __shared__ __attribute__((aligned(16))) uint16_t Xs[FW_TM * FW_LS];
   __shared__ __attribute__((aligned(16))) uint16_t Qs[FW_TN * FW_LS];
   __shared__ __attribute__((aligned(16))) float tqs[FW_TN];
+  __shared__ __attribute__((aligned(16))) float lqs[LOWER ? FW_TN : 4];      // LOWER: the query's term of the mirrored test
   const FlatPool &p = a.p;
   const int d = a.d;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -146,6 +166,9 @@ __global__ __launch_bounds__(256, 2) void flat_filter_mfma_wide_kernel(FwArgs a)
   if (threadIdx.x < FW_TN) {
     const int qi = q0 + threadIdx.x;
     float t;
+    [[maybe_unused]] float lq = INFINITY;      // the mirrored quantity is -inf (or a NaN) with this term: nothing is rejected
+    [[maybe_unused]] const float lower = LOWER ? key_to_float(p.lo_key) : 0.0f;
+    [[maybe_unused]] const bool lower_ok = LOWER && fabsf(lower) < INFINITY;
     if (qi < p.nq) {
       const uint32_t tk = p.tkey[qi];
       const float T = tk >= 0xFF800000u ? INFINITY : key_to_float(tk);      // no threshold yet / NaN threshold: every row is a candidate
@@ -153,18 +176,22 @@ __global__ __launch_bounds__(256, 2) void flat_filter_mfma_wide_kernel(FwArgs a)
         const float qn = p.q_norm[qi];
         t = (qn > FW_COS_TINY && qn < INFINITY) ? (1.0f - FW_EWC - T) * qn : -INFINITY;      // degenerate query: everything passes to the exact evaluation
         q_odd = !(qn > FW_COS_TINY && qn < INFINITY);
+        if (lower_ok && !q_odd) lq = (1.0f + FW_EWC - lower) * qn;      // sl = x~.q~ - lq |x| > 0: the pair lies under the bound
       } else if constexpr (METRIC == METRIC_DOT) {
         t = T + FW_EW * a.qn2[qi] + 4.7683716e-7f;      // (+ 2^-22: the reference's distance is the f32 value of 1 - x.q -- products closer than an ulp of 1 tie there)
         q_odd = !(a.qn2[qi] < FW_NORM_HUGE);
+        if (lower_ok && !q_odd) lq = (1.0f - lower) + FW_EW * a.qn2[qi] + 4.7683716e-7f;      // sl = x~.q~ - (lq + EW |x|^2) > 0
       } else {
         const float qn = a.qn2[qi];
         t = T - (qn - FW_EW * qn);
         q_odd = !(qn < FW_NORM_HUGE);
+        if (lower_ok && !q_odd) lq = (qn + FW_EW * qn) - lower;      // sl = 2 x~.q~ - (lq + |x|^2 (1 + EW)) > 0
       }
     } else {
       t = METRIC == METRIC_COSINE ? INFINITY : -INFINITY;      // padded query: nothing passes (and the queue test below checks qi < nq)
     }
     tqs[threadIdx.x] = t;
+    if constexpr (LOWER) lqs[threadIdx.x] = lq;
   }
 
   // staging: thread (r, h) moves half a stage (HK elements) of query r and of the rows r, r + 128, .. per stage
@@ -230,6 +257,7 @@ __global__ __launch_bounds__(256, 2) void flat_filter_mfma_wide_kernel(FwArgs a)
     const int64_t row = row0 + wr * 32 * BR + bi * 32 + j;
     const bool rvalid = row < p.r1;
     float xk = 0.0f;        // per-row constant of the test
+    [[maybe_unused]] float xh = 0.0f;        // LOWER: per-row constant of the mirrored test (cosine: xk serves both)
     bool odd = false;       // row whose norm is not usable: every query takes it
     bool tiny = false;      // row whose part of the margin is in the denormal range: the queries that are tiny too take it
     if (rvalid) {
@@ -239,6 +267,7 @@ __global__ __launch_bounds__(256, 2) void flat_filter_mfma_wide_kernel(FwArgs a)
       } else {
         const float n2 = a.xn2[row];
         xk = METRIC == METRIC_DOT ? 1.0f - FW_EW * n2 : n2 - FW_EW * n2;
+        xh = METRIC == METRIC_DOT ? FW_EW * n2 : n2 + FW_EW * n2;
         odd = !(n2 < FW_NORM_HUGE);
         tiny = !(0.000244140625f * n2 > FW_E_TINY);
       }
@@ -250,6 +279,8 @@ __global__ __launch_bounds__(256, 2) void flat_filter_mfma_wide_kernel(FwArgs a)
 #pragma unroll
       for (int vq = 0; vq < 4; ++vq) {
         const f4 t4 = *reinterpret_cast<const f4 *>(tqb + 8 * vq);
+        [[maybe_unused]] f4 l4 = {0.0f, 0.0f, 0.0f, 0.0f};
+        if constexpr (LOWER) l4 = *reinterpret_cast<const f4 *>(lqs + (tqb - tqs) + 8 * vq);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const float dot = acc[bi][bj][4 * vq + e];
@@ -257,6 +288,7 @@ __global__ __launch_bounds__(256, 2) void flat_filter_mfma_wide_kernel(FwArgs a)
           if constexpr (METRIC == METRIC_COSINE) sv = __builtin_fmaf(t4[e], xk, -dot);
           else if constexpr (METRIC == METRIC_DOT) sv = (xk - t4[e]) - dot;
           else sv = __builtin_fmaf(-2.0f, dot, xk - t4[e]);
+          if constexpr (LOWER) sv = __builtin_fmaxf(sv, fw_lower_side<METRIC>(dot, xk, xh, l4[e]));      // (fmaxf drops a NaN: the fold only widens)
           mn = __builtin_fminf(mn, sv);      // (a NaN is ignored by the minimum and fails `<=` below alike)
         }
       }
@@ -268,6 +300,8 @@ __global__ __launch_bounds__(256, 2) void flat_filter_mfma_wide_kernel(FwArgs a)
 #pragma unroll
         for (int vq = 0; vq < 4; ++vq) {
           const f4 t4 = *reinterpret_cast<const f4 *>(tqb + 8 * vq);
+          [[maybe_unused]] f4 l4 = {0.0f, 0.0f, 0.0f, 0.0f};
+          if constexpr (LOWER) l4 = *reinterpret_cast<const f4 *>(lqs + (tqb - tqs) + 8 * vq);
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const float dot = acc[bi][bj][4 * vq + e];
@@ -278,7 +312,8 @@ __global__ __launch_bounds__(256, 2) void flat_filter_mfma_wide_kernel(FwArgs a)
             const int qi = q0 + wq * 32 * BQ + bj * 32 + 8 * vq + 4 * g + e;
             bool pass = false;
             if (qi < p.nq) {
-              pass = odd || sv <= 0.0f;
+              if constexpr (LOWER) pass = odd || (sv <= 0.0f && !(fw_lower_side<METRIC>(dot, xk, xh, l4[e]) > 0.0f));      // (a NaN rejects nothing)
+              else pass = odd || sv <= 0.0f;
               if constexpr (METRIC == METRIC_COSINE) {
                 if (!pass && tile_qodd) { const float qn = p.q_norm[qi]; pass = !(qn > FW_COS_TINY && qn < INFINITY); }
               } else {
@@ -297,13 +332,16 @@ __global__ __launch_bounds__(256, 2) void flat_filter_mfma_wide_kernel(FwArgs a)
 }
 
 // exact evaluation of the queued (query, row) pairs: one workgroup per query, one lane per queued row
-template <int METRIC>
+template <int METRIC, bool LOWER = false>
 __global__ __launch_bounds__(256) void flat_wide_eval_kernel(FwArgs a) {
   const FlatPool &p = a.p;
   const int d = a.d;
   const int qi = blockIdx.x;
   const uint32_t raw = a.scnt[qi];
   if (raw == 0) return;
+  if constexpr (LOWER) {
+    if (p.qfill && threadIdx.x == 0) atomicMax(p.qfill, raw);      // flat_topk_v2 sizes the next epoch by the fullest queue
+  }
   if (raw > (uint32_t)FW_SQ_CAP && threadIdx.x == 0) atomicOr(p.overflow, 1u);   // rows were lost: the caller's repair loop rescans
   const int c = (int)min(raw, (uint32_t)FW_SQ_CAP);
   const uint32_t tk = p.tkey[qi];
@@ -318,6 +356,9 @@ __global__ __launch_bounds__(256) void flat_wide_eval_kernel(FwArgs a) {
     if constexpr (METRIC == METRIC_COSINE) v = cosine_exact_rt<float>(qv, qnorm, p.x + row * d, d);
     else v = finish_metric<METRIC>(dist_exact_rt<METRIC, float, 16, METRIC == METRIC_L2>(qv, p.x + row * d, d));      // (L2: x - q, flat_mfma.hip)
     const uint32_t key = order_key(v);
+    if constexpr (LOWER) {
+      if (key < p.lo_key) continue;      // below the range: a row that is not there
+    }
     if (key < tk || (key == tk && rid <= tr)) {
       const uint32_t pos = atomicAdd(&p.cnt[qi], 1u);
       if (pos < (uint32_t)p.cap) {
@@ -387,7 +428,18 @@ int launch_flat_filter_mfma_wide(lance_hip_ctx *ctx, const FlatPool &e, int d, i
   ScopedTimer t(ctx, "flat_mfma_wide");
   auto go = [&](auto br_tag, auto bq_tag) {
     constexpr int BR = decltype(br_tag)::value, BQ = decltype(bq_tag)::value;
-    if (metric == METRIC_COSINE) {
+    if (e.has_lower) {
+      if (metric == METRIC_COSINE) {
+        hipLaunchKernelGGL((flat_filter_mfma_wide_kernel<METRIC_COSINE, BR, 64, BQ, true>), grid, dim3(256), 0, ctx->stream, a);
+        hipLaunchKernelGGL((flat_wide_eval_kernel<METRIC_COSINE, true>), dim3(e.nq), dim3(256), 0, ctx->stream, a);
+      } else if (metric == METRIC_DOT) {
+        hipLaunchKernelGGL((flat_filter_mfma_wide_kernel<METRIC_DOT, BR, 64, BQ, true>), grid, dim3(256), 0, ctx->stream, a);
+        hipLaunchKernelGGL((flat_wide_eval_kernel<METRIC_DOT, true>), dim3(e.nq), dim3(256), 0, ctx->stream, a);
+      } else {
+        hipLaunchKernelGGL((flat_filter_mfma_wide_kernel<METRIC_L2, BR, 64, BQ, true>), grid, dim3(256), 0, ctx->stream, a);
+        hipLaunchKernelGGL((flat_wide_eval_kernel<METRIC_L2, true>), dim3(e.nq), dim3(256), 0, ctx->stream, a);
+      }
+    } else if (metric == METRIC_COSINE) {
       hipLaunchKernelGGL((flat_filter_mfma_wide_kernel<METRIC_COSINE, BR, 64, BQ>), grid, dim3(256), 0, ctx->stream, a);
       hipLaunchKernelGGL((flat_wide_eval_kernel<METRIC_COSINE>), dim3(e.nq), dim3(256), 0, ctx->stream, a);
     } else if (metric == METRIC_DOT) {

@@ -21,6 +21,9 @@
 // More rows tied at a threshold than the list holds (thousands of duplicate vectors) raise a flag and the caller takes the
 // batch path, which repairs such cases.  For one query the flag reaches the host through a pinned word the merge kernel
 // writes (and it clears the device word behind itself): a call is two launches and a stream wait.
+// Distance ranges: the running threshold starts at the upper bound's last key instead of ~0 (it only ever drops, to the
+// k-th key of entries already listed: never below the k-th in-range key), and the LOWER instantiation lists a row only at or above the
+// lower bound's key.  The merge kernel sees in-range pairs only and is unchanged.
 // C1 (1M x 128 f32, k = 10): 0.140 ms per call, of which the scan kernel 96 us (5.3 TB/s) and the merge 16 us
 // (profiles/r06zzo_flat_one_*).
 #include <algorithm>
@@ -54,9 +57,12 @@ struct FsArgs {
   uint64_t *lrids;
   uint32_t *overflow;
   uint32_t *host_flag = nullptr; // one query: pinned host word the merge kernel leaves the overflow flag in (it also clears `overflow` for the next call)
+  // distance range: the running threshold of every query starts at start_key (hi_key - 1 under an upper bound, else ~0)
+  // and only drops; the LOWER instantiation appends a row only when key >= lo_key.  The merge kernel sees in-range pairs only.
+  uint32_t start_key = 0xFFFFFFFFu, lo_key = 0;
 };
 
-template <int METRIC, typename TX, int NQ>
+template <int METRIC, typename TX, int NQ, bool LOWER = false>
 __global__ __launch_bounds__(FS_BS) void flat_small_scan_kernel(FsArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int dpad = (a.d + 15) & ~15;
@@ -73,7 +79,7 @@ __global__ __launch_bounds__(FS_BS) void flat_small_scan_kernel(FsArgs a) {
     const int qi = i / dpad, e = i - qi * dpad;
     qs[i] = e < a.d ? a.q[(int64_t)qi * a.d + e] : 0.0f;
   }
-  if (threadIdx.x < NQ * 4) misc[threadIdx.x] = (threadIdx.x & 3) == 1 ? 0xFFFFFFFFu : 0u;
+  if (threadIdx.x < NQ * 4) misc[threadIdx.x] = (threadIdx.x & 3) == 1 ? a.start_key : 0u;
   __syncthreads();
   const TX *x = static_cast<const TX *>(a.x);
   const int d = a.d, full = d / 16 * 16;
@@ -150,7 +156,9 @@ __global__ __launch_bounds__(FS_BS) void flat_small_scan_kernel(FsArgs a) {
           run = prev + acc[qi];
         }
         const uint32_t key = order_key(finish_metric<METRIC>(s[qi] + run));
-        if (valid && gi == 15 && key <= T[qi]) {
+        bool take = valid && gi == 15 && key <= T[qi];
+        if constexpr (LOWER) take = take && key >= a.lo_key;
+        if (take) {
           const uint32_t slot = atomicAdd(&misc[qi * 4], 1u);
           if (slot < (uint32_t)FS_CAP) { ckey[qi * FS_CAP + slot] = key; cpos[qi * FS_CAP + slot] = (uint32_t)(row - r_begin); }
           else misc[qi * 4 + 3] = 1u;
@@ -302,22 +310,23 @@ bool flat_small_supported(int metric, int dtype, uint32_t d, uint32_t nq, uint32
   return n >= 4096;     // tiny tables: the batch path's single epoch is as good
 }
 
-template <int METRIC, typename TX>
+template <int METRIC, typename TX, bool LOWER>
 static void fs_launch_nq(lance_hip_ctx *ctx, const FsArgs &a, size_t lds_fixed) {
   const int dpad = (a.d + 15) & ~15;
   auto lds = [&](int nq) { return (size_t)nq * dpad * 4 + (size_t)nq * FS_CAP * 8 + lds_fixed; };
   const dim3 grid((unsigned)a.G), block(FS_BS);
-  if (a.nq == 1) hipLaunchKernelGGL((flat_small_scan_kernel<METRIC, TX, 1>), grid, block, lds(1), ctx->stream, a);
-  else if (a.nq == 2) hipLaunchKernelGGL((flat_small_scan_kernel<METRIC, TX, 2>), grid, block, lds(2), ctx->stream, a);
-  else if (a.nq == 3) hipLaunchKernelGGL((flat_small_scan_kernel<METRIC, TX, 3>), grid, block, lds(3), ctx->stream, a);
-  else hipLaunchKernelGGL((flat_small_scan_kernel<METRIC, TX, 4>), grid, block, lds(4), ctx->stream, a);
+  if (a.nq == 1) hipLaunchKernelGGL((flat_small_scan_kernel<METRIC, TX, 1, LOWER>), grid, block, lds(1), ctx->stream, a);
+  else if (a.nq == 2) hipLaunchKernelGGL((flat_small_scan_kernel<METRIC, TX, 2, LOWER>), grid, block, lds(2), ctx->stream, a);
+  else if (a.nq == 3) hipLaunchKernelGGL((flat_small_scan_kernel<METRIC, TX, 3, LOWER>), grid, block, lds(3), ctx->stream, a);
+  else hipLaunchKernelGGL((flat_small_scan_kernel<METRIC, TX, 4, LOWER>), grid, block, lds(4), ctx->stream, a);
 }
 
 // x: the rows in their own element type; q: f32 queries.  *done = false: the list overflowed (mass ties) -- take the batch path.
 int flat_topk_small(lance_hip_ctx *ctx, int metric, int dtype, const void *x, const uint64_t *row_ids, uint64_t n, uint32_t d, const float *q,
-                    uint32_t nq, uint32_t k, uint64_t *ids, float *dists, bool *done) {
+                    uint32_t nq, uint32_t k, const FlatRange &rg, uint64_t *ids, float *dists, bool *done) {
   *done = false;
   FsArgs a;
+  a.start_key = rg.start_key(); a.lo_key = rg.has_lower ? rg.lo_key : 0u;
   a.x = x; a.row_ids = row_ids; a.n = (int64_t)n; a.d = (int)d; a.nq = (int)nq; a.k = (int)k; a.q = q;
   const uint64_t step = 16 * FS_RPI;
   static const int wgs_per_cu = getenv("LANCE_HIP_FS_WGS_PER_CU") ? std::max(1, atoi(getenv("LANCE_HIP_FS_WGS_PER_CU"))) : 4;      // A/B
@@ -348,8 +357,11 @@ int flat_topk_small(lance_hip_ctx *ctx, int metric, int dtype, const void *x, co
     ScopedTimer t(ctx, "flat_scan");
     auto go = [&](auto tag) {
       using TX = decltype(tag);
-      if (metric == LANCE_HIP_DOT) fs_launch_nq<METRIC_DOT, TX>(ctx, a, lds_fixed);
-      else fs_launch_nq<METRIC_L2, TX>(ctx, a, lds_fixed);
+      if (rg.has_lower) {
+        if (metric == LANCE_HIP_DOT) fs_launch_nq<METRIC_DOT, TX, true>(ctx, a, lds_fixed);
+        else fs_launch_nq<METRIC_L2, TX, true>(ctx, a, lds_fixed);
+      } else if (metric == LANCE_HIP_DOT) fs_launch_nq<METRIC_DOT, TX, false>(ctx, a, lds_fixed);
+      else fs_launch_nq<METRIC_L2, TX, false>(ctx, a, lds_fixed);
     };
     if (dtype == LANCE_HIP_F16) go(__half());
     else if (dtype == LANCE_HIP_I8) go(int8_t());

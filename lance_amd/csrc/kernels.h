@@ -1,6 +1,7 @@
 // kernels.h -- internal launcher prototypes shared by the translation units.
 #pragma once
 #include <stdint.h>
+#include <string.h>
 
 #include "common.h"
 #include "search_plan.h"
@@ -84,7 +85,43 @@ struct FlatPool {
   uint32_t *overflow;   // [1]
   const float *row_sy = nullptr;   // cosine: sqrt(y_norm) per row   (cosine.rs:143-175)
   const float *q_norm = nullptr;   // cosine: norm_l2(query)
+  // distance range.  The upper bound is not carried: it is the threshold every query STARTS from (flat_pool_reset_kernel).
+  // has_lower picks the LOWER instantiation of the scan kernels, which append a cell only when key >= lo_key (the total order on f32,
+  // order_key); without a lower bound there is NO test, and the kernels are the ones from before ranges existed.
+  int has_lower = 0;
+  uint32_t lo_key = 0;
+  uint32_t *qfill = nullptr;       // [1] LOWER on the matrix cores: the eval kernels leave the fullest queue's count of the epoch (atomicMax)
 };
+constexpr int FLAT_MC_QUEUE_CAP = 2048;      // rows a query's queue holds per epoch of the matrix-core filters (flat_mfma.hip, flat_mfma_wide.hip)
+
+// a call's distance range as order keys (exact.cuh order_key, on the host): in range <=> (!has_lower || key >= lo_key) && (!has_upper || key < hi_key)
+struct FlatRange {
+  bool has_lower = false, has_upper = false;
+  uint32_t lo_key = 0, hi_key = 0xFFFFFFFFu;
+  bool any() const { return has_lower || has_upper; }
+  bool empty() const { return (has_upper && hi_key == 0) || (has_lower && has_upper && lo_key >= hi_key); }
+  // the threshold pair every query starts from: the largest pair still under the upper bound
+  uint32_t start_key() const { return has_upper ? hi_key - 1 : 0xFFFFFFFFu; }
+};
+// f32::total_cmp order key of a bound on the host: exact.cuh order_key, whose __float_as_uint is device code
+inline uint32_t host_order_key(float f) {
+  uint32_t b;
+  memcpy(&b, &f, 4);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+inline float key_to_float_host(uint32_t k) {
+  const uint32_t b = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
+  float f;
+  memcpy(&f, &b, 4);
+  return f;
+}
+inline FlatRange flat_range(int has_lower, float lower, int has_upper, float upper) {
+  FlatRange r;
+  r.has_lower = has_lower != 0; r.has_upper = has_upper != 0;
+  if (r.has_lower) r.lo_key = host_order_key(lower);
+  if (r.has_upper) r.hi_key = host_order_key(upper);
+  return r;
+}
 
 int launch_wide_filter(lance_hip_ctx *ctx, const FlatPool &fp, int d, int metric);   // wide.hip, any d
 // search.hip: prefilter by row id -> one bit per storage position (scratch "search.allow_bits")
@@ -173,7 +210,7 @@ int sq_merge_pairs(lance_hip_ctx *ctx, const PairLists &pl, uint32_t nq, uint64_
 // flat_small.hip: exhaustive KNN for one to four queries in a single streaming pass (*done = false: mass ties, take the batch path)
 bool flat_small_supported(int metric, int dtype, uint32_t d, uint32_t nq, uint32_t k, uint64_t n);
 int flat_topk_small(lance_hip_ctx *ctx, int metric, int dtype, const void *x, const uint64_t *row_ids, uint64_t n, uint32_t d, const float *q,
-                    uint32_t nq, uint32_t k, uint64_t *ids, float *dists, bool *done);
+                    uint32_t nq, uint32_t k, const FlatRange &rg, uint64_t *ids, float *dists, bool *done);
 // mfma_assign.hip: the coarse quantiser at query time on the matrix cores (surrogate matrix + exact re-check of the candidates)
 bool coarse_mfma_supported(int metric, int d, uint32_t nq, uint32_t nlist, uint32_t nprobes, bool lanes32, const float *q, const float *cent);
 // fewer lists than the per-group route takes: sweep + select in one kernel (coarse_fused_kernel), which needs no [nq][nlist] matrix.  Its centroid

@@ -21,6 +21,8 @@
 //
 // The top-k is a (distance key, row id) sort: blocks of 2048 candidates are sorted in LDS and keep their k best, repeated until one
 // block is left.  (key, row id) is a total order, so the answer equals the reference's SortExec, ties included.
+// Distance ranges (lance_hip_flat_multivec_topk_range): the first selection round loads a row whose distance key lies
+// outside lower <= d < upper as the empty sentinel; the scan itself does not change.
 #include <algorithm>
 
 #include "common.h"
@@ -231,10 +233,13 @@ __global__ __launch_bounds__(64) void mv_qnorm_kernel(const float *__restrict__ 
 
 // One block sorts MV_SEL candidates by (key, row id) and keeps the k best (k <= MV_SEL / 2).  First round: the candidates are the
 // rows (dists, row_ids or the row index); later rounds: the survivors of the round before.  The last round (one block) writes the answer.
+// RANGE (distance ranges), first round only: a row whose distance key lies outside lo_key <= key <= hi_last loads as the
+// empty sentinel -- a row that is not there; absent bounds are 0 / ~0, which test nothing.  RANGE = false is the kernel from before.
+template <bool RANGE>
 __global__ __launch_bounds__(256) void mv_select_kernel(const float *__restrict__ dists, const uint64_t *__restrict__ row_ids,
                                                         const uint32_t *__restrict__ in_keys, const uint64_t *__restrict__ in_rids,
                                                         uint64_t n_in, int k, uint32_t *__restrict__ out_keys, uint64_t *__restrict__ out_rids,
-                                                        uint64_t *__restrict__ ids, float *__restrict__ out_dists) {
+                                                        uint64_t *__restrict__ ids, float *__restrict__ out_dists, uint32_t lo_key, uint32_t hi_last) {
   __shared__ uint64_t rid[MV_SEL];
   __shared__ uint32_t key[MV_SEL];
   const uint64_t base = (uint64_t)blockIdx.x * MV_SEL;
@@ -243,7 +248,12 @@ __global__ __launch_bounds__(256) void mv_select_kernel(const float *__restrict_
     uint32_t kk = 0xFFFFFFFFu;
     uint64_t rr = ~0ull;
     if (g < n_in) {
-      if (dists) { kk = order_key(dists[g]); rr = row_ids ? row_ids[g] : g; }
+      if (dists) {
+        kk = order_key(dists[g]); rr = row_ids ? row_ids[g] : g;
+        if constexpr (RANGE) {
+          if (kk < lo_key || kk > hi_last) { kk = 0xFFFFFFFFu; rr = ~0ull; }
+        }
+      }
       else { kk = in_keys[g]; rr = in_rids[g]; }
     }
     key[i] = kk; rid[i] = rr;
@@ -378,14 +388,19 @@ extern "C" int lance_hip_multivec_distance(lance_hip_ctx *ctx, int dtype, int me
   return mv_finish_call(ctx, "multivec_distance", flag);
 }
 
-extern "C" int lance_hip_flat_multivec_topk(lance_hip_ctx *ctx, int dtype, int metric, const void *values, const uint64_t *offsets,
-                                            const uint64_t *row_ids, uint64_t n_rows, uint32_t d, const void *q, uint32_t nqv,
-                                            uint32_t k, uint64_t *ids, float *dists) {
-  lh::CtxLock _ctx_lock(ctx);
-  LH_TRY(mv_check_args("flat_multivec_topk", ctx, dtype, metric, values, offsets, n_rows, d, q, nqv));
-  LH_REQUIRE(ids && dists, "flat_multivec_topk: NULL argument");
-  LH_REQUIRE(k > 0 && k <= (uint32_t)MV_SEL / 2, "flat_multivec_topk: k=%u not supported (1..%d)", k, MV_SEL / 2);
+// lance_hip_flat_multivec_topk and lance_hip_flat_multivec_topk_range: the scan writes every row's distance, the range is applied
+// where the first selection round loads them (mv_select_kernel<true>); an empty range still scans, so that a malformed column is refused
+static int mv_topk_impl(const char *what, lance_hip_ctx *ctx, int dtype, int metric, const void *values, const uint64_t *offsets,
+                        const uint64_t *row_ids, uint64_t n_rows, uint32_t d, const void *q, uint32_t nqv, uint32_t k, const FlatRange &rg,
+                        uint64_t *ids, float *dists) {
+  LH_TRY(mv_check_args(what, ctx, dtype, metric, values, offsets, n_rows, d, q, nqv));
+  LH_REQUIRE(ids && dists, "%s: NULL argument", what);
+  LH_REQUIRE(k > 0 && k <= (uint32_t)MV_SEL / 2, "%s: k=%u not supported (1..%d)", what, k, MV_SEL / 2);
+  LH_REQUIRE(!(rg.has_lower && rg.has_upper) || rg.lo_key <= rg.hi_key, "%s: lower bound %g is above the upper bound %g", what,
+             (double)key_to_float_host(rg.lo_key), (double)key_to_float_host(rg.hi_key));
   LH_CHECK_HIP(hipSetDevice(ctx->device));
+  // in range <=> lo <= key <= hi_last; an empty range (lower == upper, or an upper bound under every key) is lo > hi_last
+  const uint32_t sel_lo = rg.empty() ? 1u : (rg.has_lower ? rg.lo_key : 0u), sel_hi = rg.empty() ? 0u : rg.start_key();
   const uint64_t nb0 = std::max<uint64_t>(1, cdiv(n_rows, MV_SEL));
   float *rd = ctx->scratch_t<float>("mv.dists", std::max<uint64_t>(1, n_rows));
   uint32_t *sk[2] = {nullptr, nullptr};
@@ -408,14 +423,34 @@ extern "C" int lance_hip_flat_multivec_topk(lance_hip_ctx *ctx, int dtype, int m
       const uint64_t nb = std::max<uint64_t>(1, cdiv(n_in, MV_SEL));
       const bool last = nb == 1;
       const int nxt = cur == 0 ? 1 : 0;
-      hipLaunchKernelGGL(mv_select_kernel, dim3((unsigned)nb), dim3(256), 0, ctx->stream, cur < 0 ? rd : nullptr, cur < 0 ? row_ids : nullptr,
-                         cur < 0 ? nullptr : sk[cur], cur < 0 ? nullptr : sr[cur], n_in, (int)k, last ? nullptr : sk[nxt],
-                         last ? nullptr : sr[nxt], last ? ids : nullptr, last ? dists : nullptr);
+      if (rg.any() && cur < 0)
+        hipLaunchKernelGGL(mv_select_kernel<true>, dim3((unsigned)nb), dim3(256), 0, ctx->stream, rd, row_ids, nullptr, nullptr, n_in, (int)k,
+                           last ? nullptr : sk[nxt], last ? nullptr : sr[nxt], last ? ids : nullptr, last ? dists : nullptr, sel_lo, sel_hi);
+      else
+        hipLaunchKernelGGL(mv_select_kernel<false>, dim3((unsigned)nb), dim3(256), 0, ctx->stream, cur < 0 ? rd : nullptr, cur < 0 ? row_ids : nullptr,
+                           cur < 0 ? nullptr : sk[cur], cur < 0 ? nullptr : sr[cur], n_in, (int)k, last ? nullptr : sk[nxt],
+                           last ? nullptr : sr[nxt], last ? ids : nullptr, last ? dists : nullptr, 0u, 0xFFFFFFFFu);
       if (last) break;
       n_in = nb * k;
       cur = nxt;
     }
   }
   LH_CHECK_HIP(hipGetLastError());
-  return mv_finish_call(ctx, "flat_multivec_topk", flag);
+  return mv_finish_call(ctx, what, flag);
+}
+
+extern "C" int lance_hip_flat_multivec_topk(lance_hip_ctx *ctx, int dtype, int metric, const void *values, const uint64_t *offsets,
+                                            const uint64_t *row_ids, uint64_t n_rows, uint32_t d, const void *q, uint32_t nqv,
+                                            uint32_t k, uint64_t *ids, float *dists) {
+  lh::CtxLock _ctx_lock(ctx);
+  return mv_topk_impl("flat_multivec_topk", ctx, dtype, metric, values, offsets, row_ids, n_rows, d, q, nqv, k, FlatRange{}, ids, dists);
+}
+
+extern "C" int lance_hip_flat_multivec_topk_range(lance_hip_ctx *ctx, int dtype, int metric, const void *values, const uint64_t *offsets,
+                                                  const uint64_t *row_ids, uint64_t n_rows, uint32_t d, const void *q, uint32_t nqv,
+                                                  uint32_t k, int has_lower, float lower, int has_upper, float upper, uint64_t *ids,
+                                                  float *dists) {
+  lh::CtxLock _ctx_lock(ctx);
+  return mv_topk_impl("flat_multivec_topk_range", ctx, dtype, metric, values, offsets, row_ids, n_rows, d, q, nqv, k,
+                      flat_range(has_lower, lower, has_upper, upper), ids, dists);
 }

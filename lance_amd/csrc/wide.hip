@@ -34,7 +34,9 @@ constexpr int W_ROWS = 32, W_CENTS = 64, W_DK = 64, W_LD = 80, W_BS = 512, W_RLD
 // hardware lanes of a pair make two passes over the staged slices (even chunks, then odd chunks) and the lane-ordered sum
 // continues from the first pass's total: tot = fold(fold(0, even lanes 0..15), odd lanes 0..15).  The remainder (d % 32, up to
 // 31 products) is summed sequentially first, in two 16-wide pieces, into its own buffer; result = remainder + tot.
-template <int METRIC, int MODE, bool L32 = false>
+//           LOWER (distance ranges): a cell whose key is below fp.lo_key is not appended; the upper bound is the
+//           threshold the queries start from.  LOWER = false is the kernel from before ranges existed.
+template <int METRIC, int MODE, bool L32 = false, bool LOWER = false>
 __global__ __launch_bounds__(W_BS) void pairwise_wide_kernel(PairwiseArgs p, int d, FlatPool fp) {
   static_assert(!L32 || (METRIC == METRIC_DOT && MODE != 2), "32-lane order: dot products of f16 columns, assign / matrix modes");
   __shared__ __attribute__((aligned(16))) float xt[W_ROWS * W_LD];    // 10 KB  rows x 64-slice (+pad: bank shift per row)
@@ -274,6 +276,9 @@ __global__ __launch_bounds__(W_BS) void pairwise_wide_kernel(PairwiseArgs p, int
           else v = finish_metric<METRIC>(res[r][c]);
           const uint32_t key = order_key(v);
           const uint64_t rid = trid[r];
+          if constexpr (LOWER) {
+            if (key < fp.lo_key) continue;      // below the range: a row that is not there
+          }
           if (key < tk[c] || (key == tk[c] && rid <= tr[c])) {
             const uint32_t pos = atomicAdd(&fp.cnt[c0 + c], 1u);
             if (pos < (uint32_t)fp.cap) {
@@ -355,8 +360,12 @@ int launch_wide_filter(lance_hip_ctx *ctx, const FlatPool &fp, int d, int metric
   int z = 1;
   if (rblocks < 2ll * ctx->num_cus) z = (int)std::min<int64_t>(nblocks, cdiv(2ll * ctx->num_cus, rblocks));
   const dim3 grid((unsigned)rblocks, 1, z);
-  if (metric == METRIC_COSINE) {
-    LH_REQUIRE(d % 16 == 0 && fp.row_sy && fp.q_norm, "wide filter: cosine needs d %% 16 == 0 and precomputed norms");
+  if (metric == METRIC_COSINE) LH_REQUIRE(d % 16 == 0 && fp.row_sy && fp.q_norm, "wide filter: cosine needs d %% 16 == 0 and precomputed norms");
+  if (fp.has_lower) {
+    if (metric == METRIC_COSINE) hipLaunchKernelGGL((pairwise_wide_kernel<METRIC_COSINE, 2, false, true>), grid, dim3(W_BS), 0, ctx->stream, p, d, fp);
+    else if (metric == METRIC_DOT) hipLaunchKernelGGL((pairwise_wide_kernel<METRIC_DOT, 2, false, true>), grid, dim3(W_BS), 0, ctx->stream, p, d, fp);
+    else hipLaunchKernelGGL((pairwise_wide_kernel<METRIC_L2, 2, false, true>), grid, dim3(W_BS), 0, ctx->stream, p, d, fp);
+  } else if (metric == METRIC_COSINE) {
     hipLaunchKernelGGL((pairwise_wide_kernel<METRIC_COSINE, 2>), grid, dim3(W_BS), 0, ctx->stream, p, d, fp);
   } else if (metric == METRIC_DOT) {
     hipLaunchKernelGGL((pairwise_wide_kernel<METRIC_DOT, 2>), grid, dim3(W_BS), 0, ctx->stream, p, d, fp);

@@ -489,7 +489,12 @@ class Engine:
                                               _ptr(rid), n_p, k, int(has), lo, hi, _ptr(out_i), _ptr(out_d), C.byref(cnt)))
         return out_i[:cnt.value], out_d[:cnt.value]
 
-    def flat_topk(self, x, q, k, metric="l2", row_ids=None):
+    def flat_topk(self, x, q, k, metric="l2", row_ids=None, lower=None, upper=None):
+        """exhaustive KNN -> (ids [nq][k] int64, distances [nq][k]) sorted by (distance, row id); missing slots: id -1, distance +inf.
+        lower / upper: distance range (lance_hip_flat_topk_range) -- the k nearest rows with lower <= d < upper in the total order
+        on f32.  A bound that is None is NOT TESTED (IvfFlatIndex.nearest's open ends are the largest finite f32 instead): (lower,
+        None) keeps +inf and NaN distances.  Both None: lance_hip_flat_topk, the call from before ranges existed."""
+        rng = _flat_range_args(lower, upper)
         x, dt = _vec(x)
         q = _like(q, x).reshape(-1, x.shape[1])
         n, d = x.shape
@@ -498,8 +503,12 @@ class Engine:
         ids = torch.empty((nq, k), dtype=torch.int64, device=x.device)
         dists = torch.empty((nq, k), dtype=torch.float32, device=x.device)
         torch.cuda.synchronize()
-        check(self.lib.lance_hip_flat_topk(self.h, dt, METRICS[metric], _ptr(x), _ptr(rid), n, d, _ptr(q), nq, k,
-                                           _ptr(ids), _ptr(dists)))
+        if rng is None:
+            check(self.lib.lance_hip_flat_topk(self.h, dt, METRICS[metric], _ptr(x), _ptr(rid), n, d, _ptr(q), nq, k,
+                                               _ptr(ids), _ptr(dists)))
+        else:
+            check(self.lib.lance_hip_flat_topk_range(self.h, dt, METRICS[metric], _ptr(x), _ptr(rid), n, d, _ptr(q), nq, k, *rng,
+                                                     _ptr(ids), _ptr(dists)))
         return ids, dists
 
     def multivec_distance(self, values, offsets, q, metric="cosine"):
@@ -516,9 +525,11 @@ class Engine:
                                                    _ptr(dists)))
         return dists
 
-    def multivec_topk(self, values, offsets, q, k, metric="cosine", row_ids=None):
+    def multivec_topk(self, values, offsets, q, k, metric="cosine", row_ids=None, lower=None, upper=None):
         """exhaustive KNN of one multivector query over a multivector column -> (ids [k] int64, distances [k]) sorted by
-        (distance, row id); slots beyond the number of rows hold id -1 and distance +inf, as flat_topk's do"""
+        (distance, row id); slots beyond the number of rows hold id -1 and distance +inf, as flat_topk's do.
+        lower / upper: distance range on the rows' multivector distances, with flat_topk's semantics (a None bound is not tested)"""
+        rng = _flat_range_args(lower, upper)
         m, off = check_multivector(values, offsets, q, metric, k)
         n = off.size - 1
         if row_ids is not None and int(row_ids.shape[0]) != n:
@@ -530,8 +541,12 @@ class Engine:
         ids = torch.empty(k, dtype=torch.int64, device=v.device)
         dists = torch.empty(k, dtype=torch.float32, device=v.device)
         torch.cuda.synchronize()
-        check(self.lib.lance_hip_flat_multivec_topk(self.h, dt, METRICS[m], _ptr(v), _ptr(od), _ptr(rid), n, v.shape[1], _ptr(qd),
-                                                    qd.shape[0], k, _ptr(ids), _ptr(dists)))
+        if rng is None:
+            check(self.lib.lance_hip_flat_multivec_topk(self.h, dt, METRICS[m], _ptr(v), _ptr(od), _ptr(rid), n, v.shape[1], _ptr(qd),
+                                                        qd.shape[0], k, _ptr(ids), _ptr(dists)))
+        else:
+            check(self.lib.lance_hip_flat_multivec_topk_range(self.h, dt, METRICS[m], _ptr(v), _ptr(od), _ptr(rid), n, v.shape[1], _ptr(qd),
+                                                              qd.shape[0], k, *rng, _ptr(ids), _ptr(dists)))
         return ids, dists
 
     def multivec_xtr_score(self, cand_ids, cand_dists, q_offsets, k_out):
@@ -778,6 +793,17 @@ def _range_f32(lower, upper):
     lo = float(np.finfo(np.float32).min) if lower is None else float(np.float32(lower))
     hi = float(np.finfo(np.float32).max) if upper is None else float(np.float32(upper))
     return lo, hi
+
+
+def _flat_range_args(lower, upper):
+    """flat-scan distance range -> None (no range: the un-ranged entry point) or (has_lower, lower, has_upper, upper) as
+    lance_hip_flat_topk_range takes them.  The bounds are rounded to f32 (Query::lower_bound: Option<f32>); an absent bound is
+    absent -- not the largest finite f32, which is what _range_f32 gives the IVF entry points."""
+    if lower is None and upper is None:
+        return None
+    lo = 0.0 if lower is None else float(np.float32(lower))
+    hi = 0.0 if upper is None else float(np.float32(upper))
+    return int(lower is not None), lo, int(upper is not None), hi
 
 
 # ---- the index handles ---------------------------------------------------------------------------------------------------------------

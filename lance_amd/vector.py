@@ -1119,17 +1119,35 @@ def validate_vector_index(index, vectors, refine_factor=5, sample_size=None, pas
     return passes, total
 
 
-def flat_knn(x, q, k=10, metric="l2", engine=None, prefilter=None):
+def _flat_distance_range(distance_range):
+    """distance_range of the flat scans -> {} or {"lower": .., "upper": ..}.  (None, None) is no range at all."""
+    if distance_range is None:
+        return {}
+    lo, hi = distance_range
+    if lo is None and hi is None:
+        return {}
+    return {"lower": lo, "upper": hi}
+
+
+def flat_knn(x, q, k=10, metric="l2", engine=None, prefilter=None, distance_range=None):
     """Exhaustive KNN (`use_index=False`): (row ids, distances) sorted by (distance, row id).
     prefilter: boolean array over rows; the scan then covers the selected rows only, as the reference's filtered
-    scan feeds KNNVectorDistanceExec (scanner.rs:3386-3411) -- row ids stay those of the full table."""
+    scan feeds KNNVectorDistanceExec (scanner.rs:3386-3411) -- row ids stay those of the full table.
+    distance_range: (lower, upper), either may be None -- the k nearest rows with lower <= d < upper (Scanner::flat_knn's
+    LanceFilterExec between the distance node and the sort, scanner.rs:3336-3412), d being the distance the un-ranged call returns,
+    compared in the total order on f32 (NaN above +inf, the negative NaN of an L2 row with a NaN element below -inf, -0 below +0).
+    A bound that is None is NOT TESTED: (lower, None) keeps +inf and NaN distances, (None, upper) keeps negative-NaN rows.  This
+    differs from IvfFlatIndex.nearest, whose open ends are the largest finite f32 of either sign.  lower above upper is refused;
+    lower == upper returns nothing; missing slots hold id -1 and distance +inf.  With a prefilter the selected rows are gathered
+    and the ranged scan runs over them."""
     eng = engine or default_engine()
+    rng = _flat_distance_range(distance_range)
     if prefilter is not None:
         xt = to_device(x)
         keep = torch.nonzero(to_device(np.ascontiguousarray(prefilter, dtype=bool)) if not isinstance(prefilter, torch.Tensor)
                              else prefilter.to(xt.device)).reshape(-1)
-        return eng.flat_topk(xt[keep].contiguous(), q, k, _normalize_metric_type(metric), row_ids=keep)
-    ids, dists = eng.flat_topk(x, q, k, _normalize_metric_type(metric))
+        return eng.flat_topk(xt[keep].contiguous(), q, k, _normalize_metric_type(metric), row_ids=keep, **rng)
+    ids, dists = eng.flat_topk(x, q, k, _normalize_metric_type(metric), **rng)
     return ids, dists
 
 
@@ -1141,10 +1159,12 @@ def multivector_distance(values, offsets, q, metric="cosine", engine=None):
     return (engine or default_engine()).multivec_distance(values, offsets, q, metric)
 
 
-def multivector_flat_knn(values, offsets, q, k=10, metric="cosine", engine=None, prefilter=None, row_ids=None):
+def multivector_flat_knn(values, offsets, q, k=10, metric="cosine", engine=None, prefilter=None, row_ids=None, distance_range=None):
     """Exhaustive KNN of one multivector query over a multivector column: (row ids [k], distances [k]) sorted by (distance, row id)
     (the flat scan of a List column, lance-index flat.rs:129-133).  prefilter: boolean array over rows, as in flat_knn -- the scan
-    covers the selected rows, the ids stay those of the full table (row_ids, or the row index)."""
+    covers the selected rows, the ids stay those of the full table (row_ids, or the row index).
+    distance_range: (lower, upper) on the rows' multivector distances, with flat_knn's semantics (a None bound is not tested)."""
+    rng = _flat_distance_range(distance_range)
     _, off = check_multivector(values, offsets, q, metric, k)
     n = off.size - 1
     mask = None
@@ -1156,7 +1176,7 @@ def multivector_flat_knn(values, offsets, q, k=10, metric="cosine", engine=None,
         raise ValueError(f"row_ids must hold one id per row ({n}), got {int(row_ids.shape[0])}")
     eng = engine or default_engine()
     if mask is None:
-        return eng.multivec_topk(values, offsets, q, k, metric, row_ids=row_ids)
+        return eng.multivec_topk(values, offsets, q, k, metric, row_ids=row_ids, **rng)
     # the selected rows' vectors, gathered on the device (plumbing): the scan sees a column of its own
     vt = values.to(to_device(off).device) if isinstance(values, torch.Tensor) else to_device(values)
     od = to_device(off)
@@ -1167,7 +1187,7 @@ def multivector_flat_knn(values, offsets, q, k=10, metric="cosine", engine=None,
     total = int(sub_off[-1])
     src = torch.repeat_interleave(od[:-1][keep] - sub_off[:-1], lens) + torch.arange(total, device=od.device)
     rid = keep if row_ids is None else to_device(row_ids, torch.int64)[keep]
-    return eng.multivec_topk(vt[src].contiguous(), sub_off.cpu().numpy(), q, k, metric, row_ids=rid)
+    return eng.multivec_topk(vt[src].contiguous(), sub_off.cpu().numpy(), q, k, metric, row_ids=rid, **rng)
 
 
 class IvfPqMultivectorIndex:
