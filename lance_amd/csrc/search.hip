@@ -1029,21 +1029,29 @@ __global__ __launch_bounds__(256) void refine_u8_kernel(const float *__restrict_
 //  - rows: eight lanes x 16 bytes cover one 128-byte block of a row, so a wave-instruction reads 8 whole (blocks of) rows; all 16
 //    instructions of a query's 128 slots are issued before the first is consumed.  Rows shorter than a block (d = 16, 48, the last block of
 //    d = 144, 272) use the first d / 16 lanes of the group: a lane never reads outside its row.
-//  - the loaded blocks pass through a 64-row x 128 B wave-local LDS tile (ds_write_b128, 16-byte chunks xor-swizzled by (row >> 1) & 7 so
+//  - the loaded blocks pass through a 32-row x 128 B wave-local LDS tile (ds_write_b128, 16-byte chunks xor-swizzled by (row >> 1) & 7 so
 //    that the reads below are conflict-free) and are read back in the layout of the kernel above: lane h of a pair takes the bytes
-//    [8h, 8h+8) of every 16-element chunk.  The arithmetic is that kernel's, literally: no extra VALU, the same bits.
+//    [8h, 8h+8) of every 16-element chunk.  The arithmetic is that kernel's, literally: no extra VALU, the same bits.  The tile is only
+//    a transposition buffer -- the 16 loads wait in registers -- so it holds one round of 32 slots at a time, four rounds per block.
 //  - a query belongs to one wave (4 queries per workgroup, none shared): no __syncthreads; LDS operations of a wave execute in order.
-//    LDS per wave: 8 KB tile + 1 KB row offsets + 4d bytes of query = 9.5 KB at d = 128: 16 queries in flight per CU (79 VGPRs would
-//    allow 24).  Rows longer than a block (d > 128) keep 32 accumulators live across the blocks: 137 VGPRs, 12 queries per CU.
+//    LDS per wave: 4 KB tile + 1 KB row offsets + 4d bytes of query = 5.5 KB at d = 128: six workgroups = 24 queries in flight per CU,
+//    which is what the kernel's 80 VGPRs allow (with 48 loaded registers still waiting during the first round the ids of a lane's two
+//    slots did not fit beside them: 84; they wait in the row offsets' LDS instead, which is dead once the loads are issued).  Rows
+//    longer than a block (d > 128) keep 32 accumulators live across the blocks: 136 VGPRs, 12 queries per CU.
 //  - the selection ranks only the slots at or under the got-th smallest key (found by a 32-step bit search on ballots), not P against
 //    P (at the code).  The same kernel with the rank over the live slots instead: 0.077 ms against the pair kernel's 0.068 and this
 //    one's 0.050 (scripts/variants/refine_rows_count_rank.patch).
-// Rows longer than 1,792 elements (the workgroup's 64 KB of LDS) and lists longer than 128 stay with the kernel above.
+// Rows longer than 1,792 elements (RR_MAX_D: what 64 KB of LDS held with a 64-row tile; the dispatch did not move with the tile) and
+// lists longer than 128 stay with the kernel above.
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 constexpr int RR_WAVES = 4;        // queries per workgroup
 constexpr int RR_SLOTS = 128;      // candidates per query
-static size_t refine_rows_lds_per_wave(int d) { return 64 * 128 + RR_SLOTS * 8 + (size_t)d * 4; }
+constexpr int RR_TILE = 32 * 128;  // the wave's transposition tile: 32 rows x 128 B
+constexpr int RR_MAX_D = 1792;     // longer rows stay with the pair kernel
+static size_t refine_rows_lds_per_wave(int d) { return RR_TILE + RR_SLOTS * 8 + (size_t)d * 4; }
+static_assert(RR_TILE >= RR_SLOTS * 4, "the keys go over the tile once the rows are consumed");
+static_assert((RR_TILE + RR_SLOTS * 8 + (size_t)RR_MAX_D * 4) * RR_WAVES <= 64 * 1024, "a workgroup's LDS");
 
 template <int METRIC, bool ONE>      // ONE: d <= 128, a row is one block -- no accumulator is live while the loads are issued
 __global__ __launch_bounds__(64 * RR_WAVES, ONE ? 4 : 3) void refine_rows_u8_kernel(const float *__restrict__ q, int d, const uint8_t *__restrict__ raw, uint64_t n_raw,
@@ -1057,8 +1065,8 @@ __global__ __launch_bounds__(64 * RR_WAVES, ONE ? 4 : 3) void refine_rows_u8_ker
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // in an SGPR: the count and every branch on it stay scalar
   const int qi = blockIdx.x * RR_WAVES + wv;
   if (qi >= nq) return;      // wave-uniform, and no workgroup barrier below
-  char *tile = smem + (size_t)wv * lds_per_wave;                      // [64][128 B], swizzled
-  uint64_t *roff = reinterpret_cast<uint64_t *>(tile + 64 * 128);    // [RR_SLOTS] byte offset of the slot's row
+  char *tile = smem + (size_t)wv * lds_per_wave;                      // [32][128 B], swizzled
+  uint64_t *roff = reinterpret_cast<uint64_t *>(tile + RR_TILE);     // [RR_SLOTS] byte offset of the slot's row
   f4 *qs4 = reinterpret_cast<f4 *>(roff + RR_SLOTS);                  // [d / 4] the query
   uint32_t *key = reinterpret_cast<uint32_t *>(tile);                 // [RR_SLOTS], over the tile once the rows are consumed
   // the ids in flight with the count and the query; slots beyond the count are masked after the loads come back.  Lane l keeps the
@@ -1099,40 +1107,43 @@ __global__ __launch_bounds__(64 * RR_WAVES, ONE ? 4 : 3) void refine_rows_u8_ker
         for (int j = 0; j < 8; ++j)
           if (hf * 64 + j * 8 < c) st[hf][j] = *reinterpret_cast<const u32x4 *>(src + roff[hf * 64 + j * 8 + g]);
     }
+    if constexpr (ONE) {      // the row offsets are dead once the loads are issued: the ids wait in their place while the rounds need the registers
+      __builtin_amdgcn_wave_barrier();
+      roff[lane] = r_lo; roff[lane + 64] = r_hi;
+    }
+    // four rounds of 32 slots through the tile: write (the registers loaded above), consume, and the next round overwrites it
 #pragma unroll
-    for (int hf = 0; hf < 2; ++hf)
-      if (hf * 64 < c) {
+    for (int t = 0; t < 4; ++t)
+      if (t * 32 < c) {
         if (p < nb) {
 #pragma unroll
-          for (int j = 0; j < 8; ++j)
-            if (hf * 64 + j * 8 < c) *reinterpret_cast<u32x4 *>(tile + j * 1024 + (w0 ^ ((j & 1) * 64))) = st[hf][j];
+          for (int j = 0; j < 4; ++j)
+            if (t * 32 + j * 8 < c) *reinterpret_cast<u32x4 *>(tile + j * 1024 + (w0 ^ ((j & 1) * 64))) = st[t >> 1][(t & 1) * 4 + j];
         }
         __builtin_amdgcn_wave_barrier();
+        {
+          float(&a)[8] = acc[t];
+          const f4 *xp = qs4 + 2 * h;
 #pragma unroll
-        for (int ps = 0; ps < 2; ++ps)
-          if (hf * 64 + ps * 32 < c) {
-            float(&a)[8] = acc[hf * 2 + ps];
-            const f4 *xp = qs4 + 2 * h;
+          for (int cc = 0; cc < 8; ++cc)
+            if (cc < nb) {
+              const u32x2 yb = *reinterpret_cast<const u32x2 *>(tile + rd0 + ((cc ^ s7) << 4));
+              const f4 x0 = xp[(c0 + cc) * 4], x1 = xp[(c0 + cc) * 4 + 1];
 #pragma unroll
-            for (int cc = 0; cc < 8; ++cc)
-              if (cc < nb) {
-                const u32x2 yb = *reinterpret_cast<const u32x2 *>(tile + ps * 4096 + rd0 + ((cc ^ s7) << 4));
-                const f4 x0 = xp[(c0 + cc) * 4], x1 = xp[(c0 + cc) * 4 + 1];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                  const float y0 = (float)((yb.x >> (8 * e)) & 255u), y1 = (float)((yb.y >> (8 * e)) & 255u);
-                  if constexpr (METRIC == METRIC_DOT) {
-                    a[e] += x0[e] * y0;
-                    a[4 + e] += x1[e] * y1;
-                  } else {
-                    const float d0 = x0[e] - y0, d1 = x1[e] - y1;
-                    a[e] += d0 * d0;
-                    a[4 + e] += d1 * d1;
-                  }
+              for (int e = 0; e < 4; ++e) {
+                const float y0 = (float)((yb.x >> (8 * e)) & 255u), y1 = (float)((yb.y >> (8 * e)) & 255u);
+                if constexpr (METRIC == METRIC_DOT) {
+                  a[e] += x0[e] * y0;
+                  a[4 + e] += x1[e] * y1;
+                } else {
+                  const float d0 = x0[e] - y0, d1 = x1[e] - y1;
+                  a[e] += d0 * d0;
+                  a[4 + e] += d1 * d1;
                 }
               }
-          }
-        __builtin_amdgcn_wave_barrier();      // the next half (or block) overwrites the tile
+            }
+        }
+        __builtin_amdgcn_wave_barrier();      // the next round (or block) overwrites the tile
       }
   }
   uint32_t kreg[4];
@@ -1159,6 +1170,7 @@ __global__ __launch_bounds__(64 * RR_WAVES, ONE ? 4 : 3) void refine_rows_u8_ker
   }
   __builtin_amdgcn_wave_barrier();
   const uint32_t k_lo = key[lane], k_hi = key[lane + 64];      // the keys beside their ids: slots lane and lane + 64
+  if constexpr (ONE) { r_lo = roff[lane]; r_hi = roff[lane + 64]; }
   if (cand_exact) {
     if (lane < keff) cand_exact[(int64_t)qi * keff + lane] = (lane < c && k_lo != 0xFFFFFFFFu) ? key_to_float(k_lo) : INFINITY;
     if (lane + 64 < keff) cand_exact[(int64_t)qi * keff + lane + 64] = (lane + 64 < c && k_hi != 0xFFFFFFFFu) ? key_to_float(k_hi) : INFINITY;
@@ -1544,7 +1556,7 @@ int launch_refine(lance_hip_ctx *ctx, const lance_hip_index *ix, const float *q,
         // Longer lists (the IVF_SQ / IVF_RQ re-ranking, up to 768) keep the pair kernel: 128 slots are what a wave's tile and rank hold.
         static const bool u8v1 = getenv("LANCE_HIP_REFINE_U8_V1") != nullptr;
         const size_t lds_wave = refine_rows_lds_per_wave(d);
-        if (!u8v1 && keff <= RR_SLOTS && ix->n_raw > 0 && lds_wave * RR_WAVES <= 64 * 1024) {
+        if (!u8v1 && keff <= RR_SLOTS && ix->n_raw > 0 && d <= RR_MAX_D) {
           const dim3 grid((unsigned)cdiv(nq, RR_WAVES));
           ctx->count_stage("refine_rows");      // count:refine_rows -- which of the two u8 kernels answered
           auto kern = ix->metric == LANCE_HIP_DOT ? (d <= 128 ? refine_rows_u8_kernel<METRIC_DOT, true> : refine_rows_u8_kernel<METRIC_DOT, false>)

@@ -532,14 +532,44 @@ __global__ __launch_bounds__(BS) void ivfpq_qrescan_kernel(QmergeArgs a) {
 // One workgroup of BS lanes per query.  The kernel is latency-bound (dependent position -> code -> codebook loads, selection
 // rounds), so what counts is the number of queries in flight, not lanes per query: BS = 128 is the smallest group the
 // threshold machinery allows (the k-th smallest of one value per lane needs BS >= k * refine, at most 128 here).
+// LH_QM_WAVES: the waves per SIMD the merge kernels are compiled for.  Six (80 VGPRs) cost the one-group kernel 8 spilled registers
+// and were never all resident -- LDS held 11 workgroups of two waves on a CU; five (91 VGPRs, no scratch, ten workgroups) measured
+// faster alone and under three contexts (profiles/tail_occupancy_notes.txt).
 #ifndef LH_QM_WAVES
-#define LH_QM_WAVES 6
+#define LH_QM_WAVES 5
 #endif
 #if LH_QM_WAVES > 0
 #define LH_QM_BOUNDS(BS) __launch_bounds__(BS, (SD <= 8 && MU == 1 ? LH_QM_WAVES : 4))
 #else
 #define LH_QM_BOUNDS(BS) __launch_bounds__(BS)
 #endif
+// The histogram of pass A and the compacted survivors of pass B share their LDS: the histogram is dead once the cut is written and the
+// barrier behind it has passed, and pass B's first write comes after that barrier (both merge kernels; with several chunks pass A runs
+// through all of them before the cut, and neither the pool section in front nor the sort behind touches either).
+constexpr int QM_LC = 512;       // compacted survivors per chunk
+union QmCutOverlay {
+  uint32_t hist[512];
+  struct { uint32_t pos[QM_LC]; uint8_t rr[QM_LC]; } l;
+};
+// the static LDS of ivfpq_qmerge1g_kernel, in one piece so that its size is pinned below
+template <int BS>
+struct Qm1gShared {
+  static constexpr int CAP = BS == 128 ? 512 : 1024;   // (key, pos) entries under selection
+  uint32_t ckey[CAP], cpos[CAP], sorted[BS], misc[8];
+  uint32_t cnt[QM_G], part[QM_G];
+  f2 yz[QM_G];
+  QmCutOverlay cut_ov;
+  uint32_t cut, l_cnt;
+  int amb;
+};
+// dynamic LDS of both merge kernels: the staged residuals of min(qm_g, nprobes) probes; later the (rowid, key, position) sort buffers
+static size_t qmerge_lds_bytes(int qm_g, int nprobes, int dpad) {
+  return std::max((size_t)std::min(qm_g, nprobes) * dpad * 4, (size_t)SCAN_LCAP * 16);
+}
+// twelve workgroups on a CU (160 KiB of LDS) at d = 128 with up to 10 probes, whichever the allocation granule: 163,840 / 12, rounded
+// down to a multiple of 1,280 bytes
+static_assert(sizeof(Qm1gShared<128>) == 7472 && sizeof(Qm1gShared<128>) + 10 * 128 * 4 <= 12800, "ivfpq_qmerge1g_kernel: LDS per workgroup");
+
 template <int SD, int MU, int BS, bool DOT = false>
 __global__ LH_QM_BOUNDS(BS) void ivfpq_qmerge_kernel(QmergeArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -562,9 +592,10 @@ __global__ LH_QM_BOUNDS(BS) void ivfpq_qmerge_kernel(QmergeArgs a) {
   // survivor with S > B + hi + lo is farther than keff others and cannot be in the answer: a 512-bin histogram of the sums
   // gives B, and only the survivors under the cut (about 1.1 x keff of the ~2.5 x keff) are re-evaluated exactly -- compacted
   // first, so that the lanes of a round are all busy.
-  constexpr int QM_LC = 512;                       // compacted survivors per chunk
-  __shared__ uint32_t s_hist[512], l_pos[QM_LC], s_cut, l_cnt;
-  __shared__ uint8_t l_rr[QM_LC];
+  __shared__ QmCutOverlay s_ov;                    // the histogram, then (behind the cut's barrier) the compacted survivors
+  __shared__ uint32_t s_cut, l_cnt;
+  uint32_t *const s_hist = s_ov.hist, *const l_pos = s_ov.l.pos;
+  uint8_t *const l_rr = s_ov.l.rr;
   const SelectOut &o = a.o;
   const int q = blockIdx.x;
   if (o.flags[q] & FLAG_OVERFLOW) return;   // the exact kernel recomputes this query
@@ -819,19 +850,21 @@ __global__ LH_QM_BOUNDS(BS) void ivfpq_qmerge1g_kernel(QmergeArgs a) {
   constexpr int M = MU * 16;
   constexpr int QV = SD / 4;
   constexpr int QMET = DOT ? METRIC_DOT : METRIC_L2;
-  constexpr int CAP = BS == 128 ? 512 : 1024;   // (key, pos) entries under selection
+  constexpr int CAP = Qm1gShared<BS>::CAP;      // (key, pos) entries under selection
   static_assert(BS >= SCAN_MAX_KEFF, "tighten_bs selects among one value per lane");
-  __shared__ uint32_t ckey[CAP], cpos[CAP], sorted[BS], misc[8];
+  __shared__ Qm1gShared<BS> sh;
+  uint32_t *const ckey = sh.ckey, *const cpos = sh.cpos, *const sorted = sh.sorted, *const misc = sh.misc;
   uint64_t *rid = reinterpret_cast<uint64_t *>(smem);                    // [SCAN_LCAP]  (the dynamic region holds the staged residuals first)
   uint32_t *skey = reinterpret_cast<uint32_t *>(rid + SCAN_LCAP);        // [SCAN_LCAP]
   uint32_t *spos = skey + SCAN_LCAP;                                     // [SCAN_LCAP]
-  constexpr int QM_LC = 512;                       // survivors per chunk
   constexpr int SPL = QM_LC / BS;                  // survivors per lane per chunk (registers)
-  __shared__ uint32_t s_cnt[QM_G], s_part[QM_G];
-  __shared__ f2 s_yz[QM_G];
-  __shared__ int s_amb;
-  __shared__ uint32_t s_hist[512], l_pos[QM_LC], s_cut, l_cnt;
-  __shared__ uint8_t l_rr[QM_LC];
+  uint32_t *const s_cnt = sh.cnt, *const s_part = sh.part;
+  f2 *const s_yz = sh.yz;
+  int &s_amb = sh.amb;
+  // the histogram is dead behind the cut's barrier; pass B's compaction, which starts after it, takes its place (QmCutOverlay)
+  uint32_t *const s_hist = sh.cut_ov.hist, *const l_pos = sh.cut_ov.l.pos;
+  uint8_t *const l_rr = sh.cut_ov.l.rr;
+  uint32_t &s_cut = sh.cut, &l_cnt = sh.l_cnt;
   const SelectOut &o = a.o;
   const int q = blockIdx.x;
   const int np = a.nprobes;                        // <= a.qm_g <= QM_G (launcher)
@@ -1285,8 +1318,21 @@ static void launch_qmerge_mu(lance_hip_ctx *ctx, const QmergeArgs &a, unsigned n
   // segments a batch lists, ~5 per 10,000 queries there, are single-workgroup latency in front of the merge)
   const unsigned rgrid = (unsigned)std::min<uint64_t>((uint64_t)nq * a.nprobes, (uint64_t)ctx->num_cus);
   hipLaunchKernelGGL((ivfpq_qrescan_kernel<SD, MU, 1024, DOT>), dim3(rgrid), dim3(1024), lds_rescan, ctx->stream, a);
-  // staged residuals of min(QM_G, nprobes) probes; later the (rowid, key, position) sort buffers
-  const size_t lds = std::max((size_t)std::min<int>(a.qm_g, a.nprobes) * dpad * 4, (size_t)SCAN_LCAP * 16);
+  const size_t lds = qmerge_lds_bytes(a.qm_g, a.nprobes, dpad);
+#ifdef LH_QM_OCC      // builds with -DLH_QM_OCC only (scripts/build_variant.sh): what the runtime answers for the merge's workgroups per CU
+  {
+    static bool told = false;
+    if (!told && a.nprobes <= a.qm_g) {
+      told = true;
+      int nb = -1;
+      (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, ivfpq_qmerge1g_kernel<SD, MU, 128, DOT>, 128, lds);
+      hipFuncAttributes fa{};
+      (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(ivfpq_qmerge1g_kernel<SD, MU, 128, DOT>));
+      fprintf(stderr, "[qm occ] ivfpq_qmerge1g_kernel<%d, %d, 128, %d>: static LDS %zu + dynamic %zu B, %d registers, scratch %zu B -> %d workgroups per CU\n", SD, MU,
+              (int)DOT, (size_t)fa.sharedSizeBytes, lds, fa.numRegs, (size_t)fa.localSizeBytes, nb);
+    }
+  }
+#endif
   // one residual group (nprobes <= qm_g <= 16): the kernel with the short dependent chain; LANCE_HIP_QMERGE_V1=1 keeps the general one (A/B)
   static const bool v1 = getenv("LANCE_HIP_QMERGE_V1") != nullptr;
   if (!v1 && a.nprobes <= a.qm_g) {
