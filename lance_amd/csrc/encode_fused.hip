@@ -135,6 +135,7 @@ int launch_encode_fused(lance_hip_ctx *ctx, int dtype, const void *x, int64_t n,
   if (n == 0) return LANCE_HIP_OK;
   const int sd = d / m;
   ScopedTimer t(ctx, "encode_fused");
+  ScopedTimer tl(ctx, "lane_encode");      // the same launch under its own name: encode_fused is shared with the matrix-core encoder
   if (d == 128 && sd == 4) launch_ef_tx<128, 4>(ctx, dtype, x, n, cent, part_ids, residual, codebook, codes);
   else if (d == 128 && sd == 8) launch_ef_tx<128, 8>(ctx, dtype, x, n, cent, part_ids, residual, codebook, codes);
   else if (d == 128 && sd == 16) launch_ef_tx<128, 16>(ctx, dtype, x, n, cent, part_ids, residual, codebook, codes);

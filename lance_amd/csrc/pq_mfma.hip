@@ -371,6 +371,7 @@ int launch_pq_mfma_encode(lance_hip_ctx *ctx, int dtype, const void *x, int64_t 
   if (!fb_cnt || !fb_items) return LANCE_HIP_ENOMEM;
   const size_t es = dtype == LANCE_HIP_F16 ? 2 : (dtype == LANCE_HIP_I8 ? 1 : 4);
   ScopedTimer t(ctx, "encode_fused");
+  ScopedTimer tp(ctx, "pq_mfma_encode");      // the same launches under their own name: encode_fused is shared with the lane-per-row encoder
   for (int64_t r0 = 0; r0 < n; r0 += chunk) {
     const int64_t rows = std::min<int64_t>(chunk, n - r0);
     PqmArgs a;
