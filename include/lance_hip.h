@@ -464,6 +464,17 @@ int lance_hip_flat_multivec_topk_range(lance_hip_ctx *ctx, int dtype, int metric
                                        uint32_t k, int has_lower, float lower, int has_upper, float upper, uint64_t *ids,
                                        float *dists);
 
+/* ... for a batch of n_queries multivector queries: q [q_offsets[n_queries]][d] in the column's element type (device), query b holds
+ * the vectors q_offsets[b] .. q_offsets[b + 1] - 1 (q_offsets: HOST, as lance_hip_multivec_xtr_score takes them; 1..256 vectors per
+ * query, 1..65535 queries).  ids / dists [n_queries][k]: bit for bit what lance_hip_flat_multivec_topk[_range] returns per query.
+ * Cosine without a range, d <= 256: a MaxSim surrogate on the matrix cores filters the rows and only the survivors are evaluated
+ * exactly (multivec_batch.hip); everything else is the single-query scan, query by query, inside the call.  survivors (host
+ * uint32 [n_queries], or NULL): the rows evaluated exactly for each query, n_rows where the exact scan answered it. */
+int lance_hip_flat_multivec_topk_batch(lance_hip_ctx *ctx, int dtype, int metric, const void *values, const uint64_t *offsets,
+                                       const uint64_t *row_ids, uint64_t n_rows, uint32_t d, const void *q, const uint64_t *q_offsets,
+                                       uint32_t n_queries, uint32_t k, int has_lower, float lower, int has_upper, float upper,
+                                       uint64_t *ids, float *dists, uint32_t *survivors);
+
 /* ---- multivector ANN: per-query-vector candidate lists joined by row id and scored with XTR-style imputation ----------
  * (Scanner::multivec_ann, scanner.rs:3471-3552; MultivectorScoringExec, knn.rs:1132-1329).  The index is an ordinary IVF_PQ index
  * over the FLATTENED vectors of the column whose row_ids repeat the row's id once per vector; one ANN search per query vector

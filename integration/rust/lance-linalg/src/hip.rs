@@ -162,6 +162,11 @@ extern "C" {
     /// the same followed by SortExec(dist, rowid).fetch(k) (flat.rs:129-133); row_ids NULL -> row index
     pub fn lance_hip_flat_multivec_topk(ctx: *mut LanceHipCtx, dtype: i32, metric: i32, values: *const c_void, offsets: *const u64,
         row_ids: *const u64, n_rows: u64, d: u32, q: *const c_void, nqv: u32, k: u32, ids: *mut u64, dists: *mut f32) -> i32;
+    /// lance_hip_flat_multivec_topk for a batch of `n_queries` multivector queries: `q` [q_offsets[n_queries]][d] (device), `q_offsets`
+    /// on the HOST; `ids` / `dists` [n_queries][k], bit for bit the single call's per query.  `survivors`: host u32 [n_queries] or null.
+    pub fn lance_hip_flat_multivec_topk_batch(ctx: *mut LanceHipCtx, dtype: i32, metric: i32, values: *const c_void, offsets: *const u64,
+        row_ids: *const u64, n_rows: u64, d: u32, q: *const c_void, q_offsets: *const u64, n_queries: u32, k: u32, has_lower: i32,
+        lower: f32, has_upper: i32, upper: f32, ids: *mut u64, dists: *mut f32, survivors: *mut u32) -> i32;
     /// MultivectorScoringExec (knn.rs:1132-1329) for a batch of `b` multivector queries: `cand_ids` / `cand_dists` [q_offsets[b]][keff]
     /// (device) hold one candidate list per query vector in (dist, rowid) order, `q_offsets` [b + 1] is a HOST array; the lists are
     /// joined in query-vector order and the `k_out` best rows by (distance, row id) written to `ids` / `dists` [b][k_out] (device).

@@ -39,7 +39,7 @@ SYMBOLS = [
     "lance_hip_ivfpq_search_candidates",
     "lance_hip_search_stats", "lance_hip_ivfpq_search_filtered", "lance_hip_ivfpq_search_filtered_range",
     "lance_hip_flat_topk", "lance_hip_flat_topk_range", "lance_hip_multivec_distance", "lance_hip_flat_multivec_topk",
-    "lance_hip_flat_multivec_topk_range",
+    "lance_hip_flat_multivec_topk_range", "lance_hip_flat_multivec_topk_batch",
     "lance_hip_multivec_xtr_score", "lance_hip_ivfpq_multivec_search", "lance_hip_ivfflat_create", "lance_hip_ivfflat_search", "lance_hip_ivfflat_search_filtered",
     "lance_hip_ivfflat_search_range",
     "lance_hip_sq_bounds", "lance_hip_sq_encode", "lance_hip_sq_distance", "lance_hip_ivfsq_create", "lance_hip_ivfsq_search", "lance_hip_ivfsq_search_filtered",
@@ -155,6 +155,7 @@ def load():
         "lance_hip_multivec_distance": (i32, [vp, i32, i32, vp, vp, u64, u32, vp, u32, vp]),
         "lance_hip_flat_multivec_topk": (i32, [vp, i32, i32, vp, vp, vp, u64, u32, vp, u32, u32, vp, vp]),
         "lance_hip_flat_multivec_topk_range": (i32, [vp, i32, i32, vp, vp, vp, u64, u32, vp, u32, u32, i32, f32, i32, f32, vp, vp]),
+        "lance_hip_flat_multivec_topk_batch": (i32, [vp, i32, i32, vp, vp, vp, u64, u32, vp, vp, u32, u32, i32, f32, i32, f32, vp, vp, vp]),
         "lance_hip_multivec_xtr_score": (i32, [vp, vp, vp, vp, u32, u32, u32, vp, vp]),
         "lance_hip_ivfpq_multivec_search": (i32, [vp, vp, vp, vp, u32, u32, u32, u32, u32, vp, u64, vp, vp]),
         "lance_hip_ivfflat_create": (i32, [vp, i32, i32, u32, vp, u32, vp, vp, vp, u64, C.POINTER(vp)]),

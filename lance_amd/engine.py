@@ -549,6 +549,40 @@ class Engine:
                                                               qd.shape[0], k, *rng, _ptr(ids), _ptr(dists)))
         return ids, dists
 
+    def multivec_topk_batch(self, values, offsets, q, q_offsets, k, metric="cosine", row_ids=None, lower=None, upper=None,
+                            return_survivors=False):
+        """exhaustive KNN of a BATCH of B multivector queries over a multivector column: q [sum nqv][d], the vectors of query b are
+        rows q_offsets[b] .. q_offsets[b + 1] - 1 (the pair arrow_io.multivector_from_arrow returns for a List<FixedSizeList> array of
+        queries) -> (ids [B][k] int64, distances [B][k]), row b bit for bit multivec_topk's answer for query b.  Cosine without a
+        range, d <= 256: a MaxSim surrogate on the matrix cores filters the rows (lance_hip_flat_multivec_topk_batch); everything
+        else runs the single-query scan per query inside the call.  return_survivors: also the rows evaluated exactly per query
+        (int64 numpy [B]; n_rows where the exact scan answered the query)"""
+        rng = _flat_range_args(lower, upper)
+        qoff = check_query_offsets(q_offsets)
+        B = qoff.size - 1
+        if not 1 <= B <= 65535:
+            raise ValueError(f"{B} queries: a batch holds 1..65535")
+        if len(q.shape) != 2 or int(q.shape[0]) != int(qoff[-1]):
+            raise ValueError(f"q must be [{int(qoff[-1])}][d], the vectors of all queries (q_offsets ends at {int(qoff[-1])}), got shape {tuple(q.shape)}")
+        m = off = None
+        for b in range(B):
+            m, off = check_multivector(values, offsets, q[int(qoff[b]):int(qoff[b + 1])], metric, k)
+        n = off.size - 1
+        if row_ids is not None and int(row_ids.shape[0]) != n:
+            raise ValueError(f"row_ids must hold one id per row ({n}), got {int(row_ids.shape[0])}")
+        v, dt = _vec(values)
+        qd = _like(q, v)
+        od = to_device(off, torch.int64)
+        rid = None if row_ids is None else to_device(row_ids, torch.int64)
+        ids = torch.empty((B, k), dtype=torch.int64, device=v.device)
+        dists = torch.empty((B, k), dtype=torch.float32, device=v.device)
+        surv = np.zeros(B, dtype=np.uint32)
+        torch.cuda.synchronize()
+        check(self.lib.lance_hip_flat_multivec_topk_batch(self.h, dt, METRICS[m], _ptr(v), _ptr(od), _ptr(rid), n, v.shape[1], _ptr(qd),
+                                                          qoff.ctypes.data_as(C.c_void_p), B, k, *(rng or (0, 0.0, 0, 0.0)), _ptr(ids), _ptr(dists),
+                                                          surv.ctypes.data_as(C.c_void_p)))
+        return (ids, dists, surv.astype(np.int64)) if return_survivors else (ids, dists)
+
     def multivec_xtr_score(self, cand_ids, cand_dists, q_offsets, k_out):
         """The join and score stage of the multivector ANN search (lance_hip_multivec_xtr_score; MultivectorScoringExec,
         knn.rs:1132-1329) for a batch of B multivector queries: cand_ids / cand_dists [sum nqv][keff] hold one candidate list per

@@ -1163,9 +1163,31 @@ def multivector_flat_knn(values, offsets, q, k=10, metric="cosine", engine=None,
     """Exhaustive KNN of one multivector query over a multivector column: (row ids [k], distances [k]) sorted by (distance, row id)
     (the flat scan of a List column, lance-index flat.rs:129-133).  prefilter: boolean array over rows, as in flat_knn -- the scan
     covers the selected rows, the ids stay those of the full table (row_ids, or the row index).
-    distance_range: (lower, upper) on the rows' multivector distances, with flat_knn's semantics (a None bound is not tested)."""
+    distance_range: (lower, upper) on the rows' multivector distances, with flat_knn's semantics (a None bound is not tested).
+    q may be a list or tuple of B queries [nqv_b][d] (a batch, Engine.multivec_topk_batch): -> ([B][k], [B][k]), row b the answer of
+    the single call for query b; a prefilter's sub-column is gathered once for the whole batch."""
     rng = _flat_distance_range(distance_range)
-    _, off = check_multivector(values, offsets, q, metric, k)
+    batch = isinstance(q, (list, tuple))
+    if batch:
+        if len(q) < 1:
+            raise ValueError("q holds no query: a batch has at least one")
+        for qb in q:
+            if len(getattr(qb, "shape", ())) != 2:
+                raise ValueError(f"every query of a batch must be [nqv][d], got shape {tuple(getattr(qb, 'shape', ()))}")
+            _, off = check_multivector(values, offsets, qb, metric, k)
+        q_offsets = np.concatenate([[0], np.cumsum([int(qb.shape[0]) for qb in q])]).astype(np.int64)
+        if all(isinstance(qb, torch.Tensor) for qb in q):
+            q = torch.cat([qb.reshape(qb.shape[0], -1) for qb in q], 0)
+        else:
+            q = np.concatenate([qb.detach().cpu().numpy() if isinstance(qb, torch.Tensor) else np.asarray(qb) for qb in q], 0)
+    else:
+        _, off = check_multivector(values, offsets, q, metric, k)
+
+    def topk(eng, v, o, rid):
+        if batch:
+            return eng.multivec_topk_batch(v, o, q, q_offsets, k, metric, row_ids=rid, **rng)
+        return eng.multivec_topk(v, o, q, k, metric, row_ids=rid, **rng)
+
     n = off.size - 1
     mask = None
     if prefilter is not None:
@@ -1176,7 +1198,7 @@ def multivector_flat_knn(values, offsets, q, k=10, metric="cosine", engine=None,
         raise ValueError(f"row_ids must hold one id per row ({n}), got {int(row_ids.shape[0])}")
     eng = engine or default_engine()
     if mask is None:
-        return eng.multivec_topk(values, offsets, q, k, metric, row_ids=row_ids, **rng)
+        return topk(eng, values, offsets, row_ids)
     # the selected rows' vectors, gathered on the device (plumbing): the scan sees a column of its own
     vt = values.to(to_device(off).device) if isinstance(values, torch.Tensor) else to_device(values)
     od = to_device(off)
@@ -1187,7 +1209,7 @@ def multivector_flat_knn(values, offsets, q, k=10, metric="cosine", engine=None,
     total = int(sub_off[-1])
     src = torch.repeat_interleave(od[:-1][keep] - sub_off[:-1], lens) + torch.arange(total, device=od.device)
     rid = keep if row_ids is None else to_device(row_ids, torch.int64)[keep]
-    return eng.multivec_topk(vt[src].contiguous(), sub_off.cpu().numpy(), q, k, metric, row_ids=rid, **rng)
+    return topk(eng, vt[src].contiguous(), sub_off.cpu().numpy(), rid)
 
 
 class IvfPqMultivectorIndex:
