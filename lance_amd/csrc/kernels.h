@@ -196,17 +196,6 @@ int ivfpq_scan_merge_pm(lance_hip_ctx *ctx, const lance_hip_index *ix, const Ivf
                         uint64_t *cand_rid, uint32_t *cand_cnt, uint32_t *flags, const uint32_t *allow);
 int find_partitions_f32(lance_hip_ctx *ctx, int metric, const float *qf, uint32_t nq, uint32_t d, const float *cf, uint32_t nlist,
                         uint32_t nprobes, uint32_t *part_ids, float *dists, bool lanes32);   // search.hip
-// sq.hip: SortExec(dist, rowid).fetch(k) over the per-(query, partition) candidate lists of a FlatIndex sub-index scan and the decision
-// which queries the heap replay must answer (sq_merge_kernel) -- shared by IVF_SQ and IVF_RQ (rq.hip), whose scans write the same lists
-struct PairLists {
-  const uint64_t *row_ids;       // [n] by storage position
-  int nprobes, k;
-  uint32_t *pkey, *ppos;         // [nq * nprobes][k] the k best of every pair, sorted by (key, position)
-  uint32_t *pcnt, *pamb;         // [nq * nprobes] entries of the pair; 1 = a row tied with the pair's k-th key was left out
-  uint32_t *flags;               // [nq] out: 1 = replay
-  uint32_t *n_replay;            // [1] replayed queries of the call (incremented)
-};
-int sq_merge_pairs(lance_hip_ctx *ctx, const PairLists &pl, uint32_t nq, uint64_t *ids, float *dists, const char *timer);
 // flat_small.hip: exhaustive KNN for one to four queries in a single streaming pass (*done = false: mass ties, take the batch path)
 bool flat_small_supported(int metric, int dtype, uint32_t d, uint32_t nq, uint32_t k, uint64_t n);
 int flat_topk_small(lance_hip_ctx *ctx, int metric, int dtype, const void *x, const uint64_t *row_ids, uint64_t n, uint32_t d, const float *q,
@@ -291,9 +280,6 @@ int launch_cand_count(lance_hip_ctx *ctx, const uint64_t *ids, uint32_t nq, uint
 int launch_refine(lance_hip_ctx *ctx, const lance_hip_index *ix, const float *q, uint32_t nq, int d, const uint64_t *cand_rid, const uint32_t *cand_cnt,
                   uint32_t keff, uint32_t k, uint64_t *ids, float *dists, uint32_t *flags, float *cand_exact);
 int check_flags(lance_hip_ctx *ctx, const uint32_t *flags, uint32_t nq);
-// sq.hip: the merge step of the wide candidate path (wide_cand.cuh), shared by IVF_SQ and IVF_RQ
-struct WideLists;
-int wide_merge_lists(lance_hip_ctx *ctx, const WideLists &w, uint32_t nq, uint64_t *ids, float *dists, const char *timer);
 const uint8_t *raw_compact_prepare(lance_hip_ctx *ctx, const lance_hip_index *ix);   // search.hip: lossless u8 refine copy (index.h), or nullptr
 
 }  // namespace lh

@@ -17,9 +17,10 @@
 //   filtered   every selected row under a prefilter: the same f32 terms folded by f32::sum (from -0.0)
 //
 // Search: one workgroup per (query, probed partition) prepares that pair's tables in LDS (residual, rotation, the 16-entry table of
-// every 4 dimensions and its u8 quantisation), scans the partition's rows once and keeps the pair's k best (key, storage position),
-// exactly as the IVF_SQ scan does; the per-pair lists go through IVF_SQ's merge kernel (sq.hip: (dist, rowid) order and the replay
-// decision) and flagged queries are replayed through std BinaryHeap's push / pop in storage order.
+// every 4 dimensions and its u8 quantisation), scans the partition's rows once and keeps the pair's k best (key, storage position);
+// the per-pair lists are merged per query by (dist, rowid) with the replay decision, and flagged queries are replayed through std
+// BinaryHeap's push / pop in storage order.  Selection, merge and replay are pair_cand.cuh's, shared with IVF_SQ; this file supplies
+// the preparation and the row distance.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -30,7 +31,7 @@
 #include "index.h"
 #include "kernels.h"
 #include "search_common.cuh"
-#include "wide_cand.cuh"
+#include "pair_cand.cuh"
 
 #pragma clang fp contract(off)
 
@@ -38,8 +39,6 @@ namespace lh {
 
 constexpr uint32_t RQ_MAX_DIM = LANCE_HIP_RQ_MAX_DIM;
 constexpr int RQ_MAX_K = 128;
-constexpr int RQ_BUF = 512;          // candidate buffer of the scan kernel: k kept + one 256-row chunk, padded to a power of two
-static_assert(RQ_MAX_DIM <= 4 * RQ_BUF, "the rotated query borrows the scan kernel's candidate buffer");
 constexpr int RQ_BATCH = 32;         // BATCH_SIZE of sum_4bit_dist_table: rows past the last full batch take the f32 branch
 enum { RQ_PACKED = 0, RQ_REMAINDER = 1, RQ_FILTERED = 2 };
 
@@ -277,192 +276,6 @@ __global__ __launch_bounds__(256) void rq_distance_kernel(const uint8_t *__restr
   }
 }
 
-// ---- IVF_RQ search -----------------------------------------------------------------------------------------------------------
-struct RqArgs {
-  const uint8_t *codes;          // [n][cb] partition-ordered
-  const float *add, *scale;      // [n]
-  const uint64_t *row_ids;       // [n]
-  const uint32_t *part_offsets;  // [nlist+1]
-  const uint32_t *probes;        // [nq][nprobes]
-  const float *pdists;           // [nq][nprobes] dist_q_c of every pair
-  const float *q;                // [nq][d]
-  const float *cent;             // [nlist][d]
-  const float *pt;               // [d][d] rotation, transposed
-  int d, nprobes, k, dot;
-  float sqrt_d;
-  const uint32_t *allow;         // prefilter: one bit per storage position, NULL = none
-  uint32_t *pkey, *ppos;         // [nq * nprobes][k] the k best of every pair, sorted by (key, position)
-  uint32_t *pcnt;                // [nq * nprobes] entries of the pair
-  uint32_t *pamb;                // [nq * nprobes] 1 = a row tied with the pair's k-th key was left out
-  uint32_t *flags;               // [nq] 1 = replay (written by the merge kernel)
-};
-
-struct RqCtl { int cnt; uint32_t thr; uint32_t amb_key; int amb; };
-
-// sort the candidate buffer by (key, storage position) -- bitonic_sort_kr with the position in the row-id slot --, keep the k best;
-// a tie cut at the k-th key is remembered (thresholds only fall, so only the last one can matter)
-__device__ __forceinline__ void rq_sort_truncate(uint32_t *key, uint64_t *spos, uint32_t *pos, RqCtl *ctl, int k) {
-  const int cnt = ctl->cnt;
-  int P = 2;
-  while (P < cnt) P <<= 1;
-  for (int i = cnt + threadIdx.x; i < P; i += 256) { key[i] = 0xFFFFFFFFu; spos[i] = ~0ull; pos[i] = 0xFFFFFFFFu; }
-  __syncthreads();
-  bitonic_sort_kr<256>(key, spos, pos, P);
-  if (threadIdx.x == 0 && cnt > k) {
-    const uint32_t kth = key[k - 1];
-    if (key[k] == kth) { ctl->amb = 1; ctl->amb_key = kth; }
-    ctl->thr = kth;
-    ctl->cnt = k;
-  }
-  __syncthreads();
-}
-
-// dynamic LDS: table 16 d | etab 4 d | spos u64 [RQ_BUF] | key u32 [RQ_BUF] | pos u32 [RQ_BUF] | RqQuery | RqCtl.  The three candidate
-// arrays are contiguous (16 RQ_BUF bytes); during the preparation their first 4 d bytes hold the rotated query (d <= 4 RQ_BUF = RQ_MAX_DIM).
-__global__ __launch_bounds__(256) void rq_scan_kernel(RqArgs a) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int d = a.d, cb = d / 8;
-  float *table = reinterpret_cast<float *>(smem);
-  uint8_t *etab = reinterpret_cast<uint8_t *>(smem + 16 * (size_t)d);
-  uint64_t *spos = reinterpret_cast<uint64_t *>(smem + 20 * (size_t)d);
-  uint32_t *key = reinterpret_cast<uint32_t *>(spos + RQ_BUF);
-  uint32_t *pos = key + RQ_BUF;
-  RqQuery *h = reinterpret_cast<RqQuery *>(pos + RQ_BUF);
-  RqCtl *ctl = reinterpret_cast<RqCtl *>(h + 1);
-  const int pair = blockIdx.x;
-  const int qi = pair / a.nprobes;
-  const uint32_t part = a.probes[pair];
-  const uint32_t r0 = a.part_offsets[part], r1 = a.part_offsets[part + 1];
-  if (threadIdx.x == 0) { ctl->cnt = 0; ctl->thr = 0xFFFFFFFFu; ctl->amb_key = 0; ctl->amb = 0; }
-  if (r1 > r0) {     // (uniform) an empty partition needs no tables
-    rq_prepare<256>(a.q + (int64_t)qi * d, a.cent + (int64_t)part * d, a.pt, d, a.pdists[pair], a.dot, a.allow == nullptr, table, etab,
-                    reinterpret_cast<float *>(spos), h);
-  } else {
-    __syncthreads();
-  }
-  const uint32_t np = r0 + ((r1 - r0) - (r1 - r0) % RQ_BATCH);      // first row of the f32 remainder
-  for (uint32_t base = r0; base < r1; base += 256) {
-    const uint32_t row = base + threadIdx.x;
-    if (row < r1 && row_allowed(a.allow, row)) {
-      const int mode = a.allow ? RQ_FILTERED : (row < np ? RQ_PACKED : RQ_REMAINDER);
-      const float dist = rq_row_distance(a.codes + (int64_t)row * cb, cb, mode, table, etab, h, a.sqrt_d, a.add[row], a.scale[row]);
-      const uint32_t kk = order_key(dist);
-      if (kk <= ctl->thr) {        // rows tied with the k-th key come in too: the sort decides by position and records the cut tie
-        const int slot = atomicAdd(&ctl->cnt, 1);     // at most k kept + 256 new <= RQ_BUF
-        key[slot] = kk; spos[slot] = row; pos[slot] = row;
-      }
-    }
-    __syncthreads();
-    const int filled = ctl->cnt;
-    __syncthreads();               // every wave has read the same count before the next chunk adds to it
-    if (filled > 256) rq_sort_truncate(key, spos, pos, ctl, a.k);
-  }
-  if (ctl->cnt > 0) rq_sort_truncate(key, spos, pos, ctl, a.k);
-  const int got = min(ctl->cnt, a.k);
-  for (int i = threadIdx.x; i < got; i += 256) {
-    a.pkey[(int64_t)pair * a.k + i] = key[i];
-    a.ppos[(int64_t)pair * a.k + i] = pos[i];
-  }
-  if (threadIdx.x == 0) {
-    a.pcnt[pair] = (uint32_t)got;
-    a.pamb[pair] = (got == a.k && ctl->amb && ctl->amb_key == key[a.k - 1]) ? 1u : 0u;
-  }
-}
-
-// Exact replay of a flagged query (sq_exact_kernel with the RQ distance): every probed partition through a max-heap of k with std
-// BinaryHeap semantics, rows in storage order; distances by all 64 lanes, a ballot drops rows that cannot enter, lane 0 replays the
-// rest; partition heaps are merged by (dist, rowid).
-// dynamic LDS: table 16 d | etab 4 d | rotated query 4 d | trid u64 [K] | tkey [K] | hk [K + 4] | hp [K + 4] | skey [64] | RqQuery | 4 ints
-__global__ __launch_bounds__(64) void rq_exact_kernel(RqArgs a, uint64_t *__restrict__ out_ids, float *__restrict__ out_dists) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int qi = blockIdx.x;
-  if (!a.flags[qi]) return;
-  const int lane = threadIdx.x, k = a.k, d = a.d, cb = d / 8;
-  float *table = reinterpret_cast<float *>(smem);
-  uint8_t *etab = reinterpret_cast<uint8_t *>(smem + 16 * (size_t)d);
-  float *rqv = reinterpret_cast<float *>(smem + 20 * (size_t)d);
-  uint64_t *trid = reinterpret_cast<uint64_t *>(smem + 24 * (size_t)d);   // [RQ_MAX_K]
-  uint32_t *tkey = reinterpret_cast<uint32_t *>(trid + RQ_MAX_K);         // [RQ_MAX_K]
-  uint32_t *hk = tkey + RQ_MAX_K;                                         // [RQ_MAX_K + 4]
-  uint32_t *hp = hk + RQ_MAX_K + 4;                                       // [RQ_MAX_K + 4]
-  uint32_t *skey = hp + RQ_MAX_K + 4;                                     // [64]
-  RqQuery *h = reinterpret_cast<RqQuery *>(skey + 64);
-  int *ctl = reinterpret_cast<int *>(h + 1);                              // [0] heap length, [1] merged entries
-  if (lane == 0) { ctl[0] = 0; ctl[1] = 0; }
-  __syncthreads();
-  for (int pi = 0; pi < a.nprobes; ++pi) {
-    const uint32_t part = a.probes[(int64_t)qi * a.nprobes + pi];
-    const uint32_t off = a.part_offsets[part];
-    const int np = (int)(a.part_offsets[part + 1] - off);
-    if (np == 0) continue;
-    rq_prepare<64>(a.q + (int64_t)qi * d, a.cent + (int64_t)part * d, a.pt, d, a.pdists[(int64_t)qi * a.nprobes + pi], a.dot, a.allow == nullptr,
-                   table, etab, rqv, h);
-    if (lane == 0) ctl[0] = 0;
-    __syncthreads();
-    const int packed = np - np % RQ_BATCH;
-    for (int base = 0; base < np; base += 64) {
-      const int row = base + lane;
-      uint32_t key = 0xFFFFFFFFu;
-      bool cand = false;
-      if (row < np && row_allowed(a.allow, off + (uint32_t)row)) {
-        const int mode = a.allow ? RQ_FILTERED : (row < packed ? RQ_PACKED : RQ_REMAINDER);
-        const int64_t r = (int64_t)off + row;
-        key = order_key(rq_row_distance(a.codes + r * cb, cb, mode, table, etab, h, a.sqrt_d, a.add[r], a.scale[r]));
-        cand = ctl[0] < k || key < hk[0];
-      }
-      const uint64_t mask = __ballot(cand);
-      skey[lane] = key;
-      __syncthreads();
-      if (lane == 0 && mask) {
-        int hl = ctl[0];
-        uint64_t mm = mask;
-        while (mm) {
-          const int b = __ffsll((long long)mm) - 1;
-          mm &= mm - 1;
-          const uint32_t kk = skey[b];
-          if (hl < k) {
-            heap_push(hk, hp, hl, kk, off + (uint32_t)(base + b));
-          } else if (hk[0] > kk) {
-            heap_pop(hk, hp, hl);
-            heap_push(hk, hp, hl, kk, off + (uint32_t)(base + b));
-          }
-        }
-        ctl[0] = hl;
-      }
-      __syncthreads();
-    }
-    if (lane == 0) {
-      int tc = ctl[1];
-      for (int i = 0; i < ctl[0]; ++i) {
-        const uint32_t kk = hk[i];
-        const uint64_t rr = a.row_ids[hp[i]];
-        if (tc == k) {
-          const uint32_t wk = tkey[tc - 1];
-          const uint64_t wr = trid[tc - 1];
-          if (!(kk < wk || (kk == wk && rr < wr))) continue;
-        }
-        int pos = tc < k ? tc : k - 1;
-        while (pos > 0) {
-          const uint32_t pk = tkey[pos - 1];
-          const uint64_t pr = trid[pos - 1];
-          if (pk < kk || (pk == kk && pr < rr)) break;
-          tkey[pos] = pk; trid[pos] = pr;
-          --pos;
-        }
-        tkey[pos] = kk; trid[pos] = rr;
-        if (tc < k) ++tc;
-      }
-      ctl[1] = tc;
-    }
-    __syncthreads();
-  }
-  const int got = ctl[1];
-  for (int i = lane; i < k; i += 64) {
-    out_ids[(int64_t)qi * k + i] = i < got ? trid[i] : ~0ull;
-    out_dists[(int64_t)qi * k + i] = i < got ? key_to_float(tkey[i]) : INFINITY;
-  }
-}
-
 // codes [n][cb] and factors -> partition order; one thread per output byte
 __global__ __launch_bounds__(256) void rq_gather_kernel(const uint8_t *__restrict__ codes, const float *__restrict__ add, const float *__restrict__ scale,
                                                         const uint64_t *__restrict__ row_ids, const uint32_t *__restrict__ perm, int64_t n_out, int cb,
@@ -476,6 +289,86 @@ __global__ __launch_bounds__(256) void rq_gather_kernel(const uint8_t *__restric
     if (c == 0) { add_out[s] = add[r]; scale_out[s] = scale[r]; rid_out[s] = row_ids ? row_ids[r] : (uint64_t)r; }
   }
 }
+
+// ---- IVF_RQ search (pair_cand.cuh with the RQ preparation and row distance) -------------------------------------------------------
+struct RqArgs {
+  const uint8_t *codes;          // [n][cb] partition-ordered
+  const float *add, *scale;      // [n]
+  const float *pdists;           // [nq][nprobes] dist_q_c of every pair
+  const float *q;                // [nq][d]
+  const float *cent;             // [nlist][d]
+  const float *pt;               // [d][d] rotation, transposed
+  int d, dot;
+  float sqrt_d;
+  CandLists w;
+};
+
+// dynamic LDS (rq_scan_lds): table 16 d | etab 4 d | u64 entries [w.cap] | RqQuery | CandCtl.  During the preparation the first 4 d bytes of
+// the entries hold the rotated query (4 d <= 8 w.cap: rq_scan_cap).
+__global__ __launch_bounds__(256) void rq_scan_kernel(RqArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int d = a.d, cb = d / 8;
+  float *table = reinterpret_cast<float *>(smem);
+  uint8_t *etab = reinterpret_cast<uint8_t *>(smem + 16 * (size_t)d);
+  uint64_t *e = reinterpret_cast<uint64_t *>(smem + 20 * (size_t)d);
+  RqQuery *h = reinterpret_cast<RqQuery *>(e + a.w.cap);
+  CandCtl *ctl = reinterpret_cast<CandCtl *>(h + 1);
+  const int pair = blockIdx.x;
+  const int qi = pair / a.w.nprobes;
+  const uint32_t part = a.w.probes[pair];
+  const uint32_t r0 = a.w.part_offsets[part], r1 = a.w.part_offsets[part + 1];
+  if (threadIdx.x == 0) { ctl->cnt = 0; ctl->thr = 0xFFFFFFFFu; ctl->amb_key = 0; ctl->amb = 0; }
+  if (r1 > r0) {     // (uniform) an empty partition needs no tables
+    rq_prepare<256>(a.q + (int64_t)qi * d, a.cent + (int64_t)part * d, a.pt, d, a.pdists[pair], a.dot, a.w.allow == nullptr, table, etab,
+                    reinterpret_cast<float *>(e), h);
+  } else {
+    __syncthreads();
+  }
+  const uint32_t np = r0 + ((r1 - r0) - (r1 - r0) % RQ_BATCH);      // first row of the f32 remainder
+  cand_scan_pair(a.w, pair, r0, r1, e, ctl, [&](uint32_t row) {
+    const int mode = a.w.allow ? RQ_FILTERED : (row < np ? RQ_PACKED : RQ_REMAINDER);
+    return order_key(rq_row_distance(a.codes + (int64_t)row * cb, cb, mode, table, etab, h, a.sqrt_d, a.add[row], a.scale[row]));
+  });
+}
+
+struct RqDist {
+  const RqArgs &a;
+  int qi;
+  float *table;
+  uint8_t *etab;
+  float *rqv;
+  RqQuery *h;
+  __device__ __forceinline__ void partition(int pi, uint32_t part) {
+    rq_prepare<64>(a.q + (int64_t)qi * a.d, a.cent + (int64_t)part * a.d, a.pt, a.d, a.pdists[(int64_t)qi * a.w.nprobes + pi], a.dot,
+                   a.w.allow == nullptr, table, etab, rqv, h);
+  }
+  __device__ __forceinline__ uint32_t key(uint32_t off, int row, int np) const {
+    const int cb = a.d / 8;
+    const int mode = a.w.allow ? RQ_FILTERED : (row < np - np % RQ_BATCH ? RQ_PACKED : RQ_REMAINDER);
+    const int64_t r = (int64_t)off + row;
+    return order_key(rq_row_distance(a.codes + r * cb, cb, mode, table, etab, h, a.sqrt_d, a.add[r], a.scale[r]));
+  }
+};
+
+// the heap replay of a flagged query.  Dynamic LDS (rq_replay_lds): table 16 d | etab 4 d | rotated query 4 d | RqQuery (24 bytes) |
+// replay area: at d = 2048 and k = 768 that is 49152 + 24 + 15664 = 64840 of the 65536 bytes.  (Six waves per SIMD: 80 VGPRs.  Left alone
+// the allocator takes 81 -- one occupancy step for one register --; held to 80 it needs 77 and spills nothing.)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6))) void rq_exact_kernel(RqArgs a, uint64_t *__restrict__ out_ids, float *__restrict__ out_dists) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int qi = blockIdx.x;
+  if (!a.w.flags[qi]) return;
+  const size_t d = (size_t)a.d;
+  RqDist dist = {a, qi, reinterpret_cast<float *>(smem), reinterpret_cast<uint8_t *>(smem + 16 * d), reinterpret_cast<float *>(smem + 20 * d),
+                 reinterpret_cast<RqQuery *>(smem + 24 * d)};
+  cand_replay_query(a.w, qi, smem + 24 * d + sizeof(RqQuery), dist, out_ids, out_dists);
+}
+static_assert(sizeof(RqQuery) % 8 == 0, "the replay area that follows RqQuery holds 64-bit row ids");
+
+// launch sizes.  Up to CAND_NARROW_K the buffer has 512 entries (20 d + 4096 + 40 bytes of LDS) while the rotated query fits into it, i.e. up
+// to d = 1024, and 1024 beyond (49,192 bytes at d = 2048); above, the largest that fits.
+static inline int rq_scan_cap(uint32_t d, int k) { return cand_scan_cap(k, (size_t)20 * d + sizeof(RqQuery) + sizeof(CandCtl), (size_t)4 * d); }
+static inline size_t rq_scan_lds(uint32_t d, int cap) { return (size_t)20 * d + (size_t)cap * 8 + sizeof(RqQuery) + sizeof(CandCtl); }
+static inline size_t rq_replay_lds(uint32_t d, int k) { return (size_t)24 * d + sizeof(RqQuery) + cand_replay_bytes(k); }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
 static int rq_check_shape(int metric, uint32_t d, const char *what) {
@@ -498,85 +391,7 @@ static int rq_transposed(lance_hip_ctx *ctx, const float *rotation, uint32_t d, 
   return LANCE_HIP_OK;
 }
 
-static size_t rq_scan_lds(uint32_t d) { return (size_t)20 * d + (size_t)RQ_BUF * 16 + sizeof(RqQuery) + sizeof(RqCtl); }
-static size_t rq_exact_lds(uint32_t d) { return (size_t)24 * d + RQ_MAX_K * 12 + (RQ_MAX_K + 4) * 8 + 64 * 4 + sizeof(RqQuery) + 16; }
-
-// ---- wide candidates (wide_cand.cuh): device code ---------------------------------------------------------------------------------
-// keff = k * refine_factor above RQ_MAX_K: the scan / replay of IVF_RQ at the wide capacity, with the narrow kernels' preparation and
-// row distance (the same three branches)
-struct RqWideArgs {
-  const uint8_t *codes;          // [n][cb] partition-ordered
-  const float *add, *scale;      // [n]
-  const float *pdists;           // [nq][nprobes] dist_q_c of every pair
-  const float *q;                // [nq][d]
-  const float *cent;             // [nlist][d]
-  const float *pt;               // [d][d] rotation, transposed
-  int d, dot;
-  float sqrt_d;
-  WideLists w;
-};
-
-// dynamic LDS: table 16 d | etab 4 d | u64 entries [w.cap] | RqQuery | WideCtl.  During the preparation the first 4 d bytes of the
-// entries hold the rotated query (4 d <= 8 w.cap: d <= RQ_MAX_DIM = 2048, w.cap >= 1024).
-__global__ __launch_bounds__(256) void rq_wide_scan_kernel(RqWideArgs a) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int d = a.d, cb = d / 8;
-  float *table = reinterpret_cast<float *>(smem);
-  uint8_t *etab = reinterpret_cast<uint8_t *>(smem + 16 * (size_t)d);
-  uint64_t *e = reinterpret_cast<uint64_t *>(smem + 20 * (size_t)d);
-  RqQuery *h = reinterpret_cast<RqQuery *>(e + a.w.cap);
-  WideCtl *ctl = reinterpret_cast<WideCtl *>(h + 1);
-  const int pair = blockIdx.x;
-  const int qi = pair / a.w.nprobes;
-  const uint32_t part = a.w.probes[pair];
-  const uint32_t r0 = a.w.part_offsets[part], r1 = a.w.part_offsets[part + 1];
-  if (threadIdx.x == 0) { ctl->cnt = 0; ctl->thr = 0xFFFFFFFFu; ctl->amb_key = 0; ctl->amb = 0; }
-  if (r1 > r0) {     // (uniform) an empty partition needs no tables
-    rq_prepare<256>(a.q + (int64_t)qi * d, a.cent + (int64_t)part * d, a.pt, d, a.pdists[pair], a.dot, a.w.allow == nullptr, table, etab,
-                    reinterpret_cast<float *>(e), h);
-  } else {
-    __syncthreads();
-  }
-  const uint32_t np = r0 + ((r1 - r0) - (r1 - r0) % RQ_BATCH);      // first row of the f32 remainder
-  wide_scan_pair(a.w, pair, r0, r1, e, ctl, [&](uint32_t row) {
-    const int mode = a.w.allow ? RQ_FILTERED : (row < np ? RQ_PACKED : RQ_REMAINDER);
-    return order_key(rq_row_distance(a.codes + (int64_t)row * cb, cb, mode, table, etab, h, a.sqrt_d, a.add[row], a.scale[row]));
-  });
-}
-
-struct RqWideDist {
-  const RqWideArgs &a;
-  int qi;
-  float *table;
-  uint8_t *etab;
-  float *rqv;
-  RqQuery *h;
-  __device__ __forceinline__ void partition(int pi, uint32_t part) {
-    rq_prepare<64>(a.q + (int64_t)qi * a.d, a.cent + (int64_t)part * a.d, a.pt, a.d, a.pdists[(int64_t)qi * a.w.nprobes + pi], a.dot,
-                   a.w.allow == nullptr, table, etab, rqv, h);
-  }
-  __device__ __forceinline__ uint32_t key(uint32_t off, int row, int np) const {
-    const int cb = a.d / 8;
-    const int mode = a.w.allow ? RQ_FILTERED : (row < np - np % RQ_BATCH ? RQ_PACKED : RQ_REMAINDER);
-    const int64_t r = (int64_t)off + row;
-    return order_key(rq_row_distance(a.codes + r * cb, cb, mode, table, etab, h, a.sqrt_d, a.add[r], a.scale[r]));
-  }
-};
-
-// dynamic LDS: table 16 d | etab 4 d | rotated query 4 d | RqQuery (24 bytes) | wide_replay_bytes(w.k): at d = 2048 and k = 768 that is
-// 49152 + 24 + 15664 = 64840 of the 65536 bytes
-__global__ __launch_bounds__(64) void rq_wide_exact_kernel(RqWideArgs a, uint64_t *__restrict__ out_ids, float *__restrict__ out_dists) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int qi = blockIdx.x;
-  if (!a.w.flags[qi]) return;
-  const size_t d = (size_t)a.d;
-  RqWideDist dist = {a, qi, reinterpret_cast<float *>(smem), reinterpret_cast<uint8_t *>(smem + 16 * d), reinterpret_cast<float *>(smem + 20 * d),
-                     reinterpret_cast<RqQuery *>(smem + 24 * d)};
-  wide_replay_query(a.w, qi, smem + 24 * d + sizeof(RqQuery), dist, out_ids, out_dists);
-}
-// ---- wide candidates: host side ---------------------------------------------------------------------------------------------------
-static_assert(sizeof(RqQuery) % 8 == 0, "the replay area that follows RqQuery holds 64-bit row ids");
-static_assert(WIDE_MAX_K == LANCE_HIP_SQRQ_MAX_CANDIDATES, "the wide kernels' capacity is the public limit");
+static_assert(CAND_MAX_K == LANCE_HIP_SQRQ_MAX_CANDIDATES, "the candidate path's capacity is the public limit");
 
 }  // namespace lh
 
@@ -681,100 +496,40 @@ extern "C" int lance_hip_ivfrq_create(lance_hip_ctx *ctx, int metric, uint32_t d
   return LANCE_HIP_OK;
 }
 
+static const CandNames RQ_NAMES = {"ivfrq", {"ivfrq_scan", "ivfrq_wide_scan"}, {"ivfrq_merge", "ivfrq_wide_merge"}, {"ivfrq_exact", "ivfrq_wide_exact"}};
+
 // refine_factor == 0: the k best by the RQ estimate.  Otherwise (lance_hip_ivfrq_search_refine, which has checked the arguments) the
-// keff = k * refine_factor best are candidates [nq][keff] in the scratch arena -- through the kernels above up to RQ_MAX_K, through the
-// wide ones (wide_cand.cuh) beyond --, re-scored against the raw vectors (launch_refine: flat_knn's arithmetic)
+// keff = k * refine_factor best are candidates [nq][keff] in the scratch arena, re-scored against the raw vectors (cand_search, pair_cand.cuh)
 static int ivfrq_search_impl(lance_hip_ctx *ctx, const lance_hip_index *idx, const float *q, uint32_t nq, uint32_t k, uint32_t nprobes,
                              const uint32_t *allow, uint64_t *ids, float *dists, uint32_t refine_factor = 0) {
   const bool refine = refine_factor != 0;
   if (!refine) LH_REQUIRE(k > 0 && k <= (uint32_t)RQ_MAX_K, "ivfrq_search: k=%u not supported (1..%d)", k, RQ_MAX_K);
-  const uint32_t kout = k;
-  if (refine) k *= refine_factor;      // keff: every list below is strided by it, the outputs by kout
-  const bool wide = k > (uint32_t)RQ_MAX_K;
+  const uint32_t keff = refine ? k * refine_factor : k;
   if (nq == 0) return LANCE_HIP_OK;
   if (nprobes > idx->rq_nlist) nprobes = idx->rq_nlist;
   LH_REQUIRE(nprobes > 0, "ivfrq_search: nprobes must be > 0");
   const uint32_t d = idx->d;
   uint32_t *probes = ctx->scratch_t<uint32_t>("ivfrq.probes", (size_t)nq * nprobes);
   float *pd = ctx->scratch_t<float>("ivfrq.pdists", (size_t)nq * nprobes);
-  uint32_t *flags = ctx->scratch_t<uint32_t>("ivfrq.flags", (size_t)nq + 1);
-  if (!probes || !pd || !flags) return LANCE_HIP_ENOMEM;
+  if (!probes || !pd) return LANCE_HIP_ENOMEM;
   LH_TRY(find_partitions_f32(ctx, idx->metric, q, nq, d, idx->centroids, idx->rq_nlist, nprobes, probes, pd, false));
-  // queries per launch: the per-pair candidate lists stay within 2^24 entries
-  const uint32_t qch = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nq, (1ull << 24) / ((uint64_t)nprobes * k)));
-  RqArgs a;
-  a.codes = idx->codes; a.add = idx->rq_add; a.scale = idx->rq_scale; a.row_ids = idx->row_ids; a.part_offsets = idx->part_offsets;
-  a.cent = idx->centroids; a.pt = idx->rq_rot_t;
-  a.d = (int)d; a.nprobes = (int)nprobes; a.k = (int)k; a.dot = idx->metric == LANCE_HIP_DOT; a.sqrt_d = std::sqrt((float)d);
-  a.allow = allow;
-  const size_t pairs = (size_t)qch * nprobes;
-  a.pkey = ctx->scratch_t<uint32_t>("ivfrq.pkey", pairs * k);
-  a.ppos = ctx->scratch_t<uint32_t>("ivfrq.ppos", pairs * k);
-  a.pcnt = ctx->scratch_t<uint32_t>("ivfrq.pcnt", pairs);
-  a.pamb = ctx->scratch_t<uint32_t>("ivfrq.pamb", pairs);
-  if (!a.pkey || !a.ppos || !a.pcnt || !a.pamb) return LANCE_HIP_ENOMEM;
-  uint64_t *cand = nullptr;
-  float *cand_d = nullptr;
-  uint32_t *cand_cnt = nullptr, *rflags = nullptr;
-  if (refine) {
-    cand = ctx->scratch_t<uint64_t>("ivfrq.cand", (size_t)nq * k);
-    cand_d = ctx->scratch_t<float>("ivfrq.cand_d", (size_t)nq * k);
-    cand_cnt = ctx->scratch_t<uint32_t>("ivfrq.cand_cnt", (size_t)nq);
-    rflags = ctx->scratch_t<uint32_t>("ivfrq.rflags", (size_t)nq);
-    if (!cand || !cand_d || !cand_cnt || !rflags) return LANCE_HIP_ENOMEM;
-    LH_CHECK_HIP(lh::memset_async(rflags, 0, (size_t)nq * 4, ctx->stream));
-  }
-  LH_CHECK_HIP(lh::memset_async(flags, 0, ((size_t)nq + 1) * 4, ctx->stream));
-  ctx->last_replay_counter = flags + nq;
-  RqWideArgs wa = {};
-  size_t wide_scan_lds = 0;
-  if (wide) {
-    wa.codes = a.codes; wa.add = a.add; wa.scale = a.scale; wa.cent = a.cent; wa.pt = a.pt; wa.d = a.d; wa.dot = a.dot; wa.sqrt_d = a.sqrt_d;
-    wa.w.row_ids = a.row_ids; wa.w.part_offsets = a.part_offsets; wa.w.allow = allow; wa.w.nprobes = a.nprobes; wa.w.k = a.k;
-    wa.w.cap = wide_scan_cap((size_t)20 * d + sizeof(RqQuery) + sizeof(WideCtl));
-    wa.w.pkey = a.pkey; wa.w.ppos = a.ppos; wa.w.pcnt = a.pcnt; wa.w.pamb = a.pamb; wa.w.n_replay = flags + nq;
-    wide_scan_lds = (size_t)20 * d + (size_t)wa.w.cap * 8 + sizeof(RqQuery) + sizeof(WideCtl);
-  }
-  for (uint32_t q0 = 0; q0 < nq; q0 += qch) {
-    const uint32_t nqc = std::min(qch, nq - q0);
-    a.probes = probes + (size_t)q0 * nprobes; a.pdists = pd + (size_t)q0 * nprobes; a.q = q + (size_t)q0 * d; a.flags = flags + q0;
-    uint64_t *oid = (refine ? cand : ids) + (size_t)q0 * k;
-    float *od = (refine ? cand_d : dists) + (size_t)q0 * k;
-    if (wide) {
-      wa.pdists = a.pdists; wa.q = a.q; wa.w.probes = a.probes; wa.w.flags = a.flags;
-      {
-        ScopedTimer t(ctx, "ivfrq_wide_scan");
-        hipLaunchKernelGGL(rq_wide_scan_kernel, dim3(nqc * nprobes), dim3(256), wide_scan_lds, ctx->stream, wa);
-      }
-      LH_TRY(wide_merge_lists(ctx, wa.w, nqc, oid, od, "ivfrq_wide_merge"));
-      {
-        ScopedTimer t(ctx, "ivfrq_wide_exact");
-        hipLaunchKernelGGL(rq_wide_exact_kernel, dim3(nqc), dim3(64), (size_t)24 * d + sizeof(RqQuery) + wide_replay_bytes((int)k), ctx->stream, wa,
-                           oid, od);
-      }
-      continue;
-    }
-    {
-      ScopedTimer t(ctx, "ivfrq_scan");
-      hipLaunchKernelGGL(rq_scan_kernel, dim3(nqc * nprobes), dim3(256), rq_scan_lds(d), ctx->stream, a);
-    }
-    PairLists pl;
-    pl.row_ids = a.row_ids; pl.nprobes = a.nprobes; pl.k = a.k; pl.pkey = a.pkey; pl.ppos = a.ppos; pl.pcnt = a.pcnt; pl.pamb = a.pamb;
-    pl.flags = a.flags; pl.n_replay = flags + nq;
-    LH_TRY(sq_merge_pairs(ctx, pl, nqc, oid, od, "ivfrq_merge"));
-    {
-      ScopedTimer t(ctx, "ivfrq_exact");
-      hipLaunchKernelGGL(rq_exact_kernel, dim3(nqc), dim3(64), rq_exact_lds(d), ctx->stream, a, oid, od);
-    }
-  }
-  LH_CHECK_HIP(hipGetLastError());
-  if (refine) {
-    LH_TRY(launch_cand_count(ctx, cand, nq, k, cand_cnt));
-    LH_TRY(launch_refine(ctx, idx, q, nq, (int)d, cand, cand_cnt, k, kout, ids, dists, rflags, nullptr));
-    return check_flags(ctx, rflags, nq);      // synchronises; a stored row id beyond the raw vectors is an error, not a rank
-  }
-  LH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-  return LANCE_HIP_OK;
+  RqArgs a = {};
+  a.codes = idx->codes; a.add = idx->rq_add; a.scale = idx->rq_scale; a.cent = idx->centroids; a.pt = idx->rq_rot_t;
+  a.d = (int)d; a.dot = idx->metric == LANCE_HIP_DOT; a.sqrt_d = std::sqrt((float)d);
+  a.w.row_ids = idx->row_ids; a.w.part_offsets = idx->part_offsets; a.w.allow = allow; a.w.nprobes = (int)nprobes; a.w.k = (int)keff;
+  a.w.cap = rq_scan_cap(d, (int)keff);
+  LH_REQUIRE((size_t)4 * d <= (size_t)8 * a.w.cap, "ivfrq_search: the rotated query of d=%u does not fit the %d-entry candidate buffer it borrows", d, a.w.cap);
+  auto chunk = [&](const CandLists &w, uint32_t q0) { a.w = w; a.pdists = pd + (size_t)q0 * nprobes; a.q = q + (size_t)q0 * d; };
+  return cand_search(
+      ctx, idx, RQ_NAMES, a.w, probes, nq, k, refine, q, ids, dists,
+      [&](const CandLists &w, uint32_t q0, uint32_t nqc) {
+        chunk(w, q0);
+        hipLaunchKernelGGL(rq_scan_kernel, dim3(nqc * nprobes), dim3(256), rq_scan_lds(d, w.cap), ctx->stream, a);
+      },
+      [&](const CandLists &w, uint32_t q0, uint32_t nqc, uint64_t *oid, float *od) {
+        chunk(w, q0);
+        hipLaunchKernelGGL(rq_exact_kernel, dim3(nqc), dim3(64), rq_replay_lds(d, w.k), ctx->stream, a, oid, od);
+      });
 }
 
 static int ivfrq_check(lance_hip_ctx *ctx, const lance_hip_index *idx, const void *q, uint32_t nq, const uint64_t *ids, const float *dists) {

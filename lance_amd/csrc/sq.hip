@@ -15,11 +15,12 @@
 // integer, the three terms stay below 2^32 up to d = 16384 (2 d 255^2 < 2^32 needs d <= 33025), and the packed 4 x u8 dot
 // product (v_dot4_u32_u8) serves both metrics: one instruction per 4 codes with sum(x^2) stored per row at build time.
 //
-// Search: one workgroup per (query, probed partition) keeps that pair's k best (key, storage position) -- key = order_key of the
-// SCALED f32 distance, the value the reference's heap compares (two integer sums above 2^24 may round to one float and tie).  A
-// pair is ambiguous when a row tied with its k-th key had to be left out; a query is flagged when an ambiguous pair's k-th key
-// is not above the k-th key of the merged candidates, and flagged queries are replayed through std BinaryHeap's push / pop in
-// storage order (the IVF_FLAT replay with the SQ distance).  The final order is (dist, rowid).
+// Search (pair_cand.cuh, shared with IVF_RQ; this file supplies the row distance): one workgroup per (query, probed partition) keeps
+// that pair's k best (key, storage position) -- key = order_key of the SCALED f32 distance, the value the reference's heap compares
+// (two integer sums above 2^24 may round to one float and tie).  A pair is ambiguous when a row tied with its k-th key had to be left
+// out; a query is flagged when an ambiguous pair's k-th key is not above the k-th key of the merged candidates, and flagged queries
+// are replayed through std BinaryHeap's push / pop in storage order (the IVF_FLAT replay with the SQ distance).  The final order is
+// (dist, rowid).  k here is keff = k * refine_factor under a refine_factor: up to 128 in a 512-entry buffer, up to 768 in a wide one.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -32,7 +33,7 @@
 #include "index.h"
 #include "kernels.h"
 #include "search_common.cuh"
-#include "wide_cand.cuh"
+#include "pair_cand.cuh"
 
 #pragma clang fp contract(off)
 
@@ -40,7 +41,6 @@ namespace lh {
 
 constexpr uint32_t SQ_MAX_DIM = LANCE_HIP_SQ_MAX_DIM;
 constexpr int SQ_MAX_K = 128;
-constexpr int SQ_BUF = 512;          // candidate buffer of the scan / merge kernels: k kept + one 256-row chunk, padded to a power of two
 
 __device__ __forceinline__ double sq_widen(float v) { return (double)v; }
 __device__ __forceinline__ double sq_widen(__half v) { return (double)__half2float(v); }    // f16 -> f32 -> f64: both exact
@@ -159,247 +159,6 @@ __global__ __launch_bounds__(256) void sq_distance_kernel(const uint8_t *__restr
   out[(int64_t)q * n + row] = sq_finish(dot, sq_sum(dot, xq, xx, qq), r2);
 }
 
-// ---- IVF_SQ search -----------------------------------------------------------------------------------------------------------
-struct SqArgs {
-  const uint8_t *codes;          // [n][ld] partition-ordered, zero-padded rows
-  const uint32_t *xx;            // [n] sum of squared codes
-  const uint64_t *row_ids;       // [n]
-  const uint32_t *part_offsets;  // [nlist+1]
-  const uint32_t *probes;        // [nq][nprobes]
-  const uint8_t *qcodes;         // [nq][ld]
-  const uint32_t *qq;            // [nq] sum of squared query codes
-  int ld, nprobes, k, dot;
-  float r2;                      // ((end - start) as f32)^2
-  const uint32_t *allow;         // prefilter: one bit per storage position, NULL = none
-  uint32_t *pkey, *ppos;         // [nq * nprobes][k] the k best of every pair, sorted by (key, position)
-  uint32_t *pcnt;                // [nq * nprobes] entries of the pair
-  uint32_t *pamb;                // [nq * nprobes] 1 = a row tied with the pair's k-th key was left out
-  uint32_t *flags;               // [nq] 1 = replay
-  uint32_t *n_replay;            // [1] number of replayed queries of the call
-};
-
-// ascending bitonic sort of P (power of two, <= SQ_BUF) packed (key << 32 | position) entries in LDS, 256 threads
-__device__ __forceinline__ void sq_sort_u64(uint64_t *e, int P) {
-  for (int k2 = 2; k2 <= P; k2 <<= 1) {
-    for (int j = k2 >> 1; j > 0; j >>= 1) {
-      for (int i = threadIdx.x; i < P / 2; i += 256) {
-        const int ix = 2 * j * (i / j) + (i % j);
-        const int px = ix + j;
-        const bool up = (ix & k2) == 0;
-        const uint64_t a = e[ix], b = e[px];
-        if ((a > b) == up) { e[ix] = b; e[px] = a; }
-      }
-      __syncthreads();
-    }
-  }
-}
-
-// dynamic LDS of the scan kernel: [ld] query codes | [SQ_BUF] u64 entries | 4 control words
-struct SqCtl { int cnt; uint32_t thr; uint32_t amb_key; int amb; };
-
-// sort the buffer, keep the k best; a tie cut at the k-th key is remembered (thresholds only fall, so only the last one can matter)
-__device__ __forceinline__ void sq_sort_truncate(uint64_t *e, SqCtl *ctl, int k) {
-  const int cnt = ctl->cnt;
-  int P = 2;
-  while (P < cnt) P <<= 1;
-  for (int i = cnt + threadIdx.x; i < P; i += 256) e[i] = ~0ull;
-  __syncthreads();
-  sq_sort_u64(e, P);
-  if (threadIdx.x == 0 && cnt > k) {
-    const uint32_t kth = (uint32_t)(e[k - 1] >> 32);
-    if ((uint32_t)(e[k] >> 32) == kth) { ctl->amb = 1; ctl->amb_key = kth; }
-    ctl->thr = kth;
-    ctl->cnt = k;
-  }
-  __syncthreads();
-}
-
-__global__ __launch_bounds__(256) void sq_scan_kernel(SqArgs a) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  uint4 *qs = reinterpret_cast<uint4 *>(smem);
-  uint64_t *e = reinterpret_cast<uint64_t *>(smem + a.ld);
-  SqCtl *ctl = reinterpret_cast<SqCtl *>(e + SQ_BUF);
-  const int pair = blockIdx.x;
-  const int qi = pair / a.nprobes;
-  const uint32_t part = a.probes[pair];
-  const uint32_t r0 = a.part_offsets[part], r1 = a.part_offsets[part + 1];
-  const int nv = a.ld / 16;
-  for (int i = threadIdx.x; i < nv; i += 256) qs[i] = reinterpret_cast<const uint4 *>(a.qcodes + (int64_t)qi * a.ld)[i];
-  if (threadIdx.x == 0) { ctl->cnt = 0; ctl->thr = 0xFFFFFFFFu; ctl->amb_key = 0; ctl->amb = 0; }
-  __syncthreads();
-  const uint32_t qq = a.qq[qi];
-  for (uint32_t base = r0; base < r1; base += 256) {
-    const uint32_t row = base + threadIdx.x;
-    if (row < r1 && row_allowed(a.allow, row)) {
-      const uint32_t xq = sq_row_xq(reinterpret_cast<const uint4 *>(a.codes + (int64_t)row * a.ld), qs, nv);
-      const uint32_t key = order_key(sq_finish(a.dot, sq_sum(a.dot, xq, a.xx[row], qq), a.r2));
-      if (key <= ctl->thr) {        // rows tied with the k-th key come in too: the sort decides by position and records the cut tie
-        const int slot = atomicAdd(&ctl->cnt, 1);     // at most k kept + 256 new <= SQ_BUF
-        e[slot] = ((uint64_t)key << 32) | row;
-      }
-    }
-    __syncthreads();
-    const int filled = ctl->cnt;
-    __syncthreads();               // every wave has read the same count before the next chunk adds to it
-    if (filled > 256) sq_sort_truncate(e, ctl, a.k);
-  }
-  if (ctl->cnt > 0) sq_sort_truncate(e, ctl, a.k);
-  const int got = min(ctl->cnt, a.k);
-  for (int i = threadIdx.x; i < got; i += 256) {
-    a.pkey[(int64_t)pair * a.k + i] = (uint32_t)(e[i] >> 32);
-    a.ppos[(int64_t)pair * a.k + i] = (uint32_t)e[i];
-  }
-  if (threadIdx.x == 0) {
-    a.pcnt[pair] = (uint32_t)got;
-    a.pamb[pair] = (got == a.k && ctl->amb && ctl->amb_key == (uint32_t)(e[a.k - 1] >> 32)) ? 1u : 0u;
-  }
-}
-
-// per query: SortExec(dist, rowid).fetch(k) over the candidates of its pairs, then the replay decision
-__global__ __launch_bounds__(256) void sq_merge_kernel(SqArgs a, uint64_t *__restrict__ out_ids, float *__restrict__ out_dists) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  uint64_t *rid = reinterpret_cast<uint64_t *>(smem);          // [SQ_BUF]
-  uint32_t *key = reinterpret_cast<uint32_t *>(rid + SQ_BUF);  // [SQ_BUF]
-  uint32_t *pos = key + SQ_BUF;                                // [SQ_BUF]
-  int *ctl = reinterpret_cast<int *>(pos + SQ_BUF);            // [0] entries kept, [1] real entries of this round, [2] replay
-  const int q = blockIdx.x, k = a.k;
-  const int total = a.nprobes * k;
-  constexpr int ROUND = SQ_BUF - SQ_MAX_K;
-  if (threadIdx.x == 0) { ctl[0] = 0; ctl[1] = 0; ctl[2] = 0; }
-  __syncthreads();
-  for (int c0 = 0; c0 < total; c0 += ROUND) {
-    const int kept = ctl[0];
-    const int span = min(ROUND, total - c0);
-    int P = 2;
-    while (P < kept + span) P <<= 1;
-    __syncthreads();
-    for (int j = threadIdx.x; j < P - kept; j += 256) {
-      const int c = c0 + j;
-      uint32_t kk = 0xFFFFFFFFu, pp = 0xFFFFFFFFu;
-      uint64_t rr = ~0ull;
-      if (j < span) {
-        const int pair = q * a.nprobes + c / k, i = c % k;
-        if ((uint32_t)i < a.pcnt[pair]) {
-          kk = a.pkey[(int64_t)pair * k + i]; pp = a.ppos[(int64_t)pair * k + i]; rr = a.row_ids[pp];
-          atomicAdd(&ctl[1], 1);
-        }
-      }
-      key[kept + j] = kk; pos[kept + j] = pp; rid[kept + j] = rr;
-    }
-    __syncthreads();
-    bitonic_sort_kr<256>(key, rid, pos, P);
-    if (threadIdx.x == 0) { ctl[0] = min(kept + ctl[1], k); ctl[1] = 0; }
-    __syncthreads();
-  }
-  const int got = ctl[0];
-  // an ambiguous pair matters when rows at its k-th key may be part of the answer: k-th key not above the merged k-th key
-  if (got == k) {
-    const uint32_t mk = key[k - 1];
-    for (int p = threadIdx.x; p < a.nprobes; p += 256) {
-      const int pair = q * a.nprobes + p;
-      if (a.pamb[pair] && a.pkey[(int64_t)pair * k + k - 1] <= mk) ctl[2] = 1;
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    a.flags[q] = (uint32_t)ctl[2];
-    if (ctl[2]) atomicAdd(a.n_replay, 1u);
-  }
-  for (int i = threadIdx.x; i < k; i += 256) {
-    out_ids[(int64_t)q * k + i] = i < got ? rid[i] : ~0ull;
-    out_dists[(int64_t)q * k + i] = i < got ? key_to_float(key[i]) : INFINITY;
-  }
-}
-
-// Exact replay of a flagged query (ivfflat_exact_kernel with the SQ distance): every probed partition through a max-heap of k with
-// std BinaryHeap semantics (push while len < k, else replace the root only if root.dist > dist), rows in storage order; distances
-// by all 64 lanes, a ballot drops rows that cannot enter, lane 0 replays the rest; partition heaps are merged by (dist, rowid).
-__global__ __launch_bounds__(64) void sq_exact_kernel(SqArgs a, uint64_t *__restrict__ out_ids, float *__restrict__ out_dists) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int qi = blockIdx.x;
-  if (!a.flags[qi]) return;
-  const int lane = threadIdx.x, k = a.k;
-  uint4 *qs = reinterpret_cast<uint4 *>(smem);
-  uint64_t *trid = reinterpret_cast<uint64_t *>(smem + a.ld);     // [SQ_MAX_K]
-  uint32_t *tkey = reinterpret_cast<uint32_t *>(trid + SQ_MAX_K); // [SQ_MAX_K]
-  uint32_t *hk = tkey + SQ_MAX_K;                                 // [SQ_MAX_K + 4]
-  uint32_t *hp = hk + SQ_MAX_K + 4;                               // [SQ_MAX_K + 4]
-  uint32_t *skey = hp + SQ_MAX_K + 4;                             // [64]
-  int *ctl = reinterpret_cast<int *>(skey + 64);                  // [0] heap length, [1] merged entries
-  const int nv = a.ld / 16;
-  for (int i = lane; i < nv; i += 64) qs[i] = reinterpret_cast<const uint4 *>(a.qcodes + (int64_t)qi * a.ld)[i];
-  if (lane == 0) { ctl[0] = 0; ctl[1] = 0; }
-  __syncthreads();
-  const uint32_t qq = a.qq[qi];
-  for (int pi = 0; pi < a.nprobes; ++pi) {
-    const uint32_t part = a.probes[(int64_t)qi * a.nprobes + pi];
-    const uint32_t off = a.part_offsets[part];
-    const int np = (int)(a.part_offsets[part + 1] - off);
-    if (np == 0) continue;
-    if (lane == 0) ctl[0] = 0;
-    __syncthreads();
-    for (int base = 0; base < np; base += 64) {
-      const int row = base + lane;
-      uint32_t key = 0xFFFFFFFFu;
-      bool cand = false;
-      if (row < np && row_allowed(a.allow, off + (uint32_t)row)) {
-        const uint32_t xq = sq_row_xq(reinterpret_cast<const uint4 *>(a.codes + (int64_t)(off + row) * a.ld), qs, nv);
-        key = order_key(sq_finish(a.dot, sq_sum(a.dot, xq, a.xx[off + row], qq), a.r2));
-        cand = ctl[0] < k || key < hk[0];
-      }
-      const uint64_t mask = __ballot(cand);
-      skey[lane] = key;
-      __syncthreads();
-      if (lane == 0 && mask) {
-        int hl = ctl[0];
-        uint64_t mm = mask;
-        while (mm) {
-          const int b = __ffsll((long long)mm) - 1;
-          mm &= mm - 1;
-          const uint32_t kk = skey[b];
-          if (hl < k) {
-            heap_push(hk, hp, hl, kk, off + (uint32_t)(base + b));
-          } else if (hk[0] > kk) {
-            heap_pop(hk, hp, hl);
-            heap_push(hk, hp, hl, kk, off + (uint32_t)(base + b));
-          }
-        }
-        ctl[0] = hl;
-      }
-      __syncthreads();
-    }
-    if (lane == 0) {
-      int tc = ctl[1];
-      for (int i = 0; i < ctl[0]; ++i) {
-        const uint32_t kk = hk[i];
-        const uint64_t rr = a.row_ids[hp[i]];
-        if (tc == k) {
-          const uint32_t wk = tkey[tc - 1];
-          const uint64_t wr = trid[tc - 1];
-          if (!(kk < wk || (kk == wk && rr < wr))) continue;
-        }
-        int pos = tc < k ? tc : k - 1;
-        while (pos > 0) {
-          const uint32_t pk = tkey[pos - 1];
-          const uint64_t pr = trid[pos - 1];
-          if (pk < kk || (pk == kk && pr < rr)) break;
-          tkey[pos] = pk; trid[pos] = pr;
-          --pos;
-        }
-        tkey[pos] = kk; trid[pos] = rr;
-        if (tc < k) ++tc;
-      }
-      ctl[1] = tc;
-    }
-    __syncthreads();
-  }
-  const int got = ctl[1];
-  for (int i = lane; i < k; i += 64) {
-    out_ids[(int64_t)qi * k + i] = i < got ? trid[i] : ~0ull;
-    out_dists[(int64_t)qi * k + i] = i < got ? key_to_float(tkey[i]) : INFINITY;
-  }
-}
-
 // codes [n][d] -> partition order with padded rows [n_out][ld]; one thread per output byte
 __global__ __launch_bounds__(256) void sq_gather_kernel(const uint8_t *__restrict__ codes, const uint64_t *__restrict__ row_ids,
                                                         const uint32_t *__restrict__ perm, int64_t n_out, int d, int ld,
@@ -412,6 +171,67 @@ __global__ __launch_bounds__(256) void sq_gather_kernel(const uint8_t *__restric
     if (c == 0) rid_out[s] = row_ids ? row_ids[r] : (uint64_t)r;
   }
 }
+
+// ---- IVF_SQ search (pair_cand.cuh with the SQ row distance) -----------------------------------------------------------------------
+struct SqArgs {
+  const uint8_t *codes;          // [n][ld] partition-ordered, zero-padded rows
+  const uint32_t *xx;            // [n] sum of squared codes
+  const uint8_t *qcodes;         // [nq][ld]
+  const uint32_t *qq;            // [nq] sum of squared query codes
+  int ld, dot;
+  float r2;                      // ((end - start) as f32)^2
+  CandLists w;
+};
+
+// dynamic LDS (sq_scan_lds): [ld] query codes | [w.cap] u64 entries | CandCtl
+__global__ __launch_bounds__(256) void sq_scan_kernel(SqArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  uint4 *qs = reinterpret_cast<uint4 *>(smem);
+  uint64_t *e = reinterpret_cast<uint64_t *>(smem + a.ld);
+  CandCtl *ctl = reinterpret_cast<CandCtl *>(e + a.w.cap);
+  const int pair = blockIdx.x;
+  const int qi = pair / a.w.nprobes;
+  const uint32_t part = a.w.probes[pair];
+  const uint32_t r0 = a.w.part_offsets[part], r1 = a.w.part_offsets[part + 1];
+  const int nv = a.ld / 16;
+  for (int i = threadIdx.x; i < nv; i += 256) qs[i] = reinterpret_cast<const uint4 *>(a.qcodes + (int64_t)qi * a.ld)[i];
+  if (threadIdx.x == 0) { ctl->cnt = 0; ctl->thr = 0xFFFFFFFFu; ctl->amb_key = 0; ctl->amb = 0; }
+  __syncthreads();
+  const uint32_t qq = a.qq[qi];
+  cand_scan_pair(a.w, pair, r0, r1, e, ctl, [&](uint32_t row) {
+    const uint32_t xq = sq_row_xq(reinterpret_cast<const uint4 *>(a.codes + (int64_t)row * a.ld), qs, nv);
+    return order_key(sq_finish(a.dot, sq_sum(a.dot, xq, a.xx[row], qq), a.r2));
+  });
+}
+
+struct SqDist {
+  const SqArgs &a;
+  const uint4 *qs;
+  uint32_t qq;
+  __device__ __forceinline__ void partition(int, uint32_t) {}
+  __device__ __forceinline__ uint32_t key(uint32_t off, int row, int) const {
+    const uint32_t xq = sq_row_xq(reinterpret_cast<const uint4 *>(a.codes + (int64_t)(off + row) * a.ld), qs, a.ld / 16);
+    return order_key(sq_finish(a.dot, sq_sum(a.dot, xq, a.xx[off + row], qq), a.r2));
+  }
+};
+
+// the heap replay of a flagged query (the IVF_FLAT replay with the SQ distance).  Dynamic LDS (sq_replay_lds): [ld] query codes | replay area
+__global__ __launch_bounds__(64) void sq_exact_kernel(SqArgs a, uint64_t *__restrict__ out_ids, float *__restrict__ out_dists) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int qi = blockIdx.x;
+  if (!a.w.flags[qi]) return;
+  uint4 *qs = reinterpret_cast<uint4 *>(smem);
+  const int nv = a.ld / 16;
+  for (int i = threadIdx.x; i < nv; i += 64) qs[i] = reinterpret_cast<const uint4 *>(a.qcodes + (int64_t)qi * a.ld)[i];
+  __syncthreads();
+  SqDist dist = {a, qs, a.qq[qi]};
+  cand_replay_query(a.w, qi, smem + a.ld, dist, out_ids, out_dists);
+}
+
+// launch sizes: capacity 512 up to CAND_NARROW_K (ld + 4096 + 16 bytes), the largest that fits above
+static inline int sq_scan_cap(uint32_t ld, int k) { return cand_scan_cap(k, (size_t)ld + sizeof(CandCtl)); }
+static inline size_t sq_scan_lds(uint32_t ld, int cap) { return (size_t)ld + (size_t)cap * 8 + sizeof(CandCtl); }
+static inline size_t sq_replay_lds(uint32_t ld, int k) { return (size_t)ld + cand_replay_bytes(k); }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
 static int sq_check_column(int dtype, uint32_t d, const char *what) {
@@ -451,86 +271,14 @@ static int sq_encode_launch(lance_hip_ctx *ctx, int dtype, const void *x, uint64
   return LANCE_HIP_OK;
 }
 
-}  // namespace lh
-
-// kernels.h: the merge step for another FlatIndex sub-index scan that filled the same per-pair lists (rq.hip)
-int lh::sq_merge_pairs(lance_hip_ctx *ctx, const PairLists &pl, uint32_t nq, uint64_t *ids, float *dists, const char *timer) {
-  SqArgs a = {};
-  a.row_ids = pl.row_ids; a.nprobes = pl.nprobes; a.k = pl.k; a.pkey = pl.pkey; a.ppos = pl.ppos; a.pcnt = pl.pcnt; a.pamb = pl.pamb;
-  a.flags = pl.flags; a.n_replay = pl.n_replay;
+// pair_cand.cuh: the merge step of IVF_SQ and IVF_RQ, at the capacity of w.k
+int cand_merge_lists(lance_hip_ctx *ctx, const CandLists &w, uint32_t nq, uint64_t *ids, float *dists, const char *timer) {
   {
     ScopedTimer t(ctx, timer);
-    hipLaunchKernelGGL(sq_merge_kernel, dim3(nq), dim3(256), (size_t)SQ_BUF * 16 + 16, ctx->stream, a, ids, dists);
-  }
-  LH_CHECK_HIP(hipGetLastError());
-  return LANCE_HIP_OK;
-}
-
-// ---- wide candidates (wide_cand.cuh): device code ---------------------------------------------------------------------------------
-// keff = k * refine_factor above SQ_MAX_K: the scan / replay of IVF_SQ at the wide capacity, with the narrow kernels' row distance
-namespace lh {
-
-struct SqWideArgs {
-  const uint8_t *codes;          // [n][ld] partition-ordered, zero-padded rows
-  const uint32_t *xx;            // [n] sum of squared codes
-  const uint8_t *qcodes;         // [nq][ld]
-  const uint32_t *qq;            // [nq] sum of squared query codes
-  int ld, dot;
-  float r2;                      // ((end - start) as f32)^2
-  WideLists w;
-};
-
-// dynamic LDS: [ld] query codes | [w.cap] u64 entries | WideCtl
-__global__ __launch_bounds__(256) void sq_wide_scan_kernel(SqWideArgs a) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  uint4 *qs = reinterpret_cast<uint4 *>(smem);
-  uint64_t *e = reinterpret_cast<uint64_t *>(smem + a.ld);
-  WideCtl *ctl = reinterpret_cast<WideCtl *>(e + a.w.cap);
-  const int pair = blockIdx.x;
-  const int qi = pair / a.w.nprobes;
-  const uint32_t part = a.w.probes[pair];
-  const uint32_t r0 = a.w.part_offsets[part], r1 = a.w.part_offsets[part + 1];
-  const int nv = a.ld / 16;
-  for (int i = threadIdx.x; i < nv; i += 256) qs[i] = reinterpret_cast<const uint4 *>(a.qcodes + (int64_t)qi * a.ld)[i];
-  if (threadIdx.x == 0) { ctl->cnt = 0; ctl->thr = 0xFFFFFFFFu; ctl->amb_key = 0; ctl->amb = 0; }
-  __syncthreads();
-  const uint32_t qq = a.qq[qi];
-  wide_scan_pair(a.w, pair, r0, r1, e, ctl, [&](uint32_t row) {
-    const uint32_t xq = sq_row_xq(reinterpret_cast<const uint4 *>(a.codes + (int64_t)row * a.ld), qs, nv);
-    return order_key(sq_finish(a.dot, sq_sum(a.dot, xq, a.xx[row], qq), a.r2));
-  });
-}
-
-struct SqWideDist {
-  const SqWideArgs &a;
-  const uint4 *qs;
-  uint32_t qq;
-  __device__ __forceinline__ void partition(int, uint32_t) {}
-  __device__ __forceinline__ uint32_t key(uint32_t off, int row, int) const {
-    const uint32_t xq = sq_row_xq(reinterpret_cast<const uint4 *>(a.codes + (int64_t)(off + row) * a.ld), qs, a.ld / 16);
-    return order_key(sq_finish(a.dot, sq_sum(a.dot, xq, a.xx[off + row], qq), a.r2));
-  }
-};
-
-// dynamic LDS: [ld] query codes | wide_replay_bytes(w.k)
-__global__ __launch_bounds__(64) void sq_wide_exact_kernel(SqWideArgs a, uint64_t *__restrict__ out_ids, float *__restrict__ out_dists) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int qi = blockIdx.x;
-  if (!a.w.flags[qi]) return;
-  uint4 *qs = reinterpret_cast<uint4 *>(smem);
-  const int nv = a.ld / 16;
-  for (int i = threadIdx.x; i < nv; i += 64) qs[i] = reinterpret_cast<const uint4 *>(a.qcodes + (int64_t)qi * a.ld)[i];
-  __syncthreads();
-  SqWideDist dist = {a, qs, a.qq[qi]};
-  wide_replay_query(a.w, qi, smem + a.ld, dist, out_ids, out_dists);
-}
-// ---- wide candidates: host side ---------------------------------------------------------------------------------------------------
-
-// kernels.h: the wide merge step (IVF_SQ and IVF_RQ)
-int wide_merge_lists(lance_hip_ctx *ctx, const WideLists &w, uint32_t nq, uint64_t *ids, float *dists, const char *timer) {
-  {
-    ScopedTimer t(ctx, timer);
-    hipLaunchKernelGGL((wide_merge_kernel<WIDE_MERGE_BUF>), dim3(nq), dim3(256), (size_t)WIDE_MERGE_BUF * 16 + 16, ctx->stream, w, ids, dists);
+    if (w.k <= CAND_NARROW_K)
+      hipLaunchKernelGGL((cand_merge_kernel<CAND_MERGE_NARROW, CAND_NARROW_K>), dim3(nq), dim3(256), cand_merge_bytes(CAND_MERGE_NARROW), ctx->stream, w, ids, dists);
+    else
+      hipLaunchKernelGGL((cand_merge_kernel<CAND_MERGE_WIDE, CAND_MAX_K>), dim3(nq), dim3(256), cand_merge_bytes(CAND_MERGE_WIDE), ctx->stream, w, ids, dists);
   }
   LH_CHECK_HIP(hipGetLastError());
   return LANCE_HIP_OK;
@@ -677,16 +425,16 @@ extern "C" int lance_hip_ivfsq_create(lance_hip_ctx *ctx, int dtype, int metric,
   return LANCE_HIP_OK;
 }
 
+static const CandNames SQ_NAMES = {"ivfsq", {"ivfsq_scan", "ivfsq_wide_scan"}, {"ivfsq_merge", "ivfsq_wide_merge"}, {"ivfsq_exact", "ivfsq_wide_exact"}};
+
 // refine_factor == 0: the k best by the SQ distance.  Otherwise (lance_hip_ivfsq_search_refine, which has checked the arguments) the
-// keff = k * refine_factor best are candidates [nq][keff] in the scratch arena -- through the kernels above up to SQ_MAX_K, through the
-// wide ones (wide_cand.cuh) beyond --, re-scored against the raw vectors with the ORIGINAL query (launch_refine: flat_knn's arithmetic)
+// keff = k * refine_factor best are candidates [nq][keff] in the scratch arena, re-scored against the raw vectors with the ORIGINAL query
+// (cand_search, pair_cand.cuh)
 static int ivfsq_search_impl(lance_hip_ctx *ctx, const lance_hip_index *idx, const void *q, uint32_t nq, uint32_t k, uint32_t nprobes,
                              const uint32_t *allow, uint64_t *ids, float *dists, uint32_t refine_factor = 0) {
   const bool refine = refine_factor != 0;
   if (!refine) LH_REQUIRE(k > 0 && k <= (uint32_t)SQ_MAX_K, "ivfsq_search: k=%u not supported (1..%d)", k, SQ_MAX_K);
-  const uint32_t kout = k;
-  if (refine) k *= refine_factor;      // keff: every list below is strided by it, the outputs by kout
-  const bool wide = k > (uint32_t)SQ_MAX_K;
+  const uint32_t keff = refine ? k * refine_factor : k;
   if (nq == 0) return LANCE_HIP_OK;
   if (nprobes > idx->sq_nlist) nprobes = idx->sq_nlist;
   LH_REQUIRE(nprobes > 0, "ivfsq_search: nprobes must be > 0");
@@ -697,8 +445,7 @@ static int ivfsq_search_impl(lance_hip_ctx *ctx, const lance_hip_index *idx, con
   const float *q_orig = qf;            // what the refine scores with: a cosine index's key is normalised below, the original is not
   uint32_t *probes = ctx->scratch_t<uint32_t>("ivfsq.probes", (size_t)nq * nprobes);
   float *pd = ctx->scratch_t<float>("ivfsq.pdists", (size_t)nq * nprobes);
-  uint32_t *flags = ctx->scratch_t<uint32_t>("ivfsq.flags", (size_t)nq + 1);
-  if (!probes || !pd || !flags) return LANCE_HIP_ENOMEM;
+  if (!probes || !pd) return LANCE_HIP_ENOMEM;
   const bool cosine = idx->metric == LANCE_HIP_COSINE;
   if (cosine) {
     // knn.rs:498 normalises the key of a cosine query; the coarse quantiser of a cosine index works in L2 on normalised vectors
@@ -715,84 +462,21 @@ static int ivfsq_search_impl(lance_hip_ctx *ctx, const lance_hip_index *idx, con
     ScopedTimer t(ctx, "ivfsq_encode_q");      // the key holds f32 values by now (f16 widened exactly, or the normalised key)
     LH_TRY(sq_encode_queries(ctx, LANCE_HIP_F32, qf, nq, idx->d, idx->sq_lo, idx->sq_hi, ld, &qc, &qq));
   }
-  // queries per launch: the per-pair candidate lists stay within 2^24 entries
-  const uint32_t qch = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nq, (1ull << 24) / ((uint64_t)nprobes * k)));
-  SqArgs a;
-  a.codes = idx->codes; a.xx = idx->sq_xx; a.row_ids = idx->row_ids; a.part_offsets = idx->part_offsets;
-  a.ld = (int)ld; a.nprobes = (int)nprobes; a.k = (int)k; a.dot = idx->metric == LANCE_HIP_DOT;
-  a.r2 = sq_r2(idx->sq_lo, idx->sq_hi);
-  a.allow = allow;
-  const size_t pairs = (size_t)qch * nprobes;
-  a.pkey = ctx->scratch_t<uint32_t>("ivfsq.pkey", pairs * k);
-  a.ppos = ctx->scratch_t<uint32_t>("ivfsq.ppos", pairs * k);
-  a.pcnt = ctx->scratch_t<uint32_t>("ivfsq.pcnt", pairs);
-  a.pamb = ctx->scratch_t<uint32_t>("ivfsq.pamb", pairs);
-  if (!a.pkey || !a.ppos || !a.pcnt || !a.pamb) return LANCE_HIP_ENOMEM;
-  const size_t scan_lds = (size_t)ld + SQ_BUF * 8 + sizeof(SqCtl);
-  const size_t merge_lds = (size_t)SQ_BUF * 16 + 16;
-  const size_t exact_lds = (size_t)ld + SQ_MAX_K * 12 + (SQ_MAX_K + 4) * 8 + 64 * 4 + 16;
-  uint64_t *cand = nullptr;
-  float *cand_d = nullptr;
-  uint32_t *cand_cnt = nullptr, *rflags = nullptr;
-  if (refine) {
-    cand = ctx->scratch_t<uint64_t>("ivfsq.cand", (size_t)nq * k);
-    cand_d = ctx->scratch_t<float>("ivfsq.cand_d", (size_t)nq * k);
-    cand_cnt = ctx->scratch_t<uint32_t>("ivfsq.cand_cnt", (size_t)nq);
-    rflags = ctx->scratch_t<uint32_t>("ivfsq.rflags", (size_t)nq);
-    if (!cand || !cand_d || !cand_cnt || !rflags) return LANCE_HIP_ENOMEM;
-    LH_CHECK_HIP(lh::memset_async(rflags, 0, (size_t)nq * 4, ctx->stream));
-  }
-  LH_CHECK_HIP(lh::memset_async(flags, 0, ((size_t)nq + 1) * 4, ctx->stream));
-  a.n_replay = flags + nq;
-  ctx->last_replay_counter = a.n_replay;
-  SqWideArgs wa = {};
-  size_t wide_scan_lds = 0;
-  if (wide) {
-    wa.codes = a.codes; wa.xx = a.xx; wa.ld = a.ld; wa.dot = a.dot; wa.r2 = a.r2;
-    wa.w.row_ids = a.row_ids; wa.w.part_offsets = a.part_offsets; wa.w.allow = allow; wa.w.nprobes = a.nprobes; wa.w.k = a.k;
-    wa.w.cap = wide_scan_cap((size_t)ld + sizeof(WideCtl));
-    wa.w.pkey = a.pkey; wa.w.ppos = a.ppos; wa.w.pcnt = a.pcnt; wa.w.pamb = a.pamb; wa.w.n_replay = a.n_replay;
-    wide_scan_lds = (size_t)ld + (size_t)wa.w.cap * 8 + sizeof(WideCtl);
-  }
-  for (uint32_t q0 = 0; q0 < nq; q0 += qch) {
-    const uint32_t nqc = std::min(qch, nq - q0);
-    a.probes = probes + (size_t)q0 * nprobes; a.qcodes = qc + (size_t)q0 * ld; a.qq = qq + q0; a.flags = flags + q0;
-    uint64_t *oid = (refine ? cand : ids) + (size_t)q0 * k;
-    float *od = (refine ? cand_d : dists) + (size_t)q0 * k;
-    if (wide) {
-      wa.qcodes = a.qcodes; wa.qq = a.qq; wa.w.probes = a.probes; wa.w.flags = a.flags;
-      {
-        ScopedTimer t(ctx, "ivfsq_wide_scan");
-        hipLaunchKernelGGL(sq_wide_scan_kernel, dim3(nqc * nprobes), dim3(256), wide_scan_lds, ctx->stream, wa);
-      }
-      LH_TRY(wide_merge_lists(ctx, wa.w, nqc, oid, od, "ivfsq_wide_merge"));
-      {
-        ScopedTimer t(ctx, "ivfsq_wide_exact");
-        hipLaunchKernelGGL(sq_wide_exact_kernel, dim3(nqc), dim3(64), (size_t)ld + wide_replay_bytes((int)k), ctx->stream, wa, oid, od);
-      }
-      continue;
-    }
-    {
-      ScopedTimer t(ctx, "ivfsq_scan");
-      hipLaunchKernelGGL(sq_scan_kernel, dim3(nqc * nprobes), dim3(256), scan_lds, ctx->stream, a);
-    }
-    {
-      ScopedTimer t(ctx, "ivfsq_merge");
-      hipLaunchKernelGGL(sq_merge_kernel, dim3(nqc), dim3(256), merge_lds, ctx->stream, a, oid, od);
-    }
-    {
-      ScopedTimer t(ctx, "ivfsq_exact");
-      hipLaunchKernelGGL(sq_exact_kernel, dim3(nqc), dim3(64), exact_lds, ctx->stream, a, oid, od);
-    }
-  }
-  LH_CHECK_HIP(hipGetLastError());
-  if (refine) {
-    LH_TRY(launch_cand_count(ctx, cand, nq, k, cand_cnt));
-    LH_TRY(launch_refine(ctx, idx, q_orig, nq, d, cand, cand_cnt, k, kout, ids, dists, rflags, nullptr));
-    return check_flags(ctx, rflags, nq);      // synchronises; a stored row id beyond the raw vectors is an error, not a rank
-  }
-  LH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-  return LANCE_HIP_OK;
+  SqArgs a = {};
+  a.codes = idx->codes; a.xx = idx->sq_xx; a.ld = (int)ld; a.dot = idx->metric == LANCE_HIP_DOT; a.r2 = sq_r2(idx->sq_lo, idx->sq_hi);
+  a.w.row_ids = idx->row_ids; a.w.part_offsets = idx->part_offsets; a.w.allow = allow; a.w.nprobes = (int)nprobes; a.w.k = (int)keff;
+  a.w.cap = sq_scan_cap(ld, (int)keff);
+  auto chunk = [&](const CandLists &w, uint32_t q0) { a.w = w; a.qcodes = qc + (size_t)q0 * ld; a.qq = qq + q0; };
+  return cand_search(
+      ctx, idx, SQ_NAMES, a.w, probes, nq, k, refine, q_orig, ids, dists,
+      [&](const CandLists &w, uint32_t q0, uint32_t nqc) {
+        chunk(w, q0);
+        hipLaunchKernelGGL(sq_scan_kernel, dim3(nqc * nprobes), dim3(256), sq_scan_lds(ld, w.cap), ctx->stream, a);
+      },
+      [&](const CandLists &w, uint32_t q0, uint32_t nqc, uint64_t *oid, float *od) {
+        chunk(w, q0);
+        hipLaunchKernelGGL(sq_exact_kernel, dim3(nqc), dim3(64), sq_replay_lds(ld, w.k), ctx->stream, a, oid, od);
+      });
 }
 
 static int ivfsq_check(lance_hip_ctx *ctx, const lance_hip_index *idx, const void *q, uint32_t nq, const uint64_t *ids, const float *dists) {

@@ -1,7 +1,7 @@
-// Runs the wide candidate kernels (lance_amd/csrc/wide_cand.cuh and their IVF_SQ / IVF_RQ instances in sq.hip / rq.hip) on the CPU
-// (simt_emu.h) under AddressSanitizer + UBSan: every global buffer has exactly the size the library gives it, and the dynamic LDS of every
-// launch is counted as the library counts it -- the count must stay within 64 KiB and the bytes behind it must stay untouched.
-// wide_device_code.inc is cut out of the sources by tests/test_wide_cand_kernels_cpu.py, which also builds the index storage with
+// Runs the candidate kernels (lance_amd/csrc/pair_cand.cuh and their IVF_SQ / IVF_RQ instances in sq.hip / rq.hip) on the CPU (simt_emu.h)
+// under AddressSanitizer + UBSan at a capacity the caller names: every global buffer has exactly the size the library gives it, and the
+// dynamic LDS of every launch is what the library's own sizing functions say (simt_launch_lds: within 64 KiB, the bytes behind it untouched).
+// pair_device_code.inc is cut out of the sources by tests/test_wide_cand_kernels_cpu.py, which also builds the index storage with
 // tests/sq_spec.py / tests/rq_spec.py, writes the problem file and compares the outputs with the specification.
 #include "simt_emu.h"
 
@@ -18,7 +18,7 @@ static inline uint32_t atomicMax(uint32_t *p, uint32_t v) {
 }
 
 namespace lh {
-#include "wide_device_code.inc"
+#include "pair_device_code.inc"
 }
 using namespace lh;
 
@@ -38,17 +38,7 @@ static uint8_t *aligned_copy(const std::vector<uint8_t> &src) {      // 16-byte 
   return p;
 }
 
-// a launch with `lds` bytes of dynamic LDS: within 64 KiB, and nothing behind them is written
-constexpr size_t GUARD = 4096;
-static void launch_lds(size_t lds, unsigned grid, unsigned block, const std::function<void()> &kernel) {
-  if (lds > 65536) { printf("dynamic LDS of %zu bytes\n", lds); exit(3); }
-  memset(smem + lds, 0xA5, GUARD);
-  simt_launch(grid, 1, block, kernel);
-  for (size_t i = 0; i < GUARD; ++i)
-    if ((unsigned char)smem[lds + i] != 0xA5) { printf("LDS byte %zu behind the %zu of the launch was written\n", i, lds); exit(3); }
-}
-
-// in: u32 kind (0 = IVF_SQ, 1 = IVF_RQ), n_kept, d, nlist, nq, nprobes, keff, cap, dot, has_allow | u32 offs[nlist + 1] |
+// in: u32 kind (0 = IVF_SQ, 1 = IVF_RQ), n_kept, d, nlist, nq, nprobes, keff, cap (0 = the library's), dot, has_allow | u32 offs[nlist + 1] |
 // u64 rid[n_kept] (stored order) | u32 probes[nq][nprobes] | u32 allow_bits[n_kept / 32 + 4] (if has_allow) | then
 //   IVF_SQ: f32 r2 | u8 codes[n_kept][ld] | u32 xx[n_kept] | u8 qcodes[nq][ld] | u32 qq[nq]
 //   IVF_RQ: u8 codes[n_kept][d / 8] | f32 add[n_kept], scale[n_kept] | f32 pdists[nq][nprobes] | f32 q[nq][d] | f32 cent[nlist][d] | f32 pt[d][d]
@@ -59,7 +49,10 @@ int main(int argc, char **argv) {
   FILE *f = fopen(argv[1], "rb");
   if (!f) return 2;
   const auto h = rd<uint32_t>(f, 10);
-  const uint32_t kind = h[0], n = h[1], d = h[2], nlist = h[3], nq = h[4], nprobes = h[5], keff = h[6], cap = h[7], dot = h[8], has_allow = h[9];
+  const uint32_t kind = h[0], n = h[1], d = h[2], nlist = h[3], nq = h[4], nprobes = h[5], keff = h[6], dot = h[8], has_allow = h[9];
+  // cap = 0: the capacity the library picks for this search (printed: the caller knows which it expects)
+  const uint32_t cap = h[7] ? h[7] : (uint32_t)(kind == 0 ? sq_scan_cap((d + 15u) & ~15u, (int)keff) : rq_scan_cap(d, (int)keff));
+  printf("cap %u\n", cap);
   const auto offs = rd<uint32_t>(f, nlist + 1);
   const auto rid = rd<uint64_t>(f, n);
   const auto probes = rd<uint32_t>(f, (size_t)nq * nprobes);
@@ -68,15 +61,17 @@ int main(int argc, char **argv) {
   std::vector<uint32_t> pkey(pairs * keff, 0xDEADBEEFu), ppos(pairs * keff, 0xDEADBEEFu), pcnt(pairs), pamb(pairs), flags(nq + 1, 0);
   std::vector<uint64_t> ids((size_t)nq * keff);
   std::vector<float> dists((size_t)nq * keff);
-  WideLists w;
+  CandLists w;
   w.row_ids = rid.data(); w.part_offsets = offs.data(); w.probes = probes.data(); w.allow = has_allow ? allow.data() : nullptr;
   w.nprobes = (int)nprobes; w.k = (int)keff; w.cap = (int)cap;
   w.pkey = pkey.data(); w.ppos = ppos.data(); w.pcnt = pcnt.data(); w.pamb = pamb.data(); w.flags = flags.data(); w.n_replay = flags.data() + nq;
-  const size_t replay_area = (size_t)keff * 12 + (size_t)(keff + 4) * 8 + 64 * 4 + 16;     // wide_replay_bytes
   std::vector<uint64_t> fast_ids;
   std::vector<float> fast_dists;
   auto merge = [&] {
-    launch_lds((size_t)WIDE_MERGE_BUF * 16 + 16, nq, 256, [&] { wide_merge_kernel<WIDE_MERGE_BUF>(w, ids.data(), dists.data()); });
+    if (keff <= (uint32_t)CAND_NARROW_K)      // cand_merge_lists (sq.hip)
+      simt_launch_lds(cand_merge_bytes(CAND_MERGE_NARROW), nq, 256, [&] { cand_merge_kernel<CAND_MERGE_NARROW, CAND_NARROW_K>(w, ids.data(), dists.data()); });
+    else
+      simt_launch_lds(cand_merge_bytes(CAND_MERGE_WIDE), nq, 256, [&] { cand_merge_kernel<CAND_MERGE_WIDE, CAND_MAX_K>(w, ids.data(), dists.data()); });
     fast_ids = ids; fast_dists = dists;
   };
   if (kind == 0) {
@@ -86,11 +81,11 @@ int main(int argc, char **argv) {
     const auto xx = rd<uint32_t>(f, n);
     uint8_t *qc = aligned_copy(rd<uint8_t>(f, (size_t)nq * ld));
     const auto qq = rd<uint32_t>(f, nq);
-    SqWideArgs a;
+    SqArgs a;
     a.codes = codes; a.xx = xx.data(); a.qcodes = qc; a.qq = qq.data(); a.ld = (int)ld; a.dot = (int)dot; a.r2 = r2; a.w = w;
-    launch_lds((size_t)ld + (size_t)cap * 8 + sizeof(WideCtl), nq * nprobes, 256, [&] { sq_wide_scan_kernel(a); });
+    simt_launch_lds(sq_scan_lds(ld, (int)cap), nq * nprobes, 256, [&] { sq_scan_kernel(a); });
     merge();
-    launch_lds((size_t)ld + replay_area, nq, 64, [&] { sq_wide_exact_kernel(a, ids.data(), dists.data()); });
+    simt_launch_lds(sq_replay_lds(ld, (int)keff), nq, 64, [&] { sq_exact_kernel(a, ids.data(), dists.data()); });
     free(codes); free(qc);
   } else {
     const uint32_t cb = d / 8;
@@ -98,12 +93,13 @@ int main(int argc, char **argv) {
     const auto add = rd<float>(f, n), scale = rd<float>(f, n);
     const auto pdists = rd<float>(f, (size_t)nq * nprobes);
     const auto q = rd<float>(f, (size_t)nq * d), cent = rd<float>(f, (size_t)nlist * d), pt = rd<float>(f, (size_t)d * d);
-    RqWideArgs a;
+    RqArgs a;
     a.codes = codes; a.add = add.data(); a.scale = scale.data(); a.pdists = pdists.data(); a.q = q.data(); a.cent = cent.data(); a.pt = pt.data();
     a.d = (int)d; a.dot = (int)dot; a.sqrt_d = std::sqrt((float)d); a.w = w;
-    launch_lds((size_t)20 * d + (size_t)cap * 8 + sizeof(RqQuery) + sizeof(WideCtl), nq * nprobes, 256, [&] { rq_wide_scan_kernel(a); });
+    if ((size_t)4 * d > (size_t)8 * cap) { printf("the rotated query of d = %u does not fit %u entries\n", d, cap); return 3; }
+    simt_launch_lds(rq_scan_lds(d, (int)cap), nq * nprobes, 256, [&] { rq_scan_kernel(a); });
     merge();
-    launch_lds((size_t)24 * d + sizeof(RqQuery) + replay_area, nq, 64, [&] { rq_wide_exact_kernel(a, ids.data(), dists.data()); });
+    simt_launch_lds(rq_replay_lds(d, (int)keff), nq, 64, [&] { rq_exact_kernel(a, ids.data(), dists.data()); });
     free(codes);
   }
   fclose(f);

@@ -1,7 +1,7 @@
-// Runs the device code of lance_amd/csrc/rq.hip (and the IVF_SQ merge kernel it shares) on the CPU (simt_emu.h) under AddressSanitizer +
-// UBSan: every buffer has exactly the size the library gives it, so a read past a row or a write past a list is an error here.
-// rq_device_code.inc is cut out of the sources by tests/test_rq_kernels_cpu.py, which also writes the problem file and compares the
-// outputs with tests/rq_spec.py.
+// Runs the device code of lance_amd/csrc/rq.hip (and of pair_cand.cuh, which its search instantiates) on the CPU (simt_emu.h) under
+// AddressSanitizer + UBSan: every buffer has exactly the size the library gives it, so a read past a row or a write past a list is an
+// error here, and the search's launches get the dynamic LDS the library's sizing functions give them (simt_launch_lds).  rq_device_code.inc is
+// cut out of the sources by tests/test_rq_kernels_cpu.py, which also writes the problem file and compares the outputs with tests/rq_spec.py.
 #include "simt_emu.h"
 
 // what rq.hip uses beyond the IVF_SQ kernels' needs
@@ -128,23 +128,22 @@ int main(int argc, char **argv) {
     }
   }
 
-  // search: scan, merge (the IVF_SQ merge kernel), replay
+  // search: scan, merge, replay
   const size_t pairs = (size_t)nq * nprobes;
   std::vector<uint32_t> pkey(pairs * k), ppos(pairs * k), pcnt(pairs), pamb(pairs), flags(nq + 1, 0);
   std::vector<uint64_t> ids((size_t)nq * k);
   std::vector<float> dists((size_t)nq * k);
   RqArgs a;
-  a.codes = stored; a.add = sadd.data(); a.scale = sscale.data(); a.row_ids = rid.data(); a.part_offsets = offs.data(); a.probes = probes.data();
-  a.pdists = pdists.data(); a.q = q.data(); a.cent = cent.data(); a.pt = pt.data(); a.d = (int)d; a.nprobes = (int)nprobes; a.k = (int)k; a.dot = (int)dot;
-  a.sqrt_d = sqrt_d; a.allow = has_allow ? allow.data() : nullptr;
-  a.pkey = pkey.data(); a.ppos = ppos.data(); a.pcnt = pcnt.data(); a.pamb = pamb.data(); a.flags = flags.data();
-  simt_launch(nq * nprobes, 1, 256, [&] { rq_scan_kernel(a); });
-  SqArgs m = {};
-  m.row_ids = rid.data(); m.nprobes = (int)nprobes; m.k = (int)k; m.pkey = pkey.data(); m.ppos = ppos.data(); m.pcnt = pcnt.data(); m.pamb = pamb.data();
-  m.flags = flags.data(); m.n_replay = flags.data() + nq;
-  simt_launch(nq, 1, 256, [&] { sq_merge_kernel(m, ids.data(), dists.data()); });
+  a.codes = stored; a.add = sadd.data(); a.scale = sscale.data(); a.pdists = pdists.data(); a.q = q.data(); a.cent = cent.data(); a.pt = pt.data();
+  a.d = (int)d; a.dot = (int)dot; a.sqrt_d = sqrt_d;
+  a.w.row_ids = rid.data(); a.w.part_offsets = offs.data(); a.w.probes = probes.data(); a.w.allow = has_allow ? allow.data() : nullptr;
+  a.w.nprobes = (int)nprobes; a.w.k = (int)k; a.w.cap = rq_scan_cap(d, (int)k);
+  a.w.pkey = pkey.data(); a.w.ppos = ppos.data(); a.w.pcnt = pcnt.data(); a.w.pamb = pamb.data(); a.w.flags = flags.data(); a.w.n_replay = flags.data() + nq;
+  if (k > (uint32_t)CAND_NARROW_K || (size_t)4 * d > (size_t)8 * a.w.cap) return 5;      // (narrow cases; the host's check of the borrowed buffer)
+  simt_launch_lds(rq_scan_lds(d, a.w.cap), nq * nprobes, 256, [&] { rq_scan_kernel(a); });
+  simt_launch_lds(cand_merge_bytes(CAND_MERGE_NARROW), nq, 256, [&] { cand_merge_kernel<CAND_MERGE_NARROW, CAND_NARROW_K>(a.w, ids.data(), dists.data()); });
   const std::vector<uint64_t> fast_ids = ids;
-  simt_launch(nq, 1, 64, [&] { rq_exact_kernel(a, ids.data(), dists.data()); });
+  simt_launch_lds(rq_replay_lds(d, (int)k), nq, 64, [&] { rq_exact_kernel(a, ids.data(), dists.data()); });
 
   FILE *o = fopen(argv[2], "wb");
   if (!o) return 2;

@@ -79,3 +79,13 @@ static inline void simt_launch(unsigned grid_x, unsigned grid_y, unsigned block,
       pthread_barrier_destroy(&simt_barrier);
     }
 }
+
+// a launch with `lds` bytes of dynamic LDS, counted as the library counts them: within 64 KiB, and nothing behind them is written
+constexpr size_t SIMT_LDS_GUARD = 4096;
+static inline void simt_launch_lds(size_t lds, unsigned grid, unsigned block, const std::function<void()> &kernel) {
+  if (lds > 65536) { printf("dynamic LDS of %zu bytes\n", lds); exit(3); }
+  memset(smem + lds, 0xA5, SIMT_LDS_GUARD);
+  simt_launch(grid, 1, block, kernel);
+  for (size_t i = 0; i < SIMT_LDS_GUARD; ++i)
+    if ((unsigned char)smem[lds + i] != 0xA5) { printf("LDS byte %zu behind the %zu of the launch was written\n", i, lds); exit(3); }
+}

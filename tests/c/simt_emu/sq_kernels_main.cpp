@@ -1,6 +1,7 @@
-// Runs the device code of lance_amd/csrc/sq.hip on the CPU (simt_emu.h) under AddressSanitizer + UBSan: every buffer has exactly the
-// size the library gives it, so a read past a row or a write past a list is an error here.  sq_device_code.inc is cut out of the
-// sources by tests/test_sq_kernels_cpu.py, which also writes the problem file and compares the outputs with tests/sq_spec.py.
+// Runs the device code of lance_amd/csrc/sq.hip (and of pair_cand.cuh, which its search instantiates) on the CPU (simt_emu.h) under
+// AddressSanitizer + UBSan: every buffer has exactly the size the library gives it, so a read past a row or a write past a list is an
+// error here, and the search's launches get the dynamic LDS the library's sizing functions give them (simt_launch_lds).  sq_device_code.inc is
+// cut out of the sources by tests/test_sq_kernels_cpu.py, which also writes the problem file and compares the outputs with tests/sq_spec.py.
 #include "simt_emu.h"
 
 namespace lh {
@@ -106,13 +107,15 @@ int main(int argc, char **argv) {
   std::vector<uint64_t> ids((size_t)nq * k);
   std::vector<float> dists((size_t)nq * k);
   SqArgs a;
-  a.codes = stored; a.xx = xx.data(); a.row_ids = rid.data(); a.part_offsets = offs.data(); a.probes = probes.data(); a.qcodes = qc; a.qq = qq.data();
-  a.ld = (int)ld; a.nprobes = (int)nprobes; a.k = (int)k; a.dot = (int)dot; a.r2 = r2; a.allow = has_allow ? allow.data() : nullptr;
-  a.pkey = pkey.data(); a.ppos = ppos.data(); a.pcnt = pcnt.data(); a.pamb = pamb.data(); a.flags = flags.data(); a.n_replay = flags.data() + nq;
-  simt_launch(nq * nprobes, 1, 256, [&] { sq_scan_kernel(a); });
-  simt_launch(nq, 1, 256, [&] { sq_merge_kernel(a, ids.data(), dists.data()); });
+  a.codes = stored; a.xx = xx.data(); a.qcodes = qc; a.qq = qq.data(); a.ld = (int)ld; a.dot = (int)dot; a.r2 = r2;
+  a.w.row_ids = rid.data(); a.w.part_offsets = offs.data(); a.w.probes = probes.data(); a.w.allow = has_allow ? allow.data() : nullptr;
+  a.w.nprobes = (int)nprobes; a.w.k = (int)k; a.w.cap = sq_scan_cap(ld, (int)k);
+  a.w.pkey = pkey.data(); a.w.ppos = ppos.data(); a.w.pcnt = pcnt.data(); a.w.pamb = pamb.data(); a.w.flags = flags.data(); a.w.n_replay = flags.data() + nq;
+  if (k > (uint32_t)CAND_NARROW_K) return 5;      // (the cases here are narrow ones; tests/test_wide_cand_kernels_cpu.py runs both merge instances)
+  simt_launch_lds(sq_scan_lds(ld, a.w.cap), nq * nprobes, 256, [&] { sq_scan_kernel(a); });
+  simt_launch_lds(cand_merge_bytes(CAND_MERGE_NARROW), nq, 256, [&] { cand_merge_kernel<CAND_MERGE_NARROW, CAND_NARROW_K>(a.w, ids.data(), dists.data()); });
   const std::vector<uint64_t> fast_ids = ids;
-  simt_launch(nq, 1, 64, [&] { sq_exact_kernel(a, ids.data(), dists.data()); });
+  simt_launch_lds(sq_replay_lds(ld, (int)k), nq, 64, [&] { sq_exact_kernel(a, ids.data(), dists.data()); });
 
   FILE *o = fopen(argv[2], "wb");
   if (!o) return 2;

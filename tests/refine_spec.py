@@ -74,7 +74,8 @@ def ordered_partition(oracle, kind, order, metric, k, cap, N, d=64, prefiltered=
         tie_cut      k + 8 copies of the row at rank k // 2 inside the first `cap` rows, the k // 2 nearer rows after them: the first cut
                      cuts the tie block, and the block still holds the k-th key at the end (the heap decides which copies stay)
     IVF_RQ without a prefilter scores the last N % 32 rows by another branch: they are the farthest rows by that branch, fixed first.
-    -> dict: x [N + small][d] (input order = storage order), cent, q, keys u32 [N] (storage order), cut_tie, N; rq: P; sq: bounds"""
+    -> dict: x [N + small][d] (input order = storage order), cent, q, keys u32 [N] (storage order), cut_tie, N; rq: P, built (rq_spec.build
+    of x: at d = 1024 the numpy rotation takes seconds); sq: bounds"""
     assert kind in ("rq", "sq") and order in ORDERS and 2 <= k <= cap - CHUNK and cap % CHUNK == 0
     assert N > cap + 2 * CHUNK, "the scan passes two chunks after its first cut"
     for draw in range(16):
@@ -182,7 +183,7 @@ def _ordered_partition(oracle, kind, order, metric, k, cap, N, d, prefiltered, s
             raise _Redraw("the heap happens to keep the first copies by position")
     out = {"x": x, "cent": cent, "q": q, "keys": keys, "cut_tie": bool(R.kth_is_tied(keys, k)), "N": N}
     if kind == "rq":
-        out["P"] = P
+        out["P"], out["built"] = P, (part, codes, add, scale)
     else:
         out["bounds"] = SQ_BOUNDS
     return out

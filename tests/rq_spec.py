@@ -67,10 +67,11 @@ def seq_sum(a, start=0.0):
 
 
 def rotate(P, r, block=256):
-    """[n][D] = dot(P[j], r_i), in row blocks (the broadcast product is n D d floats: at most 2^26 of them at a time)"""
+    """[n][D] = dot(P[j], r_i), in row blocks (the broadcast product is n D d floats: at most 2^20 of them at a time, which stay in cache --
+    at d = 1024 that is a row per step and nearly three times as fast as 64)"""
     r = np.asarray(r, f32).reshape(-1, P.shape[1])
     out = np.empty((r.shape[0], P.shape[0]), f32)
-    block = max(1, min(block, (1 << 26) // (P.shape[0] * P.shape[1])))
+    block = max(1, min(block, (1 << 20) // (P.shape[0] * P.shape[1])))
     for i in range(0, r.shape[0], block):
         out[i:i + block] = dot16(P[None, :, :], r[i:i + block, None, :])
     return out

@@ -1,7 +1,8 @@
 """The DEVICE code of lance_amd/csrc/rq.hip run on the CPU, lane by lane (tests/c/simt_emu: a thread per lane, a barrier for
 __syncthreads), under AddressSanitizer + UBSan, against tests/rq_spec.py bit for bit: the encoder, the query preparation, the three
 distance branches (packed rows through the u8 table, the f32 remainder, the f32 fold under a prefilter) and the search -- per-pair
-selection, the merge kernel shared with IVF_SQ, the replay decision and the heap replay.  The kernels' text is cut out of the sources at
+selection, the merge kernel, the replay decision and the heap replay (pair_cand.cuh at the capacity of k <= 128, the dynamic LDS of
+every launch sized by the library's own functions and guarded).  The kernels' text is cut out of the sources at
 test time, so what runs here is what the GPU compiles.  This checks the logic and the memory safety of the kernels without a device;
 the arithmetic of the device's own instructions is what tests/test_zz_gpu_rq.py checks."""
 import os
@@ -12,7 +13,7 @@ import numpy as np
 import pytest
 
 import rq_spec as R
-from test_sq_kernels_cpu import function_text
+from test_sq_kernels_cpu import function_text, pair_cand_code
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "lance_amd", "csrc")
@@ -20,25 +21,12 @@ EMU = os.path.join(ROOT, "tests", "c", "simt_emu")
 f32 = np.float32
 
 
-def block_text(src, head):
-    """the brace-matched definition that starts with the line `head` (a struct or a __global__ kernel)"""
-    start = src.index(head)
-    depth, i = 0, src.index("{", start)
-    while True:
-        depth += {"{": 1, "}": -1}.get(src[i], 0)
-        i += 1
-        if depth == 0:
-            return src[start:i] + (";\n" if head.startswith("struct") else "\n")
-
-
 def device_code():
     read = lambda name: open(os.path.join(CSRC, name)).read()
-    exact, common, sq, rq = read("exact.cuh"), read("search_common.cuh"), read("sq.hip"), read("rq.hip")
+    exact, common, rq = read("exact.cuh"), read("search_common.cuh"), read("rq.hip")
     parts = [function_text(exact, n) for n in ("order_key", "key_to_float")]
     parts += [function_text(common, n) for n in ("row_allowed", "bitonic_sort_kr", "heap_sift_up", "heap_push", "heap_pop")]
-    # the merge kernel IVF_RQ shares with IVF_SQ, with the constants and the argument block it uses
-    parts += [re.search(r"^constexpr int SQ_MAX_K = \d+;\n", sq, flags=re.M).group(0), re.search(r"^constexpr int SQ_BUF = \d+;", sq, flags=re.M).group(0) + "\n"]
-    parts += [block_text(sq, "struct SqArgs {"), block_text(sq, "__global__ __launch_bounds__(256) void sq_merge_kernel(")]
+    parts.append(pair_cand_code())
     body = rq[rq.index("constexpr uint32_t RQ_MAX_DIM"):rq.index("// ---- host side")]
     body = body.replace("LANCE_HIP_RQ_MAX_DIM", "2048")
     code = "".join(parts) + body
@@ -129,7 +117,7 @@ def run_case(emulator, oracle, x, q, cent, P, metric, k, nprobes, row_ids, prefi
 def test_device_code_is_found():
     code = device_code()
     for name in ("rq_transpose_kernel", "rq_encode_kernel", "rq_prepare", "rq_row_distance", "rq_distance_kernel", "rq_scan_kernel", "rq_exact_kernel",
-                 "rq_gather_kernel", "sq_merge_kernel", "heap_pop", "bitonic_sort_kr", "order_key"):
+                 "cand_scan_pair", "cand_sort_truncate", "cand_replay_query", "rq_scan_cap", "rq_gather_kernel", "cand_merge_kernel", "heap_pop", "bitonic_sort_kr", "order_key"):
         assert name in code, name
     assert "hipLaunchKernelGGL" not in code and "LH_REQUIRE" not in code, "host code must stay out"
 

@@ -1,6 +1,7 @@
 """The DEVICE code of lance_amd/csrc/sq.hip run on the CPU, lane by lane (tests/c/simt_emu: a thread per lane, a barrier for
 __syncthreads), under AddressSanitizer + UBSan, against tests/sq_spec.py bit for bit: bounds, codes, distances through both row
-readers, and the search -- per-pair selection, merge, the replay decision and the heap replay.  The kernels' text is cut out of the
+readers, and the search -- per-pair selection, merge, the replay decision and the heap replay (pair_cand.cuh at the capacity of k <= 128, the
+dynamic LDS of every launch sized by the library's own functions and guarded).  The kernels' text is cut out of the
 sources at test time, so what runs here is what the GPU compiles, minus the packed dot instruction (its portable definition in
 sq.hip stands in).  This checks the logic and the memory safety of the kernels without a device; the arithmetic of the device's own
 instructions is what tests/test_zz_gpu_sq.py checks."""
@@ -31,15 +32,23 @@ def function_text(src, name):
             return src[m.start():i] + "\n"
 
 
+def pair_cand_code():
+    """what the IVF_SQ / IVF_RQ search kernels instantiate (pair_cand.cuh): the device code and the launch-size functions behind it"""
+    src = open(os.path.join(CSRC, "pair_cand.cuh")).read()
+    i = src.index("// ---- pair candidates: device code")
+    return src[i:src.index("// ---- pair candidates: end of the code the emulator programs compile", i)]
+
+
 def device_code():
     read = lambda name: open(os.path.join(CSRC, name)).read()
     exact, common, sq = read("exact.cuh"), read("search_common.cuh"), read("sq.hip")
     parts = [function_text(exact, n) for n in ("order_key", "key_to_float")]
     parts += [function_text(common, n) for n in ("row_allowed", "bitonic_sort_kr", "heap_sift_up", "heap_push", "heap_pop")]
+    parts.append(pair_cand_code())
     body = sq[sq.index("constexpr uint32_t SQ_MAX_DIM"):sq.index("// ---- host side")]
-    body = body.replace("LANCE_HIP_SQ_MAX_DIM", "16384").replace("extern __shared__ __attribute__((aligned(16))) char smem[];", "")
+    body = body.replace("LANCE_HIP_SQ_MAX_DIM", "16384")
     assert "__global__" in body and "smem" in body
-    return "".join(parts) + body
+    return ("".join(parts) + body).replace("extern __shared__ __attribute__((aligned(16))) char smem[];", "")
 
 
 @pytest.fixture(scope="module")
@@ -121,8 +130,8 @@ def run_case(emulator, oracle, x, q, cent, metric, k, nprobes, bounds, row_ids, 
 
 def test_device_code_is_found():
     code = device_code()
-    for name in ("sq_bounds_kernel", "sq_encode_kernel", "sq_distance_kernel", "sq_scan_kernel", "sq_merge_kernel", "sq_exact_kernel",
-                 "sq_gather_kernel", "sq_norms_kernel", "heap_pop", "bitonic_sort_kr", "order_key"):
+    for name in ("sq_bounds_kernel", "sq_encode_kernel", "sq_distance_kernel", "sq_scan_kernel", "cand_merge_kernel", "sq_exact_kernel",
+                 "cand_scan_pair", "cand_sort_truncate", "cand_replay_query", "sq_scan_lds", "sq_gather_kernel", "sq_norms_kernel", "heap_pop", "bitonic_sort_kr", "order_key"):
         assert name in code, name
     assert "hipLaunchKernelGGL" not in code and "LH_REQUIRE" not in code, "host code must stay out"
 

@@ -1,10 +1,12 @@
-"""The wide candidate kernels (lance_amd/csrc/wide_cand.cuh, and their IVF_SQ / IVF_RQ instances behind the `wide candidates` markers of
-sq.hip / rq.hip: scan, merge and heap replay for 128 < keff <= 768) run on the CPU, lane by lane (tests/c/simt_emu), as a stand-alone
-program under AddressSanitizer + UBSan, against tests/sq_spec.py / tests/rq_spec.py at k = keff bit for bit.  The kernels' text is cut
-out of the sources at test time, so what runs here is what the GPU compiles.  The candidate buffer's capacity is a launch parameter:
-the cases here run at the smallest one (1024 = 768 kept + one 256-row chunk), where the buffer is sorted most often and, at keff = 768,
-filled to its last entry."""
+"""The candidate kernels of IVF_SQ / IVF_RQ (lance_amd/csrc/pair_cand.cuh and their instances in the search blocks of sq.hip / rq.hip: scan,
+merge and heap replay for keff <= 768) run on the CPU, lane by lane (tests/c/simt_emu), as a stand-alone program under AddressSanitizer +
+UBSan, against tests/sq_spec.py / tests/rq_spec.py at k = keff bit for bit.  The kernels' text and the functions that size their launches
+are cut out of the sources at test time, so what runs here is what the GPU compiles.  The candidate buffer's capacity is a launch
+parameter.  The wide cases (128 < keff) run at the smallest wide one (1024 = 768 kept + one 256-row chunk), where the buffer is sorted
+most often and, at keff = 768, filled to its last entry; the narrow cases (keff = 128) run at the capacity the library picks for them:
+512, and 1024 once IVF_RQ's rotated query (4 d bytes, parked in the buffer before the scan) no longer fits 512 entries."""
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -13,7 +15,7 @@ import pytest
 import refine_spec as F
 import rq_spec as R
 import sq_spec as S
-from test_sq_kernels_cpu import function_text
+from test_sq_kernels_cpu import function_text, pair_cand_code
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "lance_amd", "csrc")
@@ -29,25 +31,23 @@ def between(src, a, b):
 
 def device_code():
     read = lambda name: open(os.path.join(CSRC, name)).read()
-    exact, common, wide, sq, rq = read("exact.cuh"), read("search_common.cuh"), read("wide_cand.cuh"), read("sq.hip"), read("rq.hip")
+    exact, common, sq, rq = read("exact.cuh"), read("search_common.cuh"), read("sq.hip"), read("rq.hip")
     parts = [function_text(exact, n) for n in ("order_key", "key_to_float")]
     parts += [function_text(common, n) for n in ("row_allowed", "bitonic_sort_kr", "heap_sift_up", "heap_push", "heap_pop")]
     parts += [function_text(sq, n) for n in ("sq_udot4", "sq_row_xq", "sq_finish", "sq_sum")]
     parts.append(between(rq, "constexpr int RQ_BATCH", "// out[i][j] = in[j][i]"))                          # RQ_BATCH, the branches, rq_rot_dot
     parts.append(between(rq, "struct RqQuery {", "// distance_all (quantised != 0) or distance of every row"))   # rq_prepare, rq_row_distance
-    parts.append(between(wide, "// ---- wide candidates: device code", "// ---- wide candidates: end of device code"))
-    sqw = between(sq, "// ---- wide candidates (wide_cand.cuh): device code", "// ---- wide candidates: host side")
-    assert sqw.count("namespace lh {\n") == 1
-    parts.append(sqw.replace("namespace lh {\n", ""))
-    parts.append(between(rq, "// ---- wide candidates (wide_cand.cuh): device code", "// ---- wide candidates: host side"))
+    parts.append(pair_cand_code())
+    parts.append(between(sq, "// ---- IVF_SQ search", "// ---- host side"))
+    parts.append(between(rq, "// ---- IVF_RQ search", "// ---- host side"))
     code = "".join(parts).replace("extern __shared__ __attribute__((aligned(16))) char smem[];", "")
     return code
 
 
 def test_device_code_is_found():
     code = device_code()
-    for name in ("wide_sort_truncate", "wide_scan_pair", "wide_merge_kernel", "wide_replay_query", "sq_wide_scan_kernel", "sq_wide_exact_kernel",
-                 "rq_wide_scan_kernel", "rq_wide_exact_kernel", "rq_prepare", "rq_row_distance", "sq_row_xq", "heap_pop"):
+    for name in ("cand_sort_truncate", "cand_scan_pair", "cand_merge_kernel", "cand_replay_query", "cand_scan_cap", "sq_scan_kernel", "sq_exact_kernel",
+                 "rq_scan_kernel", "rq_exact_kernel", "rq_scan_cap", "rq_replay_lds", "rq_prepare", "rq_row_distance", "sq_row_xq", "heap_pop"):
         assert name in code, name
     assert "hipLaunchKernelGGL" not in code and "LH_REQUIRE" not in code and "extern __shared__" not in code, "host code must stay out"
 
@@ -55,10 +55,10 @@ def test_device_code_is_found():
 @pytest.fixture(scope="module")
 def emulator(tmp_path_factory):
     work = tmp_path_factory.mktemp("wide_emu")
-    (work / "wide_device_code.inc").write_text(device_code())
-    exe = str(work / "wide_cand")
+    (work / "pair_device_code.inc").write_text(device_code())
+    exe = str(work / "pair_cand")
     cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-pthread",
-           "-I", str(work), "-I", EMU, os.path.join(EMU, "wide_cand_main.cpp"), "-o", exe]
+           "-I", str(work), "-I", EMU, os.path.join(EMU, "pair_cand_main.cpp"), "-o", exe]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     if r.returncode != 0 and "sanitize" in r.stderr:
         pytest.skip("g++ without sanitizer runtimes")
@@ -101,6 +101,7 @@ def run(emulator, kind, head, offs, stored_ids, probes, bits, payload, nq, keff)
            "fast_ids": take(nq * keff, np.uint64).reshape(nq, keff), "fast_dists": take(nq * keff, f32).reshape(nq, keff),
            "flags": take(nq + 1, np.uint32), "ids": take(nq * keff, np.uint64).reshape(nq, keff), "dists": take(nq * keff, f32).reshape(nq, keff)}
     assert pos == raw.size
+    out["cap"] = int(re.search(r"^cap (\d+)$", r.stdout, flags=re.M).group(1))      # the capacity the scan ran at (head cap = 0: the library's)
     return out
 
 
@@ -113,10 +114,10 @@ def check(out, oi, od, nq):
     return int(out["flags"][nq])
 
 
-def run_rq(emulator, oracle, x, q, cent, P, metric, keff, nprobes, row_ids, prefilter=None, cap=CAP):
+def run_rq(emulator, oracle, x, q, cent, P, metric, keff, nprobes, row_ids, prefilter=None, cap=CAP, built=None):
     x, q, cent, P = (np.ascontiguousarray(a, f32) for a in (x, q, cent, P))
     d, nq, nlist = x.shape[1], q.shape[0], cent.shape[0]
-    part, codes, add, scale = R.build(oracle, x, cent, P, metric)
+    part, codes, add, scale = built or R.build(oracle, x, cent, P, metric)
     offs, perm = oracle.partition_layout(part, nlist)
     probes, pd = oracle.find_partitions(q, cent, nprobes, metric)
     stored_ids = row_ids[perm]
@@ -241,3 +242,45 @@ def test_mass_ties_are_replayed(emulator, oracle):
     replays, _ = run_sq(emulator, oracle, x, q, cent, "l2", 200, 1, S.bounds(x), rid)       # one probe: a cut tie of the pair is the answer's
     assert replays > 0
     run_sq(emulator, oracle, x, q, cent, "l2", 200, 3, S.bounds(x), rid)
+
+
+
+# ---- the narrow capacity: keff = 128, the buffer the library picks (cap = 0 in the problem file) -------------------------------------
+# Every N is past the buffer plus two chunks, N % 32 = 0, 1, 31, 0 over the four orders.  IVF_RQ at d = 1024: the rotated query fills the
+# 512-entry buffer it borrows to its last byte; d = 1032 is the first dimension that takes 1024 entries.
+NARROW_K = 128
+NARROW = {512: list(zip(F.ORDERS, (1056, 1057, 1087, 1056))), 1024: list(zip(F.ORDERS, (1568, 1569, 1599, 1568)))}
+
+
+@pytest.mark.parametrize("order,N", NARROW[512])
+def test_sq_narrow_ordered_partitions(emulator, oracle, order, N):
+    f = F.ordered_partition(oracle, "sq", order, "l2", NARROW_K, 512, N)
+    q = np.ascontiguousarray(np.stack([f["q"], f["x"][5] + f32(0.1)]))
+    rid = S.permuted_ids(len(f["x"]), 4)
+    replays, out = run_sq(emulator, oracle, f["x"], q, f["cent"], "l2", NARROW_K, 2, f["bounds"], rid, cap=0)
+    assert out["cap"] == 512
+    pair_contract(out, f, NARROW_K)
+    assert out["flags"][0] == 1 or not f["cut_tie"]
+
+
+@pytest.mark.parametrize("d,cap,order,N", [(1024, 512, o, n) for o, n in NARROW[512]] + [(1032, 1024, o, n) for o, n in NARROW[1024]])
+def test_rq_narrow_ordered_partitions(emulator, oracle, d, cap, order, N):
+    f = F.ordered_partition(oracle, "rq", order, "l2", NARROW_K, cap, N, d=d)
+    q = np.ascontiguousarray(np.stack([f["q"], f["x"][5] + f32(0.1)]))
+    rid = R.permuted_ids(len(f["x"]), 4)
+    replays, out = run_rq(emulator, oracle, f["x"], q, f["cent"], f["P"], "l2", NARROW_K, 2, rid, cap=0, built=f["built"])
+    assert out["cap"] == cap
+    pair_contract(out, f, NARROW_K)
+    assert f["cut_tie"] == (order == "tie_cut") and out["flags"][0] == int(f["cut_tie"])
+
+
+def test_rq_narrow_tie_cut_masked(emulator, oracle):
+    """an all-selected mask (every row through the f32 fold): every one of the first 512 rows is a candidate, so the first cut finds the
+    512-entry buffer filled to its last entry (ordered_partition asserts that the cut at storage position 511 cuts the tie block)"""
+    f = F.ordered_partition(oracle, "rq", "tie_cut", "l2", NARROW_K, 512, 1087, prefiltered=True)
+    rid = R.permuted_ids(len(f["x"]), 4)
+    replays, out = run_rq(emulator, oracle, f["x"], np.ascontiguousarray(f["q"][None]), f["cent"], f["P"], "l2", NARROW_K, 2, rid,
+                          prefilter=np.ones(int(rid.max()) + 1, bool), cap=0)
+    assert out["cap"] == 512
+    pair_contract(out, f, NARROW_K)
+    assert f["cut_tie"] and out["flags"][0] == 1 and replays == 1

@@ -1,8 +1,8 @@
 """Re-ranking for IVF_SQ and IVF_RQ on the GPU (lance_hip_ivfsq_search_refine / lance_hip_ivfrq_search_refine) against
-tests/refine_spec.py, ids exactly and distances as bits: keff = k * refine_factor candidates through the narrow kernels (keff <= 128)
-or the wide ones (wide_cand.cuh, 128 < keff <= 768), then the exact refine against the raw vectors with the original query.  The
-specification is checked on the CPU by tests/test_refine_spec.py and the wide kernels' source is run on the CPU by
-tests/test_wide_cand_kernels_cpu.py.  Sorted last: newest device code last."""
+tests/refine_spec.py, ids exactly and distances as bits: keff = k * refine_factor candidates through the scan / merge / replay of
+pair_cand.cuh at its narrow capacity (keff <= 128) or its wide one (128 < keff <= 768), then the exact refine against the raw vectors
+with the original query.  The specification is checked on the CPU by tests/test_refine_spec.py and the kernels' source is run on the
+CPU by tests/test_wide_cand_kernels_cpu.py.  Sorted last: newest device code last."""
 import ctypes as C
 import functools
 
@@ -28,7 +28,7 @@ def same_bits(a, b):
 
 
 def wide_cap(fixed):
-    """wide_scan_cap (wide_cand.cuh): the largest power of two whose 8-byte entries fit beside `fixed` bytes in 64 KiB"""
+    """cand_scan_cap above 128 candidates (pair_cand.cuh): the largest power of two whose 8-byte entries fit beside `fixed` bytes in 64 KiB"""
     cap = 1024
     while fixed + cap * 16 <= 65536:
         cap *= 2
@@ -129,7 +129,7 @@ MASKS = {"half": lambda rid: np.random.default_rng(23).random(int(rid.max()) + 1
 @pytest.mark.parametrize("k,rf", [(10, 2), (128, 1), (129, 1), (10, 50), (768, 1), (96, 8)])
 @pytest.mark.parametrize("config", CONFIGS, ids="/".join)
 def test_both_routes(config, k, rf):
-    """keff = 20 and 128 run the narrow scan / merge / replay kernels, 129, 500 and 768 the wide ones (asserted by the kernel timers)"""
+    """keff = 20 and 128 run scan / merge / replay at the narrow capacity, 129, 500 and 768 at the wide one (asserted by the kernel timers)"""
     key = "/".join(config)
     ix, spec, q = SETUPS[key]()
     e = eng()

@@ -2,6 +2,8 @@
 distance bits, no tolerances:
   * partitions of ~800 rows stored in an order chosen for one query (rq_spec.ordered_partition, self-checked by tests/test_rq_spec.py):
     the scan passes its first truncation and then admits rows by its threshold alone; ties cut at one truncation and met again later;
+  * k = 128 at d = 1024 and 1032, on either side of the dimension where the scan's candidate buffer doubles (the rotated query it borrows
+    the buffer for fills 512 entries to the last byte at d = 1024), in partitions ordered for that buffer (refine_spec.ordered_partition);
   * search at d = 8, 24, 128 (16-byte row loads), 136 (full 16-blocks and a tail in the rotation) and 2048 (the largest: the rotated
     query fills the whole candidate buffer it borrows, ~48 KiB of LDS in the scan and ~52 KiB in the replay), one query a centroid;
   * the encoder at d >= 256 (one row per iteration) and at d that do not divide 256, and its grid-stride loop;
@@ -79,6 +81,38 @@ def test_threshold_and_ties(order, k, metric, mask):
         # that key out of the merged answer
         if cut and (nprobes == 1 or R.order_key(od[0, k - 1]) >= np.sort(keys)[k - 1]):
             assert replays > 0, (order, k, metric, mask, nprobes)
+
+
+# ---- k = 128 where the candidate buffer changes size ---------------------------------------------------------------------------------
+# (d, entries of the scan's buffer at k = 128, rows of the ordered partition: past the buffer and two more chunks, N % 32 = 1)
+K128_DIMS = [(1024, 512, 1409), (1032, 1024, 1569)]
+
+
+@functools.lru_cache(maxsize=None)
+def ordered_k128(d, cap, N, order, prefiltered):
+    import oracle
+    import refine_spec as F
+    f = F.ordered_partition(oracle, "rq", order, "l2", 128, cap, N, d=d, prefiltered=prefiltered)
+    ix, spec = device_index(f["x"], f["cent"], f["P"], "l2", row_ids(len(f["x"]), prefiltered, 3), f["built"])
+    return ix, spec, f
+
+
+@pytest.mark.parametrize("mask", ["none", "all"])
+@pytest.mark.parametrize("order", ["descending", "tie_cut"])
+@pytest.mark.parametrize("d,cap,N", K128_DIMS)
+def test_k128_buffer_sizes(d, cap, N, order, mask):
+    """descending: after the first cut every row enters, the buffer is cut again at every chunk; tie_cut: the first cut cuts a block of
+    136 copies that still holds the 128th key at the end, so the design query is replayed"""
+    ix, spec, f = ordered_k128(d, cap, N, order, mask == "all")
+    rid = spec[6]
+    allow = np.ones(int(rid.max()) + 1, bool) if mask == "all" else None
+    assert f["cut_tie"] == (order == "tie_cut")
+    q = np.ascontiguousarray(np.stack([f["q"], f["x"][5] + f32(0.1)]))
+    for nprobes in (1, 2):
+        replays, _, od = check_search(ix, spec, q, 128, nprobes, "l2", prefilter=allow)
+        # replayed unless the other partition pushed the tied key out of the merged answer
+        if f["cut_tie"] and (nprobes == 1 or R.order_key(od[0, 127]) >= np.sort(f["keys"])[127]):
+            assert replays > 0, (d, order, mask, nprobes)
 
 
 # ---- dimensions in search -------------------------------------------------------------------------------------------------------------
