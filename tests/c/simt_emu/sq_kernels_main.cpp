@@ -98,7 +98,8 @@ int main(int argc, char **argv) {
   std::vector<uint64_t> rid(n_kept);
   std::vector<uint32_t> xx(n_kept);
   if (n_kept) {
-    simt_launch(((size_t)n_kept * ld + 255) / 256, 1, 256, [&] { sq_gather_kernel(codes.data(), row_ids.data(), perm.data(), (int64_t)n_kept, (int)d, (int)ld, stored, rid.data()); });
+    // (the kernel walks its bytes with a grid-stride loop; 48 workgroups here, a thread each per lane, take the later ones in further turns)
+    simt_launch(std::min<size_t>(((size_t)n_kept * ld + 255) / 256, 48), 1, 256, [&] { sq_gather_kernel(codes.data(), row_ids.data(), perm.data(), (int64_t)n_kept, (int)d, (int)ld, stored, rid.data()); });
     simt_launch((n_kept + 255) / 256, 1, 256, [&] { sq_norms_kernel(stored, (int64_t)n_kept, (int)ld, xx.data()); });
   }
   // search: scan, merge, replay
@@ -111,9 +112,13 @@ int main(int argc, char **argv) {
   a.w.row_ids = rid.data(); a.w.part_offsets = offs.data(); a.w.probes = probes.data(); a.w.allow = has_allow ? allow.data() : nullptr;
   a.w.nprobes = (int)nprobes; a.w.k = (int)k; a.w.cap = sq_scan_cap(ld, (int)k);
   a.w.pkey = pkey.data(); a.w.ppos = ppos.data(); a.w.pcnt = pcnt.data(); a.w.pamb = pamb.data(); a.w.flags = flags.data(); a.w.n_replay = flags.data() + nq;
-  if (k > (uint32_t)CAND_NARROW_K) return 5;      // (the cases here are narrow ones; tests/test_wide_cand_kernels_cpu.py runs both merge instances)
+  if (k > (uint32_t)CAND_MAX_K) return 5;
+  printf("scan capacity %d\n", a.w.cap);
   simt_launch_lds(sq_scan_lds(ld, a.w.cap), nq * nprobes, 256, [&] { sq_scan_kernel(a); });
-  simt_launch_lds(cand_merge_bytes(CAND_MERGE_NARROW), nq, 256, [&] { cand_merge_kernel<CAND_MERGE_NARROW, CAND_NARROW_K>(a.w, ids.data(), dists.data()); });
+  if (k <= (uint32_t)CAND_NARROW_K)      // the merge instance cand_merge_lists picks
+    simt_launch_lds(cand_merge_bytes(CAND_MERGE_NARROW), nq, 256, [&] { cand_merge_kernel<CAND_MERGE_NARROW, CAND_NARROW_K>(a.w, ids.data(), dists.data()); });
+  else
+    simt_launch_lds(cand_merge_bytes(CAND_MERGE_WIDE), nq, 256, [&] { cand_merge_kernel<CAND_MERGE_WIDE, CAND_MAX_K>(a.w, ids.data(), dists.data()); });
   const std::vector<uint64_t> fast_ids = ids;
   simt_launch_lds(sq_replay_lds(ld, (int)k), nq, 64, [&] { sq_exact_kernel(a, ids.data(), dists.data()); });
 

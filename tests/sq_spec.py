@@ -1,5 +1,6 @@
-"""Shared by tests/test_sq_spec.py (CPU) and tests/test_zz_gpu_sq.py (GPU): the CPU specification of 8-bit scalar quantisation and
-of the IVF_SQ search, in numpy, composed with the oracle's existing functions for the IVF side, and the fixtures of both files.
+"""Shared by tests/test_sq_spec.py, tests/test_sq_kernels_cpu.py (CPU) and tests/test_zz_gpu_sq.py, tests/test_zz_gpu_sq_scan.py (GPU):
+the CPU specification of 8-bit scalar quantisation and of the IVF_SQ search, in numpy, composed with the oracle's existing functions
+for the IVF side, the fixtures of these files, and wrong selections (mutants) the fixtures must tell from the specification.
 
 The specification (lance-index sq.rs:43-89, 263-287; sq/storage.rs:398-468; lance-linalg l2.rs:44-49, dot.rs:152-161;
 flat/index.rs:82-177), every floating-point operation one rounding in the stated format:
@@ -13,6 +14,8 @@ flat/index.rs:82-177), every floating-point operation one rounding in the stated
                if root.dist > dist), unselected rows skipped under a prefilter
     query      normalised for cosine, encoded with the index bounds; partitions by oracle.find_partitions (L2 for cosine);
                the partition results merged by oracle.sort_fetch (dist, rowid)"""
+import functools
+
 import numpy as np
 
 f32, f64 = np.float32, np.float64
@@ -76,8 +79,9 @@ def prepare_rows(oracle, x, centroids, metric):
     return xs, part
 
 
-def search(oracle, codes, part_ids, centroids, q, k, nprobes, metric, start, end, row_ids=None, prefilter=None):
-    """codes [n][d] in input order; part_ids [n] (NONE = dropped); q raw queries in the column's element type"""
+def search(oracle, codes, part_ids, centroids, q, k, nprobes, metric, start, end, row_ids=None, prefilter=None, select=None):
+    """codes [n][d] in input order; part_ids [n] (NONE = dropped); q raw queries in the column's element type.  select: a MUTANT of
+    the per-partition selection (int_sum_select, unscaled_select below) in place of the heap -- what a wrong kernel would answer"""
     codes = np.asarray(codes, np.uint8)
     n, d = codes.shape
     nlist = centroids.shape[0]
@@ -101,13 +105,34 @@ def search(oracle, codes, part_ids, centroids, q, k, nprobes, metric, start, end
                 rows = rows[ok]
             if len(rows) == 0:
                 continue
-            dist = scale(int_sums(codes[rows], qc[qi], metric), metric, start, end)
-            hi, hd = oracle.heap_topk(dist, rid[rows], k)
+            sums = int_sums(codes[rows], qc[qi], metric)
+            dist = scale(sums, metric, start, end)
+            hi, hd = oracle.heap_topk(dist, rid[rows], k) if select is None else select(oracle, sums, dist, rid[rows], k, metric)
             ci.append(hi); cd.append(hd)
         if ci:
             si, sd = oracle.sort_fetch(np.concatenate(ci), np.concatenate(cd), k)
             out_i[qi, :len(si)] = si; out_d[qi, :len(sd)] = sd
     return out_i, out_d
+
+
+# ---- wrong selections: what a kernel answers whose key is not the scaled f32 distance --------------------------------------------
+def int_sum_select(oracle, sums, dist, rid, k, metric):
+    """MUTANT: the k best of a partition by (u32 sum -- dot: descending --, storage position).  Two sums above 2^24 that are one float
+    are a tie to the reference (the heap decides) and an order here"""
+    key = sums.astype(np.int64) * (-1 if metric == "dot" else 1)
+    keep = np.lexsort((np.arange(len(sums)), key))[:k]
+    return rid[keep], dist[keep]
+
+
+def unscaled_select(oracle, sums, dist, rid, k, metric):
+    """MUTANT: the heap keyed by f32(sum) (dot: 1 - f32(sum)), before the multiply by r^2 and the divide by 65025: two floats that
+    the scaling rounds into one are a tie to the reference and an order here"""
+    d0 = sums.astype(f32)
+    if metric == "dot":
+        d0 = f32(1.0) - d0
+    pos, _ = oracle.heap_topk(d0, np.arange(len(sums), dtype=np.uint64), k)
+    pos = pos.astype(np.int64)
+    return rid[pos], dist[pos]
 
 
 def sorted_search(oracle, codes, part_ids, centroids, q, k, nprobes, metric, start, end, row_ids=None):
@@ -170,6 +195,77 @@ def large_sum_fixture(d=1024):
     x = np.full((4, d), 255.0, f32)
     x[:, -1] = [0.0, 1.0, 2.0, 3.0]
     return x, np.zeros((1, d), f32), (0.0, 255.0)
+
+
+LARGE_SUM_BOUNDS = (0.0, 441.5)       # r^2 / 65025 = 2.9977: the scaling is no power of two, it merges floats of its own
+LARGE_SUM_TAIL = 12                   # varying columns; one more column in front of them tells the two partitions apart
+LARGE_SUM_OTHER = 24                  # rows of the second partition
+LARGE_SUM_DIMS = ((259, 900), (516, 900), (1024, 900), (1536, 900), (4096, 900), (16384, 300))      # (d, rows of partition 0) the GPU file runs
+LARGE_SUM_KS = (1, 10, 128)
+LARGE_SUM_WIDE = ((1536, (129, 768)), (16384, (129,)))      # keff whose list the design query's partition cuts with a tie: 300 rows at d = 16384
+
+
+@functools.lru_cache(maxsize=None)
+def large_sum_cached(d, metric, n):
+    """one fixture per (d, metric) for every test of a process; nobody writes to it"""
+    return large_sum_partition(d, metric, n)
+
+
+def large_sum_partition(d, metric, n, seed=0):
+    """Partition 0 of a two-partition index whose integer sums against the design query lie above 2^24 (from d = 516 on) and differ by
+    single units, so that f32 holds several of them in one value -- and the scaling by r^2 / 65025 merges further ones -- while the
+    sums themselves are distinct.  Column layout: d - 13 main columns | 1 selector | 12 tail columns.
+        rows       main code 255 (saturated: the value lies above the bound); tail codes from 0 .. 5; every tail pattern is stored
+                   three times, far apart, so a key is tied wherever a partition's list is cut
+        query 0    L2: codes 0 everywhere -- the sum is (d - 13) 255^2 + sum(tail^2).  dot: code 255 on the main columns and 0 / 1 / 2
+                   on the tail -- (d - 13) 255^2 + sum(tail * q), in steps of one
+        query 1    the same with other tail codes (L2: 0 .. 2); query 2: the codes of a row of partition 1
+        partition 1  LARGE_SUM_OTHER rows of the same kind (codes 255 | 1 | tail): their keys fall among partition 0's, so nprobes = 2 merges two
+                   lists that interleave.  The selector column (-200 / code 0 in partition 0 and the queries, code 1 in partition 1)
+                   and the centroids (equal but for -1000 / +1000 there) assign every row and the design queries under L2 and under dot.
+    Values are real numbers inside their code's cell, (code + u) (end - start) / 255 with u in [0.2, 0.8), not the cell's edge.
+    -> dict x f32 [n + LARGE_SUM_OTHER][d] (input order = storage order, partition 0 first), codes (intended), q f32 [3][d], qcodes,
+       cent f32 [2][d], bounds, rid (permuted row ids), n"""
+    start, end = LARGE_SUM_BOUNDS
+    tail, m = LARGE_SUM_TAIL, n + LARGE_SUM_OTHER
+    main = d - tail - 1
+    assert main >= 1 and n % 3 == 0
+    rng = np.random.default_rng([seed, d, n, int(metric == "dot")])
+    codes = np.full((m, d), 255, np.uint8)
+    third = rng.integers(0, 6, (n // 3, tail))
+    codes[:n, main + 1:] = np.concatenate([third, third[rng.permutation(n // 3)], third[rng.permutation(n // 3)]])
+    codes[n:, main + 1:] = rng.integers(0, 6, (LARGE_SUM_OTHER, tail))
+    codes[:n, main] = 0
+    codes[n:, main] = 1
+    qcodes = np.zeros((3, d), np.uint8)
+    if metric == "dot":
+        qcodes[:, :main] = 255
+        qcodes[:2, main + 1:] = rng.integers(0, 3, (2, tail))
+    else:
+        qcodes[1, main + 1:] = rng.integers(0, 3, tail)
+    qcodes[2] = codes[n + 1]
+    qcodes[2, main] = 0
+    value = lambda c: ((c.astype(f64) + rng.uniform(0.2, 0.8, c.shape)) * (end - start) / 255.0 + start).astype(f32)
+    x, q = value(codes), value(qcodes)
+    x[:n, main] = -200.0
+    q[:, main] = -200.0
+    cent = np.full((2, d), f32(end + 0.5 * (end - start) / 255.0), f32)
+    cent[:, main + 1:] = f32(2.5 * (end - start) / 255.0)
+    cent[0, main], cent[1, main] = -1000.0, 1000.0
+    return {"x": np.ascontiguousarray(x), "codes": codes, "q": np.ascontiguousarray(q), "qcodes": qcodes, "cent": cent,
+            "bounds": LARGE_SUM_BOUNDS, "rid": permuted_ids(m, seed + 17), "n": n}
+
+
+def order_key(a):
+    """f32::total_cmp as an unsigned key: what the kernels' lists and heaps compare"""
+    b = np.ascontiguousarray(a, f32).view(np.uint32)
+    return np.where(b >> 31 != 0, ~b, b | np.uint32(0x80000000)).astype(np.uint32)
+
+
+def large_sum_keys(f, metric, qi=0):
+    """(u32 sums, order keys of the scaled distances) of partition 0's rows, in storage order, for query qi of the fixture"""
+    sums = int_sums(f["codes"][:f["n"]], f["qcodes"][qi], metric)
+    return sums, order_key(scale(sums, metric, *f["bounds"]))
 
 
 def saturation_fixture(n=257, d=16, seed=5):

@@ -1,7 +1,9 @@
 """The DEVICE code of lance_amd/csrc/sq.hip run on the CPU, lane by lane (tests/c/simt_emu: a thread per lane, a barrier for
 __syncthreads), under AddressSanitizer + UBSan, against tests/sq_spec.py bit for bit: bounds, codes, distances through both row
-readers, and the search -- per-pair selection, merge, the replay decision and the heap replay (pair_cand.cuh at the capacity of k <= 128, the
-dynamic LDS of every launch sized by the library's own functions and guarded).  The kernels' text is cut out of the
+readers, and the search -- per-pair selection, merge, the replay decision and the heap replay (pair_cand.cuh at the capacity of k <= 128 and,
+in one large-sum case, at the wide one; the dynamic LDS of every launch sized by the library's own functions and guarded).  Integer sums
+past 2^24 (sq_spec.large_sum_partition at d = 516) are answered like the specification, and a second build of the same text whose key is
+taken before the scaling FAILS that case: the fixture tells the keys apart in the kernels' own code.  The kernels' text is cut out of the
 sources at test time, so what runs here is what the GPU compiles, minus the packed dot instruction (its portable definition in
 sq.hip stands in).  This checks the logic and the memory safety of the kernels without a device; the arithmetic of the device's own
 instructions is what tests/test_zz_gpu_sq.py checks."""
@@ -39,7 +41,9 @@ def pair_cand_code():
     return src[i:src.index("// ---- pair candidates: end of the code the emulator programs compile", i)]
 
 
-def device_code():
+def device_code(mutant=False):
+    """mutant: the scan's and the replay's key taken from (float)sum, before the multiply by r^2 and the divide by 65025 -- the wrong
+    kernel tests/sq_spec.py's unscaled_select describes (L2; the distances it reports are not compared)"""
     read = lambda name: open(os.path.join(CSRC, name)).read()
     exact, common, sq = read("exact.cuh"), read("search_common.cuh"), read("sq.hip")
     parts = [function_text(exact, n) for n in ("order_key", "key_to_float")]
@@ -48,13 +52,14 @@ def device_code():
     body = sq[sq.index("constexpr uint32_t SQ_MAX_DIM"):sq.index("// ---- host side")]
     body = body.replace("LANCE_HIP_SQ_MAX_DIM", "16384")
     assert "__global__" in body and "smem" in body
+    if mutant:
+        body, count = re.subn(r"order_key\(sq_finish\(a\.dot, (sq_sum\([^;]*\)), a\.r2\)\)", r"order_key((float)(\1))", body)
+        assert count == 2, "the key of sq_scan_kernel and of SqDist::key"
     return ("".join(parts) + body).replace("extern __shared__ __attribute__((aligned(16))) char smem[];", "")
 
 
-@pytest.fixture(scope="module")
-def emulator(tmp_path_factory):
-    work = tmp_path_factory.mktemp("sq_emu")
-    (work / "sq_device_code.inc").write_text(device_code())
+def build_emulator(work, mutant=False):
+    (work / "sq_device_code.inc").write_text(device_code(mutant))
     exe = str(work / "sq_kernels")
     cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-pthread",
            "-I", str(work), "-I", EMU, os.path.join(EMU, "sq_kernels_main.cpp"), "-o", exe]
@@ -65,7 +70,17 @@ def emulator(tmp_path_factory):
     return exe, work
 
 
-def run_case(emulator, oracle, x, q, cent, metric, k, nprobes, bounds, row_ids, prefilter=None, shift=0, want_wide=None):
+@pytest.fixture(scope="module")
+def emulator(tmp_path_factory):
+    return build_emulator(tmp_path_factory.mktemp("sq_emu"))
+
+
+@pytest.fixture(scope="module")
+def mutant_emulator(tmp_path_factory):
+    return build_emulator(tmp_path_factory.mktemp("sq_emu_mutant"), mutant=True)
+
+
+def run_case(emulator, oracle, x, q, cent, metric, k, nprobes, bounds, row_ids, prefilter=None, shift=0, want_wide=None, want_cap=None, ids_only=False):
     exe, work = emulator
     xs, part = S.prepare_rows(oracle, x, cent, metric)
     qs = oracle.normalize(q) if metric == "cosine" else q
@@ -95,6 +110,8 @@ def run_case(emulator, oracle, x, q, cent, metric, k, nprobes, bounds, row_ids, 
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout[-1000:] + r.stderr[-4000:]
     if want_wide is not None:
         assert f"sq_distance wide {int(want_wide)}" in r.stdout, r.stdout
+    if want_cap is not None:
+        assert f"scan capacity {want_cap}\n" in r.stdout, r.stdout
     raw = np.fromfile(outp, np.uint8)
     if shift:
         return raw
@@ -112,6 +129,8 @@ def run_case(emulator, oracle, x, q, cent, metric, k, nprobes, bounds, row_ids, 
     flags = take(nq + 1, np.uint32)
     fast_ids = take(nq * k, np.uint64).reshape(nq, k)
     assert pos == raw.size
+    if ids_only:
+        return ids
     # bounds, codes, distances
     assert tuple(fold) == S.bounds(xs32)
     want_codes = S.encode(xs32, *bounds)
@@ -144,15 +163,17 @@ def test_ties_are_replayed(emulator, oracle):
     assert run_case(emulator, oracle, x, q, cent, "l2", 128, 4, b, rid, prefilter=np.arange(int(rid.max()) + 1) % 3 != 0) > 0
 
 
-@pytest.mark.parametrize("metric,kind,d,k,nprobes", [("l2", "f32", 20, 10, 3), ("dot", "f16", 32, 128, 8), ("cosine", "f32", 16, 1, 1)])
+@pytest.mark.parametrize("metric,kind,d,k,nprobes", [("l2", "f32", 20, 10, 3), ("dot", "f16", 32, 128, 8), ("cosine", "f32", 16, 1, 1),
+                                                     ("l2", "f32", 1, 10, 3), ("cosine", "f16", 17, 10, 3)])
 def test_gaussian_rows(emulator, oracle, metric, kind, d, k, nprobes):
     x, q = S.gaussian(700, d, 3, seed=5, kind=kind)
-    x[650, 2] = np.nan                                    # a row without a partition
+    x[650, min(2, d - 1)] = np.nan                        # a row without a partition
     rid = S.permuted_ids(700, 2)
     cent = S.centroids_with_gaps(oracle.normalize(x[:600]) if metric == "cosine" else x[:600], 8, seed=1)
     xs, _ = S.prepare_rows(oracle, x, cent, metric)
     b = S.bounds(np.asarray(xs, f32)[100:164])            # a sample's bounds: later rows saturate
-    assert run_case(emulator, oracle, x, q, cent, metric, k, nprobes, b, rid) < 3
+    replays = run_case(emulator, oracle, x, q, cent, metric, k, nprobes, b, rid)
+    assert replays < 3 or d == 1                          # (one column: 700 rows on 256 codes tie everywhere)
     half = np.zeros(int(rid.max()) + 1, bool)
     half[rid[::2]] = True
     run_case(emulator, oracle, x, q, cent, metric, k, 8, b, rid, prefilter=half)
@@ -204,3 +225,43 @@ def test_constant_column(emulator, oracle):
     rid = S.permuted_ids(300, 4)
     assert run_case(emulator, oracle, x, x[:2], cent, "l2", 10, 3, (0.0, 2.0), rid) == 2
     assert run_case(emulator, oracle, x, x[:2], cent, "l2", 128, 1, (1.25, 1.25), rid) == 2      # start == end
+
+
+# ---- integer sums past 2^24 (sq_spec.large_sum_partition; its conditions are checked by tests/test_sq_spec.py at the sizes of the GPU file) ----
+def large_sum_case(oracle):
+    """d = 516 with 426 + 24 rows; the design query's partition cuts a tie at k = 10, 128 and 129"""
+    f = S.large_sum_partition(516, "l2", 426)
+    _, keys = S.large_sum_keys(f, "l2")
+    for k in (10, 128, 129):
+        s = np.sort(keys)
+        assert s[k - 1] == s[k]
+    return f, (oracle, f["x"], f["q"][:2], f["cent"], "l2")
+
+
+@pytest.mark.parametrize("k,nprobes,cap", [(10, 2, 512), (128, 1, 512), (129, 2, 4096)])
+def test_large_sums(emulator, oracle, k, nprobes, cap):
+    """sums above 2^24 that are one float: the cut ties are replayed, and the answer is the heap's.  k = 129 runs the scan at the wide
+    capacity (4096 entries beside the 528 bytes of the query) and the wide merge instance"""
+    f, args = large_sum_case(oracle)
+    assert run_case(emulator, *args, k, nprobes, f["bounds"], f["rid"], want_cap=cap) >= 1
+    if k == 128:
+        half = np.zeros(int(f["rid"].max()) + 1, bool)
+        half[f["rid"][::2]] = True
+        run_case(emulator, *args, k, 2, f["bounds"], f["rid"], prefilter=half)
+
+
+def test_large_sums_fail_a_kernel_keyed_on_the_unscaled_sum(mutant_emulator, oracle):
+    """the same device text with order_key((float)sum) for a key: its ids at d = 516 are not the reference's -- they are the ones
+    sq_spec.unscaled_select predicts -- so the fixture tells the two keys apart in the kernels' own code.  (One probe: with two the
+    mutant also merges by the wrong key.)"""
+    f, args = large_sum_case(oracle)
+    _, part = S.prepare_rows(oracle, f["x"], f["cent"], "l2")
+    spec = (oracle, f["codes"], part, f["cent"], f["q"][:2], 128, 1, "l2") + f["bounds"]
+    want, _ = S.search(*spec, row_ids=f["rid"])
+    wrong, _ = S.search(*spec, row_ids=f["rid"], select=S.unscaled_select)
+    got = run_case(mutant_emulator, *args, 128, 1, f["bounds"], f["rid"], ids_only=True)
+    differ = (np.sort(got, axis=1) != np.sort(want, axis=1)).any(axis=1)
+    assert differ.all(), "the mutant kernel must fail both design queries"
+    assert (np.sort(got, axis=1) == np.sort(wrong, axis=1)).all()
+    with pytest.raises(AssertionError):
+        run_case(mutant_emulator, *args, 128, 1, f["bounds"], f["rid"])

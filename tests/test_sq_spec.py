@@ -1,4 +1,4 @@
-"""CPU checks of tests/sq_spec.py, the specification the GPU tests of IVF_SQ (tests/test_zz_gpu_sq.py) compare with bit for bit:
+"""CPU checks of tests/sq_spec.py, the specification the GPU tests of IVF_SQ (tests/test_zz_gpu_sq.py, tests/test_zz_gpu_sq_scan.py) compare with bit for bit:
 the reference's own recorded answers (lance-index sq.rs tests: test_f16_sq8 / test_f32_sq8 / test_f64_sq8 / test_scale_to_u8_with_nan),
 the arithmetic rules of the specification, and the conditions the shared fixtures must meet to exercise what the GPU tests claim."""
 import numpy as np
@@ -144,3 +144,93 @@ def test_tie_fixture_depends_on_heap_order(oracle):
     sort_i = S.sorted_search(oracle, codes, part, cent, q, 10, 3, "l2", start, end, row_ids=rid)
     differ = (heap_i != sort_i).any(axis=1)
     assert differ.any(), "at least one query's answer must depend on the heap's handling of ties"
+
+
+# ---- large sums: the conditions tests/test_zz_gpu_sq_scan.py and tests/test_sq_kernels_cpu.py rely on, decided by the reference alone ------
+LARGE = [(d, n, metric) for d, n in S.LARGE_SUM_DIMS for metric in ("l2", "dot")]
+
+
+def kth_is_tied(keys, k):
+    s = np.sort(keys)
+    return len(s) > k and s[k - 1] == s[k]
+
+
+@pytest.mark.parametrize("d,n,metric", LARGE)
+def test_large_sum_partition_is_what_it_says(oracle, d, n, metric):
+    f = S.large_sum_cached(d, metric, n)
+    start, end = f["bounds"]
+    assert f32(end - start) * f32(end - start) != f32(65025.0), "the scaling must not be a no-op"
+    assert f["x"].dtype == f32 and (f["x"] != np.rint(f["x"])).mean() > 0.9, "real values, not the integers of the codes"
+    assert (S.encode(f["x"], start, end) == f["codes"]).all() and (S.encode(f["q"], start, end) == f["qcodes"]).all()
+    _, part = S.prepare_rows(oracle, f["x"], f["cent"], metric)
+    assert (part[:n] == 0).all() and (part[n:] == 1).all() and len(part) == n + S.LARGE_SUM_OTHER
+    probes, _ = oracle.find_partitions(f["q"], f["cent"], 2, metric)
+    assert (probes[:, 0] == 0).all() and (probes[:, 1] == 1).all()
+    rid = f["rid"]
+    assert len(np.unique(rid)) == len(rid) and (np.diff(rid[:n].astype(np.int64)) < 0).sum() > n // 4, "row ids are no storage order"
+    for qi in (0, 1):
+        sums, _ = S.large_sum_keys(f, metric, qi)
+        distinct = np.unique(sums)
+        assert (np.diff(distinct.astype(np.int64)) == 1).sum() >= 8, "sums in steps of one"
+        assert (distinct > 2 ** 24).all() == (d >= 516) and (distinct < 2 ** 24).all() == (d < 516)
+    # the second partition's keys fall among the first's: two probes merge lists that interleave
+    _, k0 = S.large_sum_keys(f, metric)
+    k1 = S.order_key(S.scale(S.int_sums(f["codes"][n:], f["qcodes"][0], metric), metric, start, end))
+    assert (k1 <= np.sort(k0)[127]).any() and (k1 >= np.sort(k0)[9]).any()
+
+
+@pytest.mark.parametrize("d,n,metric", LARGE)
+def test_large_sums_share_their_key(d, n, metric):
+    """at least a quarter of the distinct sums of the design query end in the key of another sum.  At d = 259 every sum is below 2^24
+    and is its own float: there the scaling alone merges them"""
+    f = S.large_sum_cached(d, metric, n)
+    sums, keys = S.large_sum_keys(f, metric)
+    distinct, first = np.unique(sums, return_index=True)
+    dk = keys[first]
+    shared = np.array([(dk == v).sum() > 1 for v in dk])
+    print(f"d={d} {metric}: {len(distinct)} sums, {len(np.unique(distinct.astype(f32)))} floats, {len(np.unique(dk))} keys, {shared.mean():.2f} shared")
+    assert shared.mean() >= 0.25
+    if d == 259:
+        assert len(np.unique(distinct.astype(f32))) == len(distinct) and len(np.unique(dk)) < len(distinct)
+
+
+@pytest.mark.parametrize("d,n,metric", LARGE)
+def test_large_sum_lists_are_cut_with_a_tie(d, n, metric):
+    """more rows are tied at the k-th key of the design query's partition than fit, at every k (and keff) the GPU file searches with:
+    the cut-tie flag must be set and the query replayed"""
+    f = S.large_sum_cached(d, metric, n)
+    _, keys = S.large_sum_keys(f, metric)
+    for k in S.LARGE_SUM_KS + dict(S.LARGE_SUM_WIDE).get(d, ()):
+        assert kth_is_tied(keys, k), k
+
+
+def mutant_differences(oracle, d, n, metric, k, nprobes=1):
+    f = S.large_sum_cached(d, metric, n)
+    _, part = S.prepare_rows(oracle, f["x"], f["cent"], metric)
+    args = (oracle, f["codes"], part, f["cent"], f["q"][:2], k, nprobes, metric) + f["bounds"]
+    ref, _ = S.search(*args, row_ids=f["rid"])
+    return {"int_sum": (ref != S.search(*args, row_ids=f["rid"], select=S.int_sum_select)[0]).sum(),
+            "unscaled": (ref != S.search(*args, row_ids=f["rid"], select=S.unscaled_select)[0]).sum(),
+            "sorted": (ref != S.sorted_search(*args, row_ids=f["rid"])).sum()}
+
+
+@pytest.mark.parametrize("d,n,metric", LARGE)
+def test_large_sum_mutants_answer_differently(oracle, d, n, metric):
+    """a selection keyed by the integer sum (from d = 516 on, where sums share a float), one keyed by f32(sum) before the scaling (at
+    d = 259, where only the scaling merges), and the (dist, rowid) sort without the heap (everywhere) return other ids than the
+    reference at k = 128, one probe"""
+    diff = mutant_differences(oracle, d, n, metric, 128)
+    print(f"d={d} {metric}: ids that differ at k = 128: {diff}")
+    assert diff["sorted"] > 0
+    if d >= 516:
+        assert diff["int_sum"] > 0
+    if d == 259:
+        assert diff["unscaled"] > 0 and diff["int_sum"] > 0
+
+
+def test_large_sum_mutants_differ_at_k_10(oracle):
+    """... and at k = 10 from d = 1536 on, two probes (L2)"""
+    for d, n in S.LARGE_SUM_DIMS:
+        if d >= 1536:
+            diff = mutant_differences(oracle, d, n, "l2", 10, 2)
+            assert diff["int_sum"] > 0 and diff["sorted"] > 0, (d, diff)
