@@ -211,3 +211,18 @@ def test_dryrun_refine_real_spoiled(fake, oracle, kind, metric, d):
 def test_dryrun_refine_real_sort(fake, oracle):
     import test_zz_gpu_refine_real as R
     R.sort_case(fake, counters=False)
+
+
+# ---- training on every E-step route (tests/test_zz_gpu_train_routes.py): every case body on the stand-in, without the stage counters
+# ---- (the stand-in enqueues nothing); argument order, element types and the comparisons themselves
+@pytest.mark.parametrize("group", ["width", "gate", "4bit", "m1", "types", "mixed", "split", "cap", "budget"])
+def test_dryrun_train_routes_pq(fake, oracle, group):
+    import train_routes_spec as T
+    import test_zz_gpu_train_routes as Z
+    Z.pq_body(fake, oracle, T.pq_group(group), counters=False)
+
+
+def test_dryrun_train_routes_kmeans(fake, oracle):
+    import train_routes_spec as T
+    import test_zz_gpu_train_routes as Z
+    Z.km_body(fake, oracle, list(T.KM_CASES.values()), counters=False)
