@@ -690,6 +690,25 @@ int lance_hip_shuffle_buffer_write(const char *path, const uint64_t *row_ids, co
 int lance_hip_merge_topk(lance_hip_ctx *ctx, const int64_t *ids, const float *dists, const float *exact_dists, uint32_t nq,
                          uint32_t c, uint32_t keff, uint32_t k, int64_t *out_ids, float *out_dists);
 
+/* ---- combined search: `take` + `flat_knn` over candidate lists ------------------------------------- */
+/* The stage that joins an ANN list with the flat KNN of the rows no index covers yet (Scanner::nearest, scanner.rs:2847-3030;
+ * knn_combined / flat_knn, scanner.rs:3336-3468: UnionExec of the two lists, every distance recomputed from the column, the range
+ * filter on those distances, SortExec(_distance, _rowid).fetch(k)) -- and, with list B absent, the refine (scanner.rs:2884-2904).
+ * Per query the candidates are the ca slots of ids_a [nq][ca] and the cb slots of ids_b [nq][cb] (UINT64_MAX = an empty slot; ids_b /
+ * dists_b may be NULL with cb = 0).  No de-duplication: a row id present twice is returned twice.  Every candidate of list A is
+ * scored against x[id] (x [n_rows][d], the row id is the row index) with the query as given: the distance lance_hip_flat_topk
+ * returns for that (row, query), bit for bit (f32 / f16 / int8 columns, L2 / dot / cosine; int8 cosine: LANCE_HIP_EINVAL).  List B
+ * is what lance_hip_flat_topk[_range] returned for the unindexed rows: with dists_b its distances are taken as they are (they
+ * are those bits already), with dists_b NULL its rows are scored like list A's.  Bounds as in lance_hip_flat_topk_range, on the
+ * exact distances: the total order on f32, an absent bound is not tested, lower above upper is LANCE_HIP_EINVAL, lower == upper
+ * returns nothing.  The survivors are ordered by (distance, row id) and the first k written; missing slots: id UINT64_MAX,
+ * distance +inf.  A candidate id >= n_rows is never read: the call returns LANCE_HIP_EINVAL after the stream is drained (outputs
+ * undefined).  Limits: 1 <= k <= 1024, 1 <= ca + cb <= 4096.  q in the column's element type; device pointers.              */
+int lance_hip_take_flat_knn(lance_hip_ctx *ctx, int dtype, int metric, const void *x, uint64_t n_rows, uint32_t d, const void *q,
+                            uint32_t nq, const uint64_t *ids_a, uint32_t ca, const uint64_t *ids_b, const float *dists_b,
+                            uint32_t cb, int has_lower, float lower, int has_upper, float upper, uint32_t k, uint64_t *out_ids,
+                            float *out_dists);
+
 /* ---- measurement hooks (bench.py): per-kernel HIP-event timing on the ctx stream --- */
 /* When enabled, each internal launch of the named hot kernels is bracketed by events;
  * query returns accumulated milliseconds and launch count, then resets.              */

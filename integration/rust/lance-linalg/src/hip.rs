@@ -155,6 +155,13 @@ extern "C" {
         out: *mut *mut LanceHipIndex) -> i32;
     pub fn lance_hip_flat_topk(ctx: *mut LanceHipCtx, dtype: i32, metric: i32, x: *const c_void, row_ids: *const u64,
         n: u64, d: u32, q: *const c_void, nq: u32, k: u32, ids: *mut u64, dists: *mut f32) -> i32;
+    /// `take` + flat_knn over two candidate lists per query (scanner.rs:2884-2904 refine; knn_combined, scanner.rs:3336-3468): the ANN
+    /// list `ids_a` [nq][ca] and the flat KNN of the unindexed fragments `ids_b` / `dists_b` [nq][cb] (u64::MAX = an empty slot; may be
+    /// null with cb = 0) are scored against `x` [n_rows][d] (row id = row index) with lance_hip_flat_topk's bits, tested against
+    /// lower <= d < upper on those distances and the k best by (distance, row id) written; no de-duplication.  ca + cb <= 4096.
+    pub fn lance_hip_take_flat_knn(ctx: *mut LanceHipCtx, dtype: i32, metric: i32, x: *const c_void, n_rows: u64, d: u32, q: *const c_void,
+        nq: u32, ids_a: *const u64, ca: u32, ids_b: *const u64, dists_b: *const f32, cb: u32, has_lower: i32, lower: f32, has_upper: i32,
+        upper: f32, k: u32, out_ids: *mut u64, out_dists: *mut f32) -> i32;
     /// multivec_distance (distance.rs:107-206) of one multivector query to every row of a List<FixedSizeList> column: `values` is the
     /// list's child array, `offsets` [n_rows + 1] its offsets as u64 (device).  A row without a vector is LANCE_HIP_EINVAL.
     pub fn lance_hip_multivec_distance(ctx: *mut LanceHipCtx, dtype: i32, metric: i32, values: *const c_void, offsets: *const u64,

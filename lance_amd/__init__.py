@@ -11,7 +11,7 @@ from ._lib import LanceHipError
 
 __all__ = ["_lib", "LanceHipError", "Engine", "DeviceIndex", "KMeans", "IvfPqParams", "IvfPqIndex", "IvfSqIndex", "DeviceSqIndex", "IvfRqIndex", "DeviceRqIndex", "create_index",
            "flat_knn", "multivector_distance", "multivector_flat_knn", "create_multivector_index", "IvfPqMultivectorIndex", "train_ivf_centroids", "train_pq_codebook", "train_sq_bounds", "default_engine", "load_index",
-           "validate_vector_index", "merge_indices", "target_partition_size", "should_split", "should_join", "IndicesBuilder", "IvfModel", "PqModel"]
+           "validate_vector_index", "merge_indices", "target_partition_size", "should_split", "should_join", "IndicesBuilder", "IvfModel", "PqModel", "VectorColumn"]
 
 
 def __getattr__(name):
@@ -23,7 +23,7 @@ def __getattr__(name):
                 "create_multivector_index", "IvfPqMultivectorIndex",
                 "train_ivf_centroids", "IvfSqIndex", "IvfRqIndex", "train_sq_bounds",
                 "train_pq_codebook", "default_engine", "load_index", "validate_vector_index", "merge_indices", "target_partition_size",
-                "should_split", "should_join"):
+                "should_split", "should_join", "VectorColumn"):
         from . import vector
         return getattr(vector, name)
     if name in ("IndicesBuilder", "IvfModel", "PqModel"):

@@ -53,6 +53,7 @@ SYMBOLS = [
     "lance_hip_kmeans_shard_estep_x",
     "lance_hip_index_merge", "lance_hip_index_remap", "lance_hip_index_export_rows",
     "lance_hip_reassign_rows", "lance_hip_index_split", "lance_hip_index_join",
+    "lance_hip_take_flat_knn",
 ]
 
 
@@ -187,6 +188,7 @@ def load():
         "lance_hip_timing_query": (i32, [vp, C.c_char_p, C.POINTER(f64), C.POINTER(u64)]),
         "lance_hip_ubench": (i32, [vp, i32, C.POINTER(f64)]),
         "lance_hip_merge_topk": (i32, [vp, vp, vp, vp, u32, u32, u32, u32, vp, vp]),
+        "lance_hip_take_flat_knn": (i32, [vp, i32, i32, vp, u64, u32, vp, u32, vp, u32, vp, vp, u32, i32, f32, i32, f32, u32, vp, vp]),
         "lance_hip_shuffle_buffer_write": (i32, [C.c_char_p, vp, vp, vp, u64, u32, C.POINTER(u64)]),
         "lance_hip_comm_unique_id": (i32, [C.c_char_p]),
         "lance_hip_comm_create": (i32, [vp, C.c_char_p, i32, i32, C.POINTER(vp)]),

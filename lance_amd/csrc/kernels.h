@@ -279,7 +279,7 @@ int qscan_items(lance_hip_ctx *ctx, const uint32_t *pair_starts, int nvp, int G,
 int launch_cand_count(lance_hip_ctx *ctx, const uint64_t *ids, uint32_t nq, uint32_t keff, uint32_t *cnt);
 int launch_refine(lance_hip_ctx *ctx, const lance_hip_index *ix, const float *q, uint32_t nq, int d, const uint64_t *cand_rid, const uint32_t *cand_cnt,
                   uint32_t keff, uint32_t k, uint64_t *ids, float *dists, uint32_t *flags, float *cand_exact);
-int check_flags(lance_hip_ctx *ctx, const uint32_t *flags, uint32_t nq);
+int check_flags(lance_hip_ctx *ctx, const uint32_t *flags, uint32_t nq, const char *badrow_msg = nullptr);   // badrow_msg: what to report for FLAG_BADROW instead of the set_raw message
 const uint8_t *raw_compact_prepare(lance_hip_ctx *ctx, const lance_hip_index *ix);   // search.hip: lossless u8 refine copy (index.h), or nullptr
 
 }  // namespace lh

@@ -1936,12 +1936,16 @@ int find_partitions_f32(lance_hip_ctx *ctx, int metric, const float *qf, uint32_
   return LANCE_HIP_OK;
 }
 
-int check_flags(lance_hip_ctx *ctx, const uint32_t *flags, uint32_t nq) {
+int check_flags(lance_hip_ctx *ctx, const uint32_t *flags, uint32_t nq, const char *badrow_msg) {
   std::vector<uint32_t> fh(nq);
   LH_CHECK_HIP(hipMemcpyAsync(fh.data(), flags, (size_t)nq * 4, hipMemcpyDeviceToHost, ctx->stream));
   LH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
   uint32_t n_over = 0, n_amb = 0, n_bad = 0;
   for (uint32_t i = 0; i < nq; ++i) { n_over += (fh[i] & FLAG_OVERFLOW) ? 1 : 0; n_amb += (fh[i] & FLAG_AMBIGUOUS) ? 1 : 0; n_bad += (fh[i] & FLAG_BADROW) ? 1 : 0; }
+  if (n_bad && badrow_msg) {      // a caller outside the index searches (combine.hip) names its own column
+    set_error("%s (%u queries)", badrow_msg, n_bad);
+    return LANCE_HIP_EINVAL;
+  }
   if (n_bad) {
     set_error("search: refine met row ids beyond the %s raw vectors given to lance_hip_index_set_raw (%u queries): the raw array must be "
               "indexed by the stored row ids", "attached", n_bad);

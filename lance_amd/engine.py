@@ -707,6 +707,34 @@ class Engine:
                                             _ptr(out_i), _ptr(out_d)))
         return out_i, out_d
 
+    def take_flat_knn(self, x, q, ids_a, k, metric="l2", ids_b=None, dists_b=None, lower=None, upper=None):
+        """`take` + `flat_knn` over candidate lists (lance_hip_take_flat_knn; scanner.rs:2884-2904, 3336-3468): per query the rows
+        ids_a [nq][ca] and ids_b [nq][cb] (int64, -1 = an empty slot; a row id is a row index of x [n][d]) are scored against the
+        column with the query as given -- the distance flat_topk returns for that (row, query), bit for bit --, tested against
+        lower <= d < upper (flat_topk's bounds: None is not tested) and the k best by (distance, row id) returned; nothing is
+        de-duplicated.  dists_b: list B's distances as flat_topk returned them, taken as they are; None: its rows are scored
+        too.  -> (ids [nq][k] int64, distances [nq][k]); missing slots: id -1, distance +inf.  ca + cb <= 4096, k <= 1024."""
+        rng = _flat_range_args(lower, upper) or (0, 0.0, 0, 0.0)
+        x, dt = _vec(x)
+        n, d = x.shape
+        q = _like(q, x).reshape(-1, d)
+        nq = q.shape[0]
+        a = to_device(ids_a, torch.int64).reshape(nq, -1)
+        b = None if ids_b is None else to_device(ids_b, torch.int64).reshape(nq, -1)
+        db = None
+        if dists_b is not None:
+            if b is None:
+                raise ValueError("take_flat_knn: dists_b given without ids_b")
+            db = to_device(dists_b, torch.float32).reshape(nq, -1)
+            if db.shape != b.shape:
+                raise ValueError(f"take_flat_knn: dists_b {tuple(db.shape)} does not match ids_b {tuple(b.shape)}")
+        ids = torch.empty((nq, k), dtype=torch.int64, device=x.device)
+        dists = torch.empty((nq, k), dtype=torch.float32, device=x.device)
+        torch.cuda.synchronize()
+        check(self.lib.lance_hip_take_flat_knn(self.h, dt, METRICS[metric], _ptr(x), n, d, _ptr(q), nq, _ptr(a), a.shape[1], _ptr(b),
+                                               _ptr(db), 0 if b is None else b.shape[1], *rng, k, _ptr(ids), _ptr(dists)))
+        return ids, dists
+
     def ubench(self, what):
         """in-process ceilings for bench.py (lance_hip_ubench): "lds4" / "lds8" / "lds16" lane-gathers per second,
         "copy" bytes per second, "valu" / "valu_pk" f32 wave-instructions per second"""

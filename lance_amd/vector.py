@@ -935,11 +935,15 @@ def _transform_rows(eng, itype, metric, x, cent, codebook=None, bounds=None, tim
 
 
 def create_index(x, index_type="IVF_PQ", metric="l2", num_partitions=256, num_sub_vectors=16, num_bits=None, max_iters=50,
-                 sample_rate=256, ivf_centroids=None, pq_codebook=None, seed=42, keep_raw=True, engine=None, rq_rotation=None, _row_ids=None):
+                 sample_rate=256, ivf_centroids=None, pq_codebook=None, seed=42, keep_raw=True, engine=None, rq_rotation=None, _row_ids=None,
+                 _sq_bounds=None):
     """Dataset.create_index(column, "IVF_PQ", ...) for a vector matrix resident (or copied) in HBM.
     num_bits: None = the index type's default (8 for IVF_PQ / IVF_SQ, 1 for IVF_RQ, as in the reference's build parameters).
     rq_rotation: IVF_RQ only (ignored otherwise) -- the [d][d] float32 rotation of the model; None: rq_rotation_matrix(d, seed).
-    _row_ids: IVF_PQ only, create_multivector_index's -- the id stored with every row (several rows may share one); None: the row index."""
+    _row_ids: create_multivector_index's and VectorColumn.create_delta's -- the id stored with every row (several rows may share one);
+    None: the row index.  With ids of their own the raw vectors are NOT attached (they are indexed by row id: the caller attaches the
+    column) and the wrappers keep no per-row columns (prefiltered() refuses; nearest(prefilter=) needs none).
+    _sq_bounds: IVF_SQ only, VectorColumn.create_delta's -- the quantiser's (start, end) of an earlier delta instead of training."""
     # ---- argument rules of Dataset.create_index (python/python/lance/dataset.py:2708-2960), checked before any device work
     if not isinstance(metric, str):
         raise ValueError(f"Metric {metric} not supported.")
@@ -1032,10 +1036,10 @@ def create_index(x, index_type="IVF_PQ", metric="l2", num_partitions=256, num_su
             raise
     if itype == "IVF_FLAT":
         part, xs = _transform_rows(eng, itype, params.metric, x, cent, timed=timed)
-        fx = timed("build_partitions", lambda: DeviceFlatIndex.create(eng, params.metric, cent, xs, part))
-        out = IvfFlatIndex(fx, params, stats, part)
-        out._x = xs if keep_raw else None     # the stored rows (borrowed): needed to re-partition under a prefilter
-        out._rows_offered = n
+        fx = timed("build_partitions", lambda: DeviceFlatIndex.create(eng, params.metric, cent, xs, part, _row_ids))
+        out = IvfFlatIndex(fx, params, stats, part if _row_ids is None else None)
+        out._x = xs if keep_raw and _row_ids is None else None     # the stored rows (borrowed): needed to re-partition under a prefilter
+        out._rows_offered = n if _row_ids is None else None
         return out
     if itype == "IVF_RQ":
         rot = to_device(np.asarray(rq_rotation_matrix(d, seed) if rq_rotation is None else
@@ -1052,21 +1056,21 @@ def create_index(x, index_type="IVF_PQ", metric="l2", num_partitions=256, num_su
             return part, dvc
         part, dvc = timed("transform", transform)
         codes, add, scale = timed("encode", lambda: eng.rq_encode(x, part, dvc, cent, rot, params.metric))
-        rx = timed("build_partitions", lambda: DeviceRqIndex.create(eng, params.metric, cent, rot, codes, add, scale, part))
-        if keep_raw:
+        rx = timed("build_partitions", lambda: DeviceRqIndex.create(eng, params.metric, cent, rot, codes, add, scale, part, row_ids=_row_ids))
+        if keep_raw and _row_ids is None:
             rx.set_raw(x)
-        out = IvfRqIndex(rx, params, stats, part)
-        out._rows_offered = n
+        out = IvfRqIndex(rx, params, stats, part if _row_ids is None else None)
+        out._rows_offered = n if _row_ids is None else None
         return out
     if itype == "IVF_SQ":
         # the quantiser trains on its own sample of the column (train_sq_bounds)
-        bounds = timed("train_sq", lambda: train_sq_bounds(x, params, eng))
+        bounds = timed("train_sq", lambda: train_sq_bounds(x, params, eng)) if _sq_bounds is None else (float(_sq_bounds[0]), float(_sq_bounds[1]))
         part, codes = _transform_rows(eng, itype, params.metric, x, cent, bounds=bounds, timed=timed)
-        sx = timed("build_partitions", lambda: DeviceSqIndex.create(eng, params.metric, cent.to(x.dtype), codes, part, bounds))
-        if keep_raw:
+        sx = timed("build_partitions", lambda: DeviceSqIndex.create(eng, params.metric, cent.to(x.dtype), codes, part, bounds, _row_ids))
+        if keep_raw and _row_ids is None:
             sx.set_raw(x)          # the ORIGINAL column (a cosine index encoded its normalised rows): refine scores against it
-        out = IvfSqIndex(sx, params, stats, part, codes if keep_raw else None)
-        out._rows_offered = n
+        out = IvfSqIndex(sx, params, stats, part if _row_ids is None else None, codes if keep_raw and _row_ids is None else None)
+        out._rows_offered = n if _row_ids is None else None
         return out
     if num_bits not in (4, 8):
         raise ValueError(f"ProductQuantization: num_bits {num_bits} not supported")
@@ -1080,7 +1084,7 @@ def create_index(x, index_type="IVF_PQ", metric="l2", num_partitions=256, num_su
                 pq_pool.shutdown(wait=True)
     part, codes = _transform_rows(eng, itype, params.metric, x, cent, codebook=cb, timed=timed)
     ix = timed("build_partitions", lambda: DeviceIndex.create(eng, params.metric, cent, cb, part, codes, _row_ids,
-                                                              raw=x if keep_raw else None,
+                                                              raw=x if keep_raw and _row_ids is None else None,
                                                               dtype="int8" if x.dtype == torch.int8 else None))
     # Index::prewarm (ivf/v2.rs:349-352): the search-side constants (matrix-core scan tables, the lossless u8 refine copy of an
     # integer-valued f32 column) are built here, inside the build's clock, instead of inside the first search
@@ -1343,3 +1347,302 @@ def create_multivector_index(values, offsets, metric="cosine", num_partitions=25
         vt = values.to(flat._ix.centroids.device) if isinstance(values, torch.Tensor) else to_device(values)
     out = IvfPqMultivectorIndex(flat._ix, flat.params, flat.stats, vt, to_device(off))
     return out
+
+
+# ---- a column whose index is behind its rows: deltas + unindexed fragments ----------------------------------------------
+TAKE_FLAT_KNN_MAX_CANDIDATES = 4096      # lance_hip_take_flat_knn: ca + cb
+
+
+def _index_type_of(index):
+    for cls, name in ((IvfPqIndex, "IVF_PQ"), (IvfFlatIndex, "IVF_FLAT"), (IvfSqIndex, "IVF_SQ"), (IvfRqIndex, "IVF_RQ")):
+        if isinstance(index, cls):
+            return name
+    if isinstance(index, IvfPqMultivectorIndex):
+        raise NotImplementedError("VectorColumn: multivector columns and their indices are not supported")
+    raise TypeError(f"VectorColumn: {type(index).__name__} is not an index of this package")
+
+
+class VectorColumn:
+    """A vector column as a Lance dataset holds it after appends: the rows x [N][d] resident in HBM, split into fragments (consecutive
+    row blocks), zero or more DELTA indices built with one model, each covering a set of fragments (IndexMetadata.fragment_bitmap), and
+    whatever fragments no index covers yet.  The row id is the row index.  `nearest` is the reference's plan for such a column
+    (Scanner::nearest, scanner.rs:2847-3030, 3336-3468); every method that changes the column returns a NEW column and leaves this one
+    as it is.  x: numpy (copied to HBM once) or a torch tensor (kept by reference).  Multivector columns are refused."""
+
+    def __init__(self, x, fragment_sizes=None, engine=None):
+        if isinstance(x, (list, tuple)) or len(getattr(x, "shape", ())) != 2:
+            raise NotImplementedError("VectorColumn: multivector columns are not supported (a [N][d] matrix is required); "
+                                      "see create_multivector_index")
+        self._engine = engine
+        self._x = x if isinstance(x, torch.Tensor) else to_device(x)
+        n = int(self._x.shape[0])
+        sizes = [n] if fragment_sizes is None else [int(s) for s in fragment_sizes]
+        if any(s < 0 for s in sizes) or sum(sizes) != n:
+            raise ValueError(f"VectorColumn: fragment_sizes must be non-negative and sum to the {n} rows, got {sizes}")
+        self._offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        self._deltas = ()          # ((index, frozenset of fragment ids), ...) in the order they were added
+
+    # ---- what the column is made of ----
+    @property
+    def num_fragments(self):
+        return int(self._offsets.size) - 1
+
+    @property
+    def deltas(self):
+        """the delta indices, oldest first"""
+        return [ix for ix, _ in self._deltas]
+
+    def indexed_fragments(self):
+        out = set()
+        for _, frags in self._deltas:
+            out |= frags
+        return out
+
+    def unindexed_fragments(self):
+        covered = self.indexed_fragments()
+        return [f for f in range(self.num_fragments) if f not in covered]
+
+    def _runs(self, fragments):
+        """contiguous runs of the given fragment ids -> [(first row, end row)], empty runs dropped"""
+        runs, frags = [], sorted(fragments)
+        i = 0
+        while i < len(frags):
+            j = i
+            while j + 1 < len(frags) and frags[j + 1] == frags[j] + 1:
+                j += 1
+            r0, r1 = int(self._offsets[frags[i]]), int(self._offsets[frags[j] + 1])
+            if r1 > r0:
+                runs.append((r0, r1))
+            i = j + 1
+        return runs
+
+    def _engine_or_default(self):
+        return self._engine or default_engine()
+
+    def _copy(self, deltas):
+        out = VectorColumn.__new__(VectorColumn)
+        out._engine, out._x, out._offsets, out._deltas = self._engine, self._x, self._offsets, tuple(deltas)
+        return out
+
+    def _check_fragments(self, fragments, what):
+        frags = frozenset(int(f) for f in fragments)
+        bad = sorted(f for f in frags if not 0 <= f < self.num_fragments)
+        if bad:
+            raise ValueError(f"{what}: fragments {bad} do not exist (the column has {self.num_fragments})")
+        return frags
+
+    # ---- maintenance ----
+    def with_index(self, index, fragments):
+        """The column with `index` as one more delta over the given fragment ids.  The index must store the column's row ids (the row
+        index).  Refused: fragments another delta covers; a metric, element type, index type or dimension other than the first delta's."""
+        itype = _index_type_of(index)
+        frags = self._check_fragments(fragments, "with_index")
+        both = sorted(frags & self.indexed_fragments())
+        if both:
+            raise ValueError(f"with_index: fragments {both} are covered by another delta (fragment bitmaps of deltas do not overlap)")
+        d = int(index._ix.centroids.shape[1])
+        if d != int(self._x.shape[1]):
+            raise ValueError(f"with_index: the index has dimension {d}, the column {int(self._x.shape[1])}")
+        if self._deltas:
+            first = self._deltas[0][0]
+            mine = (itype, _normalize_metric_type(index.params.metric), index._ix.data_dtype, d)
+            theirs = (_index_type_of(first), _normalize_metric_type(first.params.metric), first._ix.data_dtype, int(first._ix.centroids.shape[1]))
+            for name, a, b in zip(("index type", "metric", "element type", "dimension"), mine, theirs):
+                if a != b:
+                    raise ValueError(f"with_index: {name} {a} differs from the first delta's {b} (the deltas of a column share one model)")
+        return self._copy(self._deltas + ((index, frags),))
+
+    def _rows_of(self, fragments):
+        runs = self._runs(fragments)
+        if not runs:
+            return None
+        dev = self._x.device
+        return torch.cat([torch.arange(r0, r1, dtype=torch.int64, device=dev) for r0, r1 in runs])
+
+    def create_delta(self, fragments=None, **create_index_args):
+        """The column with a new delta over the rows of `fragments` (default: every unindexed fragment), storing the column's row ids.
+        With a delta already there its model is used -- centroids, and codebook / quantiser bounds / rotation: an index type, metric or
+        size in create_index_args that differs from that delta's, or a model of the caller's, is refused -- otherwise create_index
+        trains one from those rows with create_index_args.  keep_raw is not the caller's to give: the column itself is attached."""
+        for name in ("keep_raw", "_row_ids", "_sq_bounds"):
+            if name in create_index_args:
+                raise ValueError(f"create_delta: {name} is set by the column (its row ids are stored and the column is attached)")
+        frags = self._check_fragments(self.unindexed_fragments() if fragments is None else fragments, "create_delta")
+        both = sorted(frags & self.indexed_fragments())
+        if both:
+            raise ValueError(f"create_delta: fragments {both} are covered by another delta")
+        rows = self._rows_of(frags)
+        if rows is None:
+            raise ValueError("create_delta: no rows to index (no unindexed fragment holds a row)")
+        args = dict(create_index_args)
+        if self._deltas:
+            first = self._deltas[0][0]
+            itype, p = _index_type_of(first), first.params
+            theirs = {"index_type": itype, "metric": _normalize_metric_type(p.metric), "num_partitions": int(first._ix.centroids.shape[0])}
+            if itype == "IVF_PQ":
+                theirs.update(num_sub_vectors=p.num_sub_vectors, num_bits=p.num_bits)
+            for name, want in theirs.items():
+                got = args.get(name)
+                if name == "index_type" and got is not None:
+                    got = str(got).upper()
+                elif name == "metric" and got is not None:
+                    got = _normalize_metric_type(got)
+                if got is not None and got != want:
+                    raise ValueError(f"create_delta: {name}={args[name]} differs from the first delta's {want} (the deltas of a column share one model)")
+            for name in ("ivf_centroids", "pq_codebook", "rq_rotation"):
+                if args.get(name) is not None:
+                    raise ValueError(f"create_delta: {name} was given, but the column has a delta: its model is used")
+            args.update(index_type=itype, metric=p.metric, num_partitions=int(first._ix.centroids.shape[0]), ivf_centroids=first.centroids)
+            if itype == "IVF_PQ":
+                args.update(num_sub_vectors=p.num_sub_vectors, num_bits=p.num_bits, pq_codebook=first.codebook)
+            elif itype == "IVF_SQ":
+                args.update(_sq_bounds=first.bounds)
+            elif itype == "IVF_RQ":
+                args.update(rq_rotation=first.rotation)
+        args.setdefault("engine", self._engine)
+        index = create_index(self._x[rows], _row_ids=rows, keep_raw=False, **args)
+        if hasattr(index._ix, "set_raw"):
+            index._ix.set_raw(self._x)         # indexed by row id: index.nearest(refine_factor=) of the delta alone works too
+        return self.with_index(index, frags)
+
+    def optimize(self):
+        """The column with its unindexed fragments folded into the LAST delta by that index's `append` (its model, nothing re-trained).
+        IVF_RQ has no append: it refuses with its own message -- use create_delta there."""
+        tail = self.unindexed_fragments()
+        if not self._deltas:
+            raise ValueError("optimize: the column has no index to fold rows into (create_delta builds one)")
+        last, frags = self._deltas[-1]
+        rows = self._rows_of(tail)
+        if rows is None:
+            return self._copy(self._deltas[:-1] + ((last, frags | frozenset(tail)),))
+        kw = {"raw": self._x} if isinstance(last, IvfPqIndex) else {}
+        grown = last.append(self._x[rows], row_ids=rows, **kw)
+        return self._copy(self._deltas[:-1] + ((grown, frags | frozenset(tail)),))
+
+    # ---- the search plan ----
+    def _ann(self, index, itype, q, keff, nprobes, prefilter, rng):
+        """one delta's own search for keff rows, un-refined -> (ids int64, distances) on the device"""
+        ix = index._ix
+        if itype == "IVF_PQ":
+            if rng:
+                return ix.search_range(q, keff, nprobes, rng.get("lower"), rng.get("upper"), refine_factor=0, allow=prefilter)
+            return ix.search(q, keff, nprobes, 0) if prefilter is None else ix.search_filtered(q, keff, nprobes, prefilter, 0)
+        if itype == "IVF_FLAT":
+            if rng:
+                return ix.search(q, keff, nprobes, allow=prefilter, lower=rng.get("lower"), upper=rng.get("upper"))
+            return ix.search(q, keff, nprobes) if prefilter is None else ix.search(q, keff, nprobes, allow=prefilter)
+        return ix.search(q, keff, nprobes) if prefilter is None else ix.search(q, keff, nprobes, allow=prefilter)
+
+    def _refines_on_this_column(self, index, itype):
+        """True when the delta re-ranks inside its own search AND on this very column (the tensor attached to it is the column's storage):
+        steps 2 and 3 of a single un-ranged delta are then that one search -- the same ids and distance bits as the search for keff
+        rows followed by take_flat_knn (tests/test_zz_gpu_knn_combined.py compares the two), without the second kernel's pass"""
+        raw = getattr(index._ix, "_raw", None)
+        return (itype != "IVF_FLAT" and isinstance(raw, torch.Tensor) and raw.data_ptr() == self._x.data_ptr()
+                and raw.dtype == self._x.dtype and tuple(raw.shape) == tuple(self._x.shape))
+
+    def _ann_refined(self, index, itype, q, k, nprobes, prefilter, refine_factor):
+        """the delta's own search with its refine: k rows by the exact distance out of k * refine_factor by the index's"""
+        ix = index._ix
+        if itype == "IVF_PQ":
+            return ix.search(q, k, nprobes, refine_factor) if prefilter is None else ix.search_filtered(q, k, nprobes, prefilter, refine_factor)
+        return ix.search(q, k, nprobes, allow=prefilter, refine_factor=refine_factor)
+
+    def _tail_lists(self, eng, q, k, metric, prefilter, rng):
+        """flat_knn(k) over every contiguous run of unindexed fragments, with the rows' ids, the prefilter and the bounds"""
+        dev = self._x.device
+        allow = None
+        if prefilter is not None:
+            allow = prefilter if isinstance(prefilter, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(prefilter, dtype=bool))
+            allow = allow.to(dev)
+        lists = []
+        for r0, r1 in self._runs(self.unindexed_fragments()):
+            rid = torch.arange(r0, r1, dtype=torch.int64, device=dev)
+            if allow is not None:
+                inside = rid[rid < allow.numel()]
+                rid = inside[allow[inside]]
+                if rid.numel() == 0:
+                    continue
+                xs = self._x[rid].contiguous()
+            else:
+                xs = self._x[r0:r1]
+            lists.append(eng.flat_topk(xs, q, k, metric, row_ids=rid, **rng))
+        return lists
+
+    def _combine(self, eng, q, ids_a, lists, k, metric, rng):
+        """take_flat_knn of list A with the tail lists, several per call up to the candidate limit, chained beyond it: the k best of
+        (the k best of a part of the candidates) and the rest are the k best of all of them"""
+        pend = []
+        for bi, bd in lists:
+            if pend and ids_a.shape[1] + sum(int(i.shape[1]) for i, _ in pend) + int(bi.shape[1]) > TAKE_FLAT_KNN_MAX_CANDIDATES:
+                ids_a, _ = eng.take_flat_knn(self._x, q, ids_a, k, metric, ids_b=torch.cat([i for i, _ in pend], 1),
+                                             dists_b=torch.cat([d for _, d in pend], 1), **rng)
+                pend = []
+            pend.append((bi, bd))
+        if not pend:
+            return eng.take_flat_knn(self._x, q, ids_a, k, metric, **rng)
+        return eng.take_flat_knn(self._x, q, ids_a, k, metric, ids_b=torch.cat([i for i, _ in pend], 1),
+                                 dists_b=torch.cat([d for _, d in pend], 1), **rng)
+
+    def nearest(self, q, k=10, nprobes=1, refine_factor=None, prefilter=None, distance_range=None, fast_search=False, use_index=True,
+                metric=None, minimum_nprobes=None, maximum_nprobes=None):
+        """-> (row ids int64 [nq][k] (-1 = missing), distances f32 [nq][k]) as numpy: Scanner::nearest over the whole column.
+        1. use_index=False, or no delta: flat_knn over the column with the prefilter and the range (scanner.rs:2912-2942).
+        2. ANN over every delta for keff = k * (refine_factor or 1) rows -- each delta's own search takes the prefilter and, where the
+           index type answers ranges (IVF_PQ, IVF_FLAT), the bounds, tested on the INDEX's distances inside the partitions --, the
+           lists joined by (distance, row id) and cut to keff (lance_hip_merge_topk; one delta needs no merge).
+        3. With a refine_factor: take_flat_knn over those keff ids, the bounds on the EXACT distances, fetch k.  (A single un-ranged
+           IVF_PQ / IVF_SQ / IVF_RQ delta that has this very column attached for its own refine answers steps 2 and 3 in one search of
+           its own: the same ids and distance bits, without the second pass.)
+        4. fast_search=True, or no unindexed fragment: done.
+        5. Otherwise flat_knn(k) over the unindexed fragments (their rows' ids, the prefilter, the bounds) and take_flat_knn of the
+           list so far with that tail list: every distance exact, the bounds on them, the k best by (distance, row id); a row id in
+           both lists comes back twice (the reference's UnionExec does not de-duplicate).
+        So an un-refined ANN list comes back with EXACT distances when, and only when, the column holds unindexed rows: that is what
+        the reference's knn_combined does.  With one delta, no unindexed rows and no range the answer is `index.nearest(...)`'s, bit
+        for bit, with and without refine_factor.  With a range AND a refine_factor it differs from IvfPqIndex.nearest by design: the
+        column filters the exact distances, as the scanner does; lance_hip_ivfpq_search_range does not.
+        metric: of the flat scan when the column has no delta (default l2); with deltas it is theirs.
+        Limits of the plan (the library refuses beyond them, with its own message): k <= 1024; keff = k * refine_factor <= 4096
+        (take_flat_knn's candidates) and, with several deltas, deltas * keff <= 4096 (merge_topk's); each delta's own search is asked
+        for keff rows and has its index type's limit on that -- these are not the limits of index.nearest, which re-ranks inside.
+        Refused: minimum_nprobes / maximum_nprobes (how the reference's late search interacts across deltas is not established here);
+        distance_range on IVF_SQ / IVF_RQ deltas (those indices' own message); refine_factor=0."""
+        for name, val in (("minimum_nprobes", minimum_nprobes), ("maximum_nprobes", maximum_nprobes)):
+            if val is not None:
+                raise NotImplementedError(f"VectorColumn.nearest: {name} is not supported (adaptive probing across delta indices)")
+        if refine_factor is not None and int(refine_factor) < 1:
+            raise ValueError("Refine factor can not be zero")
+        rng = _flat_distance_range(distance_range)
+        k = int(k)
+        searched = use_index and bool(self._deltas)
+        if self._deltas:
+            first = self._deltas[0][0]
+            itype = _index_type_of(first)
+            if metric is not None and _normalize_metric_type(metric) != _normalize_metric_type(first.params.metric):
+                raise ValueError(f"VectorColumn.nearest: metric {metric} is not the deltas' ({first.params.metric})")
+            metric = _normalize_metric_type(first.params.metric)
+            if searched and rng and itype in ("IVF_SQ", "IVF_RQ"):
+                raise NotImplementedError(f"{itype}: distance_range is not supported by this engine")
+        else:
+            metric = _normalize_metric_type("l2" if metric is None else metric)
+        eng = self._engine_or_default()
+        if not searched:
+            ids, dists = flat_knn(self._x, q, k, metric, engine=eng, prefilter=prefilter, distance_range=distance_range)
+            return ids.cpu().numpy(), dists.cpu().numpy()
+        keff = k * (1 if refine_factor is None else int(refine_factor))
+        tail = (not fast_search) and bool(self._runs(self.unindexed_fragments()))
+        if refine_factor is not None and len(self._deltas) == 1 and not rng and self._refines_on_this_column(first, itype):
+            # steps 2 and 3 in the delta's own pipeline: the same answer bit for bit, one pass less (DESIGN.md 4h, measurement (a))
+            ids, dists = self._ann_refined(first, itype, q, k, nprobes, prefilter, int(refine_factor))
+        else:
+            found = [self._ann(ix, itype, q, keff, nprobes, prefilter, rng) for ix, _ in self._deltas]
+            if len(found) == 1:
+                ids, dists = found[0]
+            else:
+                ids, dists = eng.merge_topk(torch.cat([i for i, _ in found], 1), torch.cat([d for _, d in found], 1), keff)
+            if refine_factor is not None:
+                ids, dists = eng.take_flat_knn(self._x, q, ids, k, metric, **rng)
+        if tail:
+            ids, dists = self._combine(eng, q, ids, self._tail_lists(eng, q, k, metric, prefilter, rng), k, metric, rng)
+        return ids.cpu().numpy(), dists.cpu().numpy()
