@@ -591,6 +591,11 @@ int lance_hip_ivfsq_search_refine(lance_hip_ctx *ctx, const lance_hip_index *idx
 int lance_hip_ivfrq_search_refine(lance_hip_ctx *ctx, const lance_hip_index *idx, const float *q, uint32_t nq, uint32_t k,
                                   uint32_t nprobes, uint32_t refine_factor, const uint8_t *allow_by_rowid /* NULL = none */,
                                   uint64_t n_allow, uint64_t *ids, float *dists);
+/* Which scan stage an IVF_SQ search of nq queries takes (decided once per call, before anything is enqueued): 1 = the partition-major
+ * scan on the int8 matrix cores (keff = k * refine_factor <= 128 and nq * nprobes >= 64 * nlist, unless
+ * LANCE_HIP_NO_SQ_GROUPED is set: pass it as grouped_off), 0 = one workgroup per (query, probed partition).  Both fill the same
+ * candidate lists: the answer does not depend on it.  A pure function: no context, no device.                                  */
+int lance_hip_ivfsq_plan(uint32_t nq, uint32_t nprobes, uint32_t nlist, uint32_t keff, int grouped_off);
 
 /* ---- N5: 8-bit scalar quantisation and IVF_SQ (lance-index/src/vector/sq.rs, sq/storage.rs, sq/builder.rs) ------------ */
 /* Columns are LANCE_HIP_F32 or LANCE_HIP_F16 (an int8 column is refused: the reference's SQ builder takes float arrays only; f64

@@ -21,6 +21,7 @@
 
 #include <algorithm>
 #include <string>
+#include <type_traits>
 
 #include "common.h"
 #include "exact.cuh"
@@ -281,8 +282,19 @@ static inline int cand_scan_cap(int k, size_t fixed, size_t borrow = 0) {
 // timers [0]: keff <= CAND_NARROW_K, [1]: above -- the name says which capacity class ran.  String literals: a captured call keeps the pointers.
 struct CandNames {
   const char *slots;             // prefix of the scratch slots ("ivfsq")
-  const char *scan[2], *merge[2], *exact[2];
+  const char *scan[2], *merge[2], *exact[2];      // scan[i] == NULL: the scan callable times its own steps
 };
+
+// queries per launch: the per-pair candidate lists stay within 2^24 entries
+static inline uint32_t cand_queries_per_launch(uint32_t nq, uint32_t nprobes, uint32_t k) {
+  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nq, (1ull << 24) / ((uint64_t)nprobes * k)));
+}
+// a scan callable may return void (it only launches) or a status
+template <class Scan>
+static int cand_run_scan(Scan &scan, const CandLists &w, uint32_t q0, uint32_t nqc) {
+  if constexpr (std::is_void_v<decltype(scan(w, q0, nqc))>) { scan(w, q0, nqc); return LANCE_HIP_OK; }
+  else return scan(w, q0, nqc);
+}
 
 // sq.hip: the merge launch (one instantiation of each merge instance in the library), picked by w.k
 int cand_merge_lists(lance_hip_ctx *ctx, const CandLists &w, uint32_t nq, uint64_t *ids, float *dists, const char *timer);
@@ -297,8 +309,7 @@ static int cand_search(lance_hip_ctx *ctx, const lance_hip_index *idx, const Can
   const uint32_t k = (uint32_t)w.k, nprobes = (uint32_t)w.nprobes;
   const int wide = k > (uint32_t)CAND_NARROW_K;
   auto slot = [&](const char *what) { return std::string(nm.slots) + what; };
-  // queries per launch: the per-pair candidate lists stay within 2^24 entries
-  const uint32_t qch = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nq, (1ull << 24) / ((uint64_t)nprobes * k)));
+  const uint32_t qch = cand_queries_per_launch(nq, nprobes, k);
   const size_t pairs = (size_t)qch * nprobes;
   w.pkey = ctx->scratch_t<uint32_t>(slot(".pkey").c_str(), pairs * k);
   w.ppos = ctx->scratch_t<uint32_t>(slot(".ppos").c_str(), pairs * k);
@@ -325,9 +336,11 @@ static int cand_search(lance_hip_ctx *ctx, const lance_hip_index *idx, const Can
     w.probes = probes + (size_t)q0 * nprobes; w.flags = flags + q0;
     uint64_t *oid = (refine ? cand : ids) + (size_t)q0 * k;
     float *od = (refine ? cand_d : dists) + (size_t)q0 * k;
-    {
+    if (nm.scan[wide]) {
       ScopedTimer t(ctx, nm.scan[wide]);
-      scan(w, q0, nqc);
+      LH_TRY(cand_run_scan(scan, w, q0, nqc));
+    } else {
+      LH_TRY(cand_run_scan(scan, w, q0, nqc));
     }
     LH_TRY(cand_merge_lists(ctx, w, nqc, oid, od, nm.merge[wide]));
     {

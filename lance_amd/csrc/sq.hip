@@ -21,6 +21,7 @@
 // out; a query is flagged when an ambiguous pair's k-th key is not above the k-th key of the merged candidates, and flagged queries
 // are replayed through std BinaryHeap's push / pop in storage order (the IVF_FLAT replay with the SQ distance).  The final order is
 // (dist, rowid).  k here is keff = k * refine_factor under a refine_factor: up to 128 in a 512-entry buffer, up to 768 in a wide one.
+// Batches with many pairs per partition fill the same lists partition-major on the int8 matrix cores instead (sq_pm.cuh).
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -255,6 +256,10 @@ static float sq_r2(double lo, double hi) {
 
 static unsigned sq_grid(uint64_t count) { return grid_stride_blocks(count, 256, 2048); }
 
+}  // namespace lh
+#include "sq_pm.cuh"      // the partition-major scan of large batches (ivfsq_pm_scan_kernel) and its plan
+namespace lh {
+
 // rows of `dtype` elements -> codes out[row * ldo + col]
 static int sq_encode_launch(lance_hip_ctx *ctx, int dtype, const void *x, uint64_t n, uint32_t d, double lo, double hi, int64_t ldo, uint8_t *out) {
   const uint64_t count = n * d;
@@ -426,10 +431,13 @@ extern "C" int lance_hip_ivfsq_create(lance_hip_ctx *ctx, int dtype, int metric,
 }
 
 static const CandNames SQ_NAMES = {"ivfsq", {"ivfsq_scan", "ivfsq_wide_scan"}, {"ivfsq_merge", "ivfsq_wide_merge"}, {"ivfsq_exact", "ivfsq_wide_exact"}};
+// the partition-major scan times its own two steps (ivfsq_pm_group, ivfsq_pm_scan): no scan timer around them
+static const CandNames SQ_PM_NAMES = {"ivfsq", {nullptr, nullptr}, {"ivfsq_merge", "ivfsq_wide_merge"}, {"ivfsq_exact", "ivfsq_wide_exact"}};
 
 // refine_factor == 0: the k best by the SQ distance.  Otherwise (lance_hip_ivfsq_search_refine, which has checked the arguments) the
 // keff = k * refine_factor best are candidates [nq][keff] in the scratch arena, re-scored against the raw vectors with the ORIGINAL query
-// (cand_search, pair_cand.cuh)
+// (cand_search, pair_cand.cuh).  Large batches at the narrow capacity take the partition-major scan (sq_pm.cuh: plan_ivfsq_grouped); the
+// stages behind the scan do not know which one filled the lists.
 static int ivfsq_search_impl(lance_hip_ctx *ctx, const lance_hip_index *idx, const void *q, uint32_t nq, uint32_t k, uint32_t nprobes,
                              const uint32_t *allow, uint64_t *ids, float *dists, uint32_t refine_factor = 0) {
   const bool refine = refine_factor != 0;
@@ -467,11 +475,17 @@ static int ivfsq_search_impl(lance_hip_ctx *ctx, const lance_hip_index *idx, con
   a.w.row_ids = idx->row_ids; a.w.part_offsets = idx->part_offsets; a.w.allow = allow; a.w.nprobes = (int)nprobes; a.w.k = (int)keff;
   a.w.cap = sq_scan_cap(ld, (int)keff);
   auto chunk = [&](const CandLists &w, uint32_t q0) { a.w = w; a.qcodes = qc + (size_t)q0 * ld; a.qq = qq + q0; };
+  const bool grouped = sqpm_forced_g() < 0 ? plan_ivfsq_grouped(nq, nprobes, idx->sq_nlist, keff, sqpm_switched_off())
+                                           : plan_ivfsq_grouped(nq, nprobes, idx->sq_nlist, keff, sqpm_switched_off(), (uint32_t)sqpm_forced_g());
+  SqPmScratch pm;
+  if (grouped) LH_TRY(sqpm_scratch(ctx, (size_t)std::min<uint64_t>(nq, cand_queries_per_launch(nq, nprobes, keff)) * nprobes, idx->sq_nlist, &pm));
   return cand_search(
-      ctx, idx, SQ_NAMES, a.w, probes, nq, k, refine, q_orig, ids, dists,
+      ctx, idx, grouped ? SQ_PM_NAMES : SQ_NAMES, a.w, probes, nq, k, refine, q_orig, ids, dists,
       [&](const CandLists &w, uint32_t q0, uint32_t nqc) {
         chunk(w, q0);
+        if (grouped) return sqpm_scan(ctx, a, nqc, idx->sq_nlist, pm);
         hipLaunchKernelGGL(sq_scan_kernel, dim3(nqc * nprobes), dim3(256), sq_scan_lds(ld, w.cap), ctx->stream, a);
+        return (int)LANCE_HIP_OK;
       },
       [&](const CandLists &w, uint32_t q0, uint32_t nqc, uint64_t *oid, float *od) {
         chunk(w, q0);
@@ -484,6 +498,10 @@ static int ivfsq_check(lance_hip_ctx *ctx, const lance_hip_index *idx, const voi
   LH_REQUIRE(idx->sq && idx->codes, "ivfsq_search: not an IVF_SQ index");
   LH_REQUIRE(ctx->device == idx->device, "ivfsq_search: context and index live on different devices");
   return LANCE_HIP_OK;
+}
+
+extern "C" int lance_hip_ivfsq_plan(uint32_t nq, uint32_t nprobes, uint32_t nlist, uint32_t keff, int grouped_off) {
+  return plan_ivfsq_grouped(nq, nprobes, nlist, keff, grouped_off != 0) ? 1 : 0;
 }
 
 extern "C" int lance_hip_ivfsq_search(lance_hip_ctx *ctx, const lance_hip_index *idx, const void *q, uint32_t nq, uint32_t k,
