@@ -596,6 +596,11 @@ int lance_hip_ivfrq_search_refine(lance_hip_ctx *ctx, const lance_hip_index *idx
  * LANCE_HIP_NO_SQ_GROUPED is set: pass it as grouped_off), 0 = one workgroup per (query, probed partition).  Both fill the same
  * candidate lists: the answer does not depend on it.  A pure function: no context, no device.                                  */
 int lance_hip_ivfsq_plan(uint32_t nq, uint32_t nprobes, uint32_t nlist, uint32_t keff, int grouped_off);
+/* The same for an IVF_RQ search of d-dimensional rows: 1 = the partition-major scan on the int8 matrix cores (no prefilter -- under one
+ * there is no integer sum to multiply: pass it as filtered --, keff <= 128, d a multiple of 8 up to 584, where a block's tables still fit
+ * one workgroup's LDS, and nq * nprobes >= 128 * nlist, unless LANCE_HIP_NO_RQ_GROUPED is set: pass it as grouped_off), 0 = one
+ * workgroup per (query, probed partition).  The answer does not depend on it.  A pure function: no context, no device.          */
+int lance_hip_ivfrq_plan(uint32_t nq, uint32_t nprobes, uint32_t nlist, uint32_t keff, uint32_t d, int filtered, int grouped_off);
 
 /* ---- N5: 8-bit scalar quantisation and IVF_SQ (lance-index/src/vector/sq.rs, sq/storage.rs, sq/builder.rs) ------------ */
 /* Columns are LANCE_HIP_F32 or LANCE_HIP_F16 (an int8 column is refused: the reference's SQ builder takes float arrays only; f64

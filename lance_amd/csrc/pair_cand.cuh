@@ -278,6 +278,72 @@ static inline int cand_scan_cap(int k, size_t fixed, size_t borrow = 0) {
 }
 // ---- pair candidates: end of the code the emulator programs compile -----------------------------------------------------------------
 
+// ---- a block of pairs per workgroup: the selection of the partition-major scans (sq_pm.cuh, rq_pm.cuh) -------------------------------------
+// CAND_BLOCK_PAIRS pairs of one partition share a workgroup; every pair has a buffer of CAND_BLOCK_CAP entries in LDS and is sorted and cut
+// by ONE wave (no workgroup barrier inside the sort).  The contract above does not depend on the capacity or on who sorts.
+constexpr int CAND_BLOCK_PAIRS = 32;
+constexpr int CAND_BLOCK_CAP = 256;
+
+struct CandBlockCtl {              // one word per pair of the block
+  int cnt[CAND_BLOCK_PAIRS];
+  uint32_t thr[CAND_BLOCK_PAIRS], amb_key[CAND_BLOCK_PAIRS];
+  int amb[CAND_BLOCK_PAIRS];
+  int pair[CAND_BLOCK_PAIRS];      // index into the lists (qi * nprobes + j), -1 behind the block's last pair
+};
+
+__device__ __forceinline__ void cand_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// cand_sort_truncate for pair p by ONE wave: sort its buffer, keep the k best, remember a tie cut at the k-th key
+__device__ __forceinline__ void cand_block_sort_truncate(uint64_t *e, CandBlockCtl *ctl, int p, int k, int lane) {
+  const int cnt = ctl->cnt[p];
+  int P = 2;
+  while (P < cnt) P <<= 1;
+  for (int i = cnt + lane; i < P; i += 64) e[i] = ~0ull;
+  cand_wave_sync();
+  for (int k2 = 2; k2 <= P; k2 <<= 1) {
+    for (int j = k2 >> 1; j > 0; j >>= 1) {
+      for (int i = lane; i < P / 2; i += 64) {
+        const int ix = 2 * j * (i / j) + (i % j);
+        const int px = ix + j;
+        const bool up = (ix & k2) == 0;
+        const uint64_t a = e[ix], b = e[px];
+        if ((a > b) == up) { e[ix] = b; e[px] = a; }
+      }
+      cand_wave_sync();
+    }
+  }
+  if (lane == 0 && cnt > k) {
+    const uint32_t kth = (uint32_t)(e[k - 1] >> 32);
+    if ((uint32_t)(e[k] >> 32) == kth) { ctl->amb[p] = 1; ctl->amb_key[p] = kth; }
+    ctl->thr[p] = kth;
+    ctl->cnt[p] = k;
+  }
+  cand_wave_sync();
+}
+
+// the block's lists, each at its own pair index: wave w sorts and writes pairs 8 w .. 8 w + 7 (after a workgroup barrier behind the last push)
+__device__ __forceinline__ void cand_block_write(const CandLists &w, uint64_t *ebuf, CandBlockCtl *ctl, int k, int wave, int lane) {
+  for (int u = 0; u < CAND_BLOCK_PAIRS / 4; ++u) {
+    const int p = wave * (CAND_BLOCK_PAIRS / 4) + u, pair = ctl->pair[p];
+    if (pair < 0) continue;
+    uint64_t *e = ebuf + p * CAND_BLOCK_CAP;
+    if (ctl->cnt[p] > 0) cand_block_sort_truncate(e, ctl, p, k, lane);
+    const int got = min(ctl->cnt[p], k);
+    for (int i = lane; i < got; i += 64) {
+      w.pkey[(int64_t)pair * k + i] = (uint32_t)(e[i] >> 32);
+      w.ppos[(int64_t)pair * k + i] = (uint32_t)e[i];
+    }
+    if (lane == 0) {
+      w.pcnt[pair] = (uint32_t)got;
+      w.pamb[pair] = (got == k && ctl->amb[p] && ctl->amb_key[p] == (uint32_t)(e[k - 1] >> 32)) ? 1u : 0u;
+    }
+  }
+}
+
 // ---- host side: one search, around the scan and the replay launch of the index type ---------------------------------------------------
 // timers [0]: keff <= CAND_NARROW_K, [1]: above -- the name says which capacity class ran.  String literals: a captured call keeps the pointers.
 struct CandNames {

@@ -208,6 +208,16 @@ __device__ __forceinline__ void rq_prepare(const float *__restrict__ q, const fl
   __syncthreads();
 }
 
+// the estimate of a row from its raw table sum, and the packed branch's way to it from the integer sum (rq_pm.cuh's matrix product ends here too)
+__device__ __forceinline__ float rq_finish(float dist, const RqQuery *h, float sqrt_d, float add, float scale) {
+  const float x = __fdiv_rn(2.0f * dist - h->sum_q, sqrt_d);
+  return x * scale + add + h->q_factor;
+}
+__device__ __forceinline__ float rq_packed_tail(uint32_t s, const RqQuery *h, float sqrt_d, float add, float scale) {
+  s = s < 65535u ? s : 65535u;                      // u16 saturating adds of non-negative terms
+  return rq_finish((float)s * h->range + h->sum_min, h, sqrt_d, add, scale);
+}
+
 // one row's distance; `row` points at its d / 8 code bytes (16-byte aligned when cb % 16 == 0)
 __device__ __forceinline__ float rq_row_distance(const uint8_t *__restrict__ row, int cb, int mode, const float *table, const uint8_t *etab,
                                                  const RqQuery *h, float sqrt_d, float add, float scale) {
@@ -231,8 +241,7 @@ __device__ __forceinline__ float rq_row_distance(const uint8_t *__restrict__ row
         s += (uint32_t)etab[(2 * b) * 16 + (code & 15u)] + (uint32_t)etab[(2 * b + 1) * 16 + (code >> 4)];
       }
     }
-    s = s < 65535u ? s : 65535u;                    // u16 saturating adds of non-negative terms
-    dist = (float)s * h->range + h->sum_min;
+    return rq_packed_tail(s, h, sqrt_d, add, scale);
   } else {
     dist = mode == RQ_FILTERED ? -0.0f : 0.0f;      // f32::sum / `dists = vec![0.0; n]`
     if ((cb & 15) == 0) {
@@ -253,8 +262,7 @@ __device__ __forceinline__ float rq_row_distance(const uint8_t *__restrict__ row
       }
     }
   }
-  const float x = __fdiv_rn(2.0f * dist - h->sum_q, sqrt_d);
-  return x * scale + add + h->q_factor;
+  return rq_finish(dist, h, sqrt_d, add, scale);
 }
 
 // distance_all (quantised != 0) or distance of every row (quantised == 0) of ONE partition's storage [n][cb] against residual queries
@@ -395,6 +403,8 @@ static_assert(CAND_MAX_K == LANCE_HIP_SQRQ_MAX_CANDIDATES, "the candidate path's
 
 }  // namespace lh
 
+#include "rq_pm.cuh"      // the partition-major scan of large batches (ivfrq_pm_scan_kernel) and its plan
+
 using namespace lh;
 
 extern "C" int lance_hip_rq_encode(lance_hip_ctx *ctx, int metric, const float *x, uint64_t n, uint32_t d, const uint32_t *part_ids,
@@ -497,9 +507,13 @@ extern "C" int lance_hip_ivfrq_create(lance_hip_ctx *ctx, int metric, uint32_t d
 }
 
 static const CandNames RQ_NAMES = {"ivfrq", {"ivfrq_scan", "ivfrq_wide_scan"}, {"ivfrq_merge", "ivfrq_wide_merge"}, {"ivfrq_exact", "ivfrq_wide_exact"}};
+// the partition-major scan times its own two steps (ivfrq_pm_group, ivfrq_pm_scan): no scan timer around them
+static const CandNames RQ_PM_NAMES = {"ivfrq", {nullptr, nullptr}, {"ivfrq_merge", "ivfrq_wide_merge"}, {"ivfrq_exact", "ivfrq_wide_exact"}};
 
 // refine_factor == 0: the k best by the RQ estimate.  Otherwise (lance_hip_ivfrq_search_refine, which has checked the arguments) the
-// keff = k * refine_factor best are candidates [nq][keff] in the scratch arena, re-scored against the raw vectors (cand_search, pair_cand.cuh)
+// keff = k * refine_factor best are candidates [nq][keff] in the scratch arena, re-scored against the raw vectors (cand_search, pair_cand.cuh).
+// Large unfiltered batches at the narrow capacity take the partition-major scan (rq_pm.cuh: plan_ivfrq_grouped); the stages behind the scan
+// do not know which one filled the lists.
 static int ivfrq_search_impl(lance_hip_ctx *ctx, const lance_hip_index *idx, const float *q, uint32_t nq, uint32_t k, uint32_t nprobes,
                              const uint32_t *allow, uint64_t *ids, float *dists, uint32_t refine_factor = 0) {
   const bool refine = refine_factor != 0;
@@ -520,16 +534,26 @@ static int ivfrq_search_impl(lance_hip_ctx *ctx, const lance_hip_index *idx, con
   a.w.cap = rq_scan_cap(d, (int)keff);
   LH_REQUIRE((size_t)4 * d <= (size_t)8 * a.w.cap, "ivfrq_search: the rotated query of d=%u does not fit the %d-entry candidate buffer it borrows", d, a.w.cap);
   auto chunk = [&](const CandLists &w, uint32_t q0) { a.w = w; a.pdists = pd + (size_t)q0 * nprobes; a.q = q + (size_t)q0 * d; };
+  const bool grouped = rqpm_forced_g() < 0 ? plan_ivfrq_grouped(nq, nprobes, idx->rq_nlist, keff, d, allow != nullptr, rqpm_switched_off())
+                                           : plan_ivfrq_grouped(nq, nprobes, idx->rq_nlist, keff, d, allow != nullptr, rqpm_switched_off(), (uint32_t)rqpm_forced_g());
+  RqPmScratch pm;
+  if (grouped) LH_TRY(rqpm_scratch(ctx, (size_t)std::min<uint64_t>(nq, cand_queries_per_launch(nq, nprobes, keff)) * nprobes, idx->rq_nlist, &pm));
   return cand_search(
-      ctx, idx, RQ_NAMES, a.w, probes, nq, k, refine, q, ids, dists,
+      ctx, idx, grouped ? RQ_PM_NAMES : RQ_NAMES, a.w, probes, nq, k, refine, q, ids, dists,
       [&](const CandLists &w, uint32_t q0, uint32_t nqc) {
         chunk(w, q0);
+        if (grouped) return rqpm_scan(ctx, a, nqc, idx->rq_nlist, pm);
         hipLaunchKernelGGL(rq_scan_kernel, dim3(nqc * nprobes), dim3(256), rq_scan_lds(d, w.cap), ctx->stream, a);
+        return (int)LANCE_HIP_OK;
       },
       [&](const CandLists &w, uint32_t q0, uint32_t nqc, uint64_t *oid, float *od) {
         chunk(w, q0);
         hipLaunchKernelGGL(rq_exact_kernel, dim3(nqc), dim3(64), rq_replay_lds(d, w.k), ctx->stream, a, oid, od);
       });
+}
+
+extern "C" int lance_hip_ivfrq_plan(uint32_t nq, uint32_t nprobes, uint32_t nlist, uint32_t keff, uint32_t d, int filtered, int grouped_off) {
+  return plan_ivfrq_grouped(nq, nprobes, nlist, keff, d, filtered != 0, grouped_off != 0) ? 1 : 0;
 }
 
 static int ivfrq_check(lance_hip_ctx *ctx, const lance_hip_index *idx, const void *q, uint32_t nq, const uint64_t *ids, const float *dists) {

@@ -41,6 +41,7 @@ constexpr int SQPM_KT = 64;        // bytes of a row staged per K step
 constexpr int SQPM_QK = 128;       // bytes of a query a lane keeps in registers for the whole item
 constexpr int SQPM_RS = SQPM_KT + 16;                             // LDS stride of a staged row
 static_assert(CAND_NARROW_K + SQPM_TILE <= SQPM_CAP, "the kept entries and one row tile fit a pair's buffer");
+static_assert(SQPM_QB == CAND_BLOCK_PAIRS && SQPM_CAP == CAND_BLOCK_CAP, "the block selection of pair_cand.cuh");
 static_assert(SQPM_TILE * (SQPM_KT / 16) == 512 && SQPM_QK == 2 * SQPM_KT, "staging: two row chunks per thread; resident queries span two K steps");
 
 // ---- the plan: which scan serves an IVF_SQ batch.  Decided once per call, before anything is enqueued. ---------------------------------------
@@ -61,12 +62,6 @@ static inline size_t sqpm_lds_bytes() {
 typedef int sqpm_i32x4 __attribute__((ext_vector_type(4)));
 typedef int sqpm_i32x16 __attribute__((ext_vector_type(16)));
 
-__device__ __forceinline__ void sqpm_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 __device__ __forceinline__ uint32_t sqpm_sum16(uint4 v, uint32_t acc) {
   acc = sq_udot4(v.x, 0x01010101u, acc); acc = sq_udot4(v.y, 0x01010101u, acc);
   acc = sq_udot4(v.z, 0x01010101u, acc); return sq_udot4(v.w, 0x01010101u, acc);
@@ -74,41 +69,9 @@ __device__ __forceinline__ uint32_t sqpm_sum16(uint4 v, uint32_t acc) {
 __device__ __forceinline__ sqpm_i32x4 sqpm_vec(uint4 v) { return sqpm_i32x4{(int)v.x, (int)v.y, (int)v.z, (int)v.w}; }
 __device__ __forceinline__ uint4 sqpm_flip(uint4 v) { return make_uint4(v.x ^ 0x80808080u, v.y ^ 0x80808080u, v.z ^ 0x80808080u, v.w ^ 0x80808080u); }
 
-struct SqPmCtl {                   // one word per pair of the block
-  int cnt[SQPM_QB];
-  uint32_t thr[SQPM_QB], amb_key[SQPM_QB];
-  int amb[SQPM_QB];
+struct SqPmCtl : CandBlockCtl {    // pair_cand.cuh's selection words, and per pair of the block:
   uint32_t qq[SQPM_QB], qsum[SQPM_QB];
-  int pair[SQPM_QB];               // index into the lists (qi * nprobes + j), -1 behind the block's last pair
 };
-
-// cand_sort_truncate for pair p by ONE wave: sort its buffer, keep the k best, remember a tie cut at the k-th key
-__device__ __forceinline__ void sqpm_sort_truncate(uint64_t *e, SqPmCtl *ctl, int p, int k, int lane) {
-  const int cnt = ctl->cnt[p];
-  int P = 2;
-  while (P < cnt) P <<= 1;
-  for (int i = cnt + lane; i < P; i += 64) e[i] = ~0ull;
-  sqpm_wave_sync();
-  for (int k2 = 2; k2 <= P; k2 <<= 1) {
-    for (int j = k2 >> 1; j > 0; j >>= 1) {
-      for (int i = lane; i < P / 2; i += 64) {
-        const int ix = 2 * j * (i / j) + (i % j);
-        const int px = ix + j;
-        const bool up = (ix & k2) == 0;
-        const uint64_t a = e[ix], b = e[px];
-        if ((a > b) == up) { e[ix] = b; e[px] = a; }
-      }
-      sqpm_wave_sync();
-    }
-  }
-  if (lane == 0 && cnt > k) {
-    const uint32_t kth = (uint32_t)(e[k - 1] >> 32);
-    if ((uint32_t)(e[k] >> 32) == kth) { ctl->amb[p] = 1; ctl->amb_key[p] = kth; }
-    ctl->thr[p] = kth;
-    ctl->cnt[p] = k;
-  }
-  sqpm_wave_sync();
-}
 
 // grid: one workgroup per work item; desc[item] = {partition, first grouped pair, pairs (1..32), 0}, partition -1 = no item.
 // Dynamic LDS: sqpm_lds_bytes().
@@ -229,25 +192,11 @@ __global__ __launch_bounds__(256) void ivfsq_pm_scan_kernel(SqArgs a, const uint
     // before a tile at most SQPM_CAP - SQPM_TILE entries are held (k <= 128 after a cut), so its 128 rows always fit
     for (int u = 0; u < SQPM_QB / 4; ++u) {
       const int p = wave * (SQPM_QB / 4) + u;
-      if (ctl->cnt[p] > SQPM_CAP - SQPM_TILE) sqpm_sort_truncate(ebuf + p * SQPM_CAP, ctl, p, k, lane);
+      if (ctl->cnt[p] > SQPM_CAP - SQPM_TILE) cand_block_sort_truncate(ebuf + p * SQPM_CAP, ctl, p, k, lane);
     }
     __syncthreads();
   }
-  for (int u = 0; u < SQPM_QB / 4; ++u) {
-    const int p = wave * (SQPM_QB / 4) + u, pair = ctl->pair[p];
-    if (pair < 0) continue;
-    uint64_t *e = ebuf + p * SQPM_CAP;
-    if (ctl->cnt[p] > 0) sqpm_sort_truncate(e, ctl, p, k, lane);
-    const int got = min(ctl->cnt[p], k);
-    for (int i = lane; i < got; i += 64) {
-      a.w.pkey[(int64_t)pair * k + i] = (uint32_t)(e[i] >> 32);
-      a.w.ppos[(int64_t)pair * k + i] = (uint32_t)e[i];
-    }
-    if (lane == 0) {
-      a.w.pcnt[pair] = (uint32_t)got;
-      a.w.pamb[pair] = (got == k && ctl->amb[p] && ctl->amb_key[p] == (uint32_t)(e[k - 1] >> 32)) ? 1u : 0u;
-    }
-  }
+  cand_block_write(a.w, ebuf, ctl, k, wave, lane);
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------------
