@@ -731,6 +731,26 @@ int lance_hip_timing_query(lance_hip_ctx *ctx, const char *kernel, double *ms_to
  * v_mfma_f32_32x32x16_f16 / _bf16 issue rate in flop per second (round 6: the MFMA roofline's measured peak).          */
 int lance_hip_ubench(lance_hip_ctx *ctx, int what, double *result);
 
+/* ---- diagnostic hooks (tests/test_zz_gpu_grouping.py): the grouping every build and every grouped search shares -- */
+/* The stable group-by of row numbers by a small integer key (csrc/group.hip), as the index builds, the pair tables of the grouped
+ * scans, the index updates and the k-means M-step call it.  `batches` independent problems: problem b reads the n keys at
+ * keys + b * key_stride, and where active is not NULL and active[b] == 0 it is skipped and none of its outputs is written.  A row
+ * whose key is >= k (LANCE_HIP_NONE among them) is dropped.  Written per problem: starts[b][0 .. k] = the exclusive running sum of
+ * the number of rows per key (starts[b][k] = the number of rows kept), and rows[b * out_stride + i] for i < starts[b][k] = the row
+ * numbers grouped by key, ascending inside a key.  rows[b * out_stride + i] for starts[b][k] <= i < n is unspecified; nothing at
+ * i >= n is written.  Limits: 1 <= k <= 4194304; k > 16384 only with batches == 1 and active == NULL; n < 2^32; with several
+ * problems both strides >= n.  batches == 0 writes nothing.  Device pointers; the call returns after the stream has drained.   */
+int lance_hip_stable_group(lance_hip_ctx *ctx, const uint32_t *keys, uint64_t n, uint64_t key_stride, uint32_t k, uint32_t batches,
+                           uint32_t *starts /*[batches][k+1]*/, uint32_t *rows /*[batches][out_stride]*/, uint64_t out_stride,
+                           const uint8_t *active /*[batches] or NULL*/);
+/* The work items of a grouped scan (csrc/search_q.hip): the pairs of partition vp are pair_starts[vp] .. pair_starts[vp + 1]
+ * (non-decreasing), and every partition is cut into blocks of at most G pairs.  item_start[0 .. nvp] = the exclusive running sum of
+ * ceil(pairs of vp / G); desc[item] = {vp, pair_starts[vp] + G * g, min(G, pairs left), 0} for the g-th block of vp, items in
+ * partition order, and {-1, 0, 0, 0} for every item from item_start[nvp] up to max_items.  A max_items below item_start[nvp] cuts
+ * the list short.  G >= 1; desc 16-byte aligned.  Device pointers; the call returns after the stream has drained.               */
+int lance_hip_work_items(lance_hip_ctx *ctx, const uint32_t *pair_starts /*[nvp+1]*/, uint32_t nvp, uint32_t G,
+                         uint32_t *item_start /*[nvp+1]*/, int32_t *desc /*[max_items][4]*/, uint32_t max_items);
+
 #ifdef __cplusplus
 }
 #endif

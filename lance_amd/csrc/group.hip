@@ -308,3 +308,22 @@ int stable_group(lance_hip_ctx *ctx, const uint32_t *ids, int64_t n, int64_t id_
 }
 
 }  // namespace lh
+
+using namespace lh;
+
+// Diagnostic entry point (include/lance_hip.h): stable_group as the builds and the grouped searches call it, nothing added but the
+// checks the internal function leaves to its callers (pointers, and sizes that fit its signed parameters).
+extern "C" int lance_hip_stable_group(lance_hip_ctx *ctx, const uint32_t *keys, uint64_t n, uint64_t key_stride, uint32_t k, uint32_t batches,
+                                      uint32_t *starts, uint32_t *rows, uint64_t out_stride, const uint8_t *active) {
+  lh::CtxLock _ctx_lock(ctx);
+  LH_REQUIRE(ctx, "stable_group: NULL context");
+  LH_REQUIRE(batches == 0 || (starts && (n == 0 || (keys && rows))), "stable_group: NULL argument");
+  LH_REQUIRE(k <= (uint32_t)INT32_MAX && batches <= (uint32_t)INT32_MAX, "stable_group: k=%u, batches=%u not supported", k, batches);
+  LH_REQUIRE(n <= (uint64_t)INT64_MAX && key_stride <= (uint64_t)INT64_MAX && out_stride <= (uint64_t)INT64_MAX,
+             "stable_group: n or a stride does not fit 63 bits");
+  LH_REQUIRE(batches <= 1 || (key_stride >= n && out_stride >= n), "stable_group: strides below n with %u batches", batches);
+  LH_CHECK_HIP(hipSetDevice(ctx->device));
+  LH_TRY(stable_group(ctx, keys, (int64_t)n, (int64_t)key_stride, (int)k, (int)batches, starts, rows, (int64_t)out_stride, active));
+  LH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  return LANCE_HIP_OK;
+}

@@ -1278,7 +1278,8 @@ int qscan_index_constants(lance_hip_ctx *ctx, lance_hip_index *ix) {
 // item_start[vp] = exclusive scan of ceil(pairs of vp / G), desc[item] = {virtual partition, first grouped pair, pairs (1..G), 0}
 int qscan_items(lance_hip_ctx *ctx, const uint32_t *pair_starts, int nvp, int G, uint32_t *item_start, int4 *desc, uint32_t max_items) {
   hipLaunchKernelGGL(q_item_table_kernel, dim3(1), dim3(256), 0, ctx->stream, pair_starts, nvp, G, item_start);
-  hipLaunchKernelGGL(q_item_desc_kernel, dim3((unsigned)cdiv(max_items, 256)), dim3(256), 0, ctx->stream, item_start, pair_starts, nvp, G, max_items, desc);
+  if (max_items)      // (an empty grid is a launch error; the searches always pass pairs / G + nvp + 1)
+    hipLaunchKernelGGL(q_item_desc_kernel, dim3((unsigned)cdiv(max_items, 256)), dim3(256), 0, ctx->stream, item_start, pair_starts, nvp, G, max_items, desc);
   LH_CHECK_HIP(hipGetLastError());
   return LANCE_HIP_OK;
 }
@@ -1412,3 +1413,19 @@ int qmerge_launch(lance_hip_ctx *ctx, const lance_hip_index *ix, const float *qs
 }
 
 }  // namespace lh
+
+using namespace lh;
+
+// Diagnostic entry point (include/lance_hip.h): qscan_items as the four grouped scans call it, nothing added but the checks the internal
+// function leaves to its callers.
+extern "C" int lance_hip_work_items(lance_hip_ctx *ctx, const uint32_t *pair_starts, uint32_t nvp, uint32_t G, uint32_t *item_start, int32_t *desc,
+                                    uint32_t max_items) {
+  lh::CtxLock _ctx_lock(ctx);
+  LH_REQUIRE(ctx && pair_starts && item_start && (desc || max_items == 0), "work_items: NULL argument");
+  LH_REQUIRE(nvp <= (uint32_t)INT32_MAX && G >= 1 && G <= (uint32_t)INT32_MAX, "work_items: nvp=%u, G=%u not supported", nvp, G);
+  LH_REQUIRE((reinterpret_cast<uintptr_t>(desc) & 15) == 0, "work_items: desc must be 16-byte aligned");
+  LH_CHECK_HIP(hipSetDevice(ctx->device));
+  LH_TRY(qscan_items(ctx, pair_starts, (int)nvp, (int)G, item_start, reinterpret_cast<int4 *>(desc), max_items));
+  LH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  return LANCE_HIP_OK;
+}

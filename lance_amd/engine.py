@@ -735,6 +735,49 @@ class Engine:
                                                _ptr(db), 0 if b is None else b.shape[1], *rng, k, _ptr(ids), _ptr(dists)))
         return ids, dists
 
+    @staticmethod
+    def _u32_buffer(t, name, need):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.dtype == torch.int32):
+            raise ValueError(f"{name} must be a contiguous int32 cuda tensor (the uint32 bits)")
+        if t.numel() < need:
+            raise ValueError(f"{name} holds {t.numel()} entries, the call touches {need}")
+
+    def stable_group(self, keys, n, k, starts, rows, batches=1, key_stride=None, out_stride=None, active=None):
+        """The library's stable group-by (lance_hip_stable_group), on the caller's tensors and in place: keys, starts and rows are
+        int32 cuda tensors holding uint32 bits, active a uint8 cuda tensor or None.  Problem b reads keys[b * key_stride : ... + n]
+        and writes starts[b * (k + 1) : ... + k + 1] and rows[b * out_stride : ... + starts[b][k]]; the strides default to n.
+        Every tensor must be as long as what the call touches (checked here, before the device call).  -> None"""
+        n, k, batches = int(n), int(k), int(batches)
+        key_stride = n if key_stride is None else int(key_stride)
+        out_stride = n if out_stride is None else int(out_stride)
+        if min(n, k, batches, key_stride, out_stride) < 0:
+            raise ValueError("stable_group: negative size")
+        last = max(batches - 1, 0)
+        self._u32_buffer(keys, "keys", last * key_stride + n if batches else 0)
+        self._u32_buffer(starts, "starts", batches * (k + 1))
+        self._u32_buffer(rows, "rows", last * out_stride + n if batches else 0)
+        if active is not None:
+            if not (isinstance(active, torch.Tensor) and active.is_cuda and active.is_contiguous() and active.dtype == torch.uint8):
+                raise ValueError("active must be a contiguous uint8 cuda tensor")
+            if active.numel() < batches:
+                raise ValueError(f"active holds {active.numel()} entries for {batches} problems")
+        torch.cuda.synchronize()
+        check(self.lib.lance_hip_stable_group(self.h, _ptr(keys), n, key_stride, k, batches, _ptr(starts), _ptr(rows), out_stride,
+                                              _ptr(active)))
+
+    def work_items(self, pair_starts, G, item_start, desc, max_items):
+        """The work items of a grouped scan (lance_hip_work_items), on the caller's tensors and in place: pair_starts [nvp + 1] and
+        item_start [>= nvp + 1] int32 cuda tensors holding uint32 bits, desc an int32 cuda tensor of at least max_items * 4 entries.
+        -> None"""
+        nvp, G, max_items = int(pair_starts.numel()) - 1, int(G), int(max_items)
+        if nvp < 0 or G < 0 or max_items < 0:
+            raise ValueError("work_items: pair_starts is empty, or a negative size")
+        self._u32_buffer(pair_starts, "pair_starts", nvp + 1)
+        self._u32_buffer(item_start, "item_start", nvp + 1)
+        self._u32_buffer(desc, "desc", max_items * 4)
+        torch.cuda.synchronize()
+        check(self.lib.lance_hip_work_items(self.h, _ptr(pair_starts), nvp, G, _ptr(item_start), _ptr(desc), max_items))
+
     def ubench(self, what):
         """in-process ceilings for bench.py (lance_hip_ubench): "lds4" / "lds8" / "lds16" lane-gathers per second,
         "copy" bytes per second, "valu" / "valu_pk" f32 wave-instructions per second"""
