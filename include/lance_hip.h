@@ -601,6 +601,13 @@ int lance_hip_ivfsq_plan(uint32_t nq, uint32_t nprobes, uint32_t nlist, uint32_t
  * one workgroup's LDS, and nq * nprobes >= 128 * nlist, unless LANCE_HIP_NO_RQ_GROUPED is set: pass it as grouped_off), 0 = one
  * workgroup per (query, probed partition).  The answer does not depend on it.  A pure function: no context, no device.          */
 int lance_hip_ivfrq_plan(uint32_t nq, uint32_t nprobes, uint32_t nlist, uint32_t keff, uint32_t d, int filtered, int grouped_off);
+/* The same for an IVF_FLAT search of d-dimensional rows (dtype: the column's LANCE_HIP_F32 / F16 / I8, metric: the index's): 1 = the main
+ * pass runs partition-major on the bf16 matrix cores -- an f32 column whose shape the fixed-dimension partition-major kernel does not
+ * serve (cosine, or a dimension other than 8, 16, 32, 64, 96, 128), d a multiple of 4 up to 4096, no distance range (pass it as has_range),
+ * and nq * nprobes >= 16 * nlist, unless LANCE_HIP_NO_FLAT_MC is set: pass it as switched_off --, 0 = the route the search had before.
+ * The search itself also asks for k <= 128, 16-byte aligned queries and a non-empty index.  The answer does not depend on it.  A pure
+ * function: no context, no device.                                                                                              */
+int lance_hip_ivfflat_plan(uint32_t nq, uint32_t nprobes, uint32_t nlist, uint32_t d, int dtype, int metric, int has_range, int switched_off);
 
 /* ---- N5: 8-bit scalar quantisation and IVF_SQ (lance-index/src/vector/sq.rs, sq/storage.rs, sq/builder.rs) ------------ */
 /* Columns are LANCE_HIP_F32 or LANCE_HIP_F16 (an int8 column is refused: the reference's SQ builder takes float arrays only; f64

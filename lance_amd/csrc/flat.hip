@@ -636,18 +636,7 @@ __device__ __forceinline__ uint32_t kth_smallest_256(uint32_t v, int kk, uint32_
   return *slot;
 }
 
-// distance of one stored row as FlatDistanceCal sees it (flat/storage.rs:345-402: distance_type.func()(query, vector)).  Cosine:
-// f32::cosine = norm_l2(query) once, then cosine_fast per row (cosine.rs:36-39,143-175) -- the rows of a cosine IVF_FLAT index
-// are stored normalised (IvfTransformer::new_flat, ivf.rs:147-160) and the query arrives normalised (knn.rs:498), but the
-// distance function is still the full cosine.
-// H32: the rows are widened f16 values -- FlatDistanceCal over a Float16 column calls f16's dot / cosine (32-lane dot_scalar and
-// norm_l2_impl, the scalar cosine; dot.rs:91-102, norm_l2.rs:60-85, cosine.rs:171-179); L2 stays the 16-lane l2_scalar.
-template <int METRIC, bool H32 = false>
-__device__ __forceinline__ float ivfflat_dist_rt(const float *__restrict__ q, float qnorm, const float *__restrict__ row, int d) {
-  if constexpr (METRIC == METRIC_COSINE) return H32 ? cosine_scalar32_rt(q, qnorm, row, d) : cosine_exact_rt(q, qnorm, row, d);
-  else return finish_metric<METRIC>(dist_exact_rt<METRIC, float, (H32 && METRIC == METRIC_DOT) ? 32 : 16, METRIC == METRIC_L2>(q, row, d));      // (L2: row - q, exact.cuh SWAP)
-}
-
+// (ivfflat_dist_rt, the distance of one stored row as FlatDistanceCal sees it: search_common.cuh -- flat_ivf_mc.hip evaluates with it too)
 template <int D, int METRIC, bool H32 = false, bool RANGE = false>   // D = 0: run-time dimension (H32 only there)
 __global__ __launch_bounds__(256) void ivfflat_kernel(IvfFlatArgs a) {
   static_assert(!H32 || D == 0, "the f16 orders run on the run-time-dimension kernel");
@@ -1077,6 +1066,37 @@ __global__ __launch_bounds__(256) void ivfflat_flag_all_kernel(int nq, uint32_t 
   if (q < nq) flags[q] = 1u;
 }
 
+// The main pass of an un-ranged f32 search that ivfflat_pm_kernel does not serve (a dimension outside the fixed set, or cosine) runs
+// partition-major on the bf16 matrix cores (flat_ivf_mc.hip) once the batch brings IVFFLAT_MC_MIN_PAIRS_PER_LIST pairs per partition on
+// average (a matrix tile is 32 queries wide; half-empty tiles still won, nothing smaller was measured).  d % 4 == 0 and d <= 4096: the range the filter's
+// margin was derived in.  A pure function of the call's shape; ivfflat_search_impl adds what only it can see (the pointers' alignment,
+// k below the big_k path, an index with rows).  DESIGN.md 4f.1.
+constexpr uint32_t IVFFLAT_MC_MIN_PAIRS_PER_LIST = 16;      // the smallest point of the sweep (16, 32, 64), and the route won there: DESIGN.md 4f.1
+static bool plan_ivfflat_mc(uint32_t nq, uint32_t nprobes, uint32_t nlist, uint32_t d, int dtype, int metric, bool has_range, bool switched_off,
+                            uint32_t g = IVFFLAT_MC_MIN_PAIRS_PER_LIST) {
+  if (switched_off || has_range || dtype != LANCE_HIP_F32) return false;
+  if (metric != LANCE_HIP_L2 && metric != LANCE_HIP_DOT && metric != LANCE_HIP_COSINE) return false;
+  if (metric != LANCE_HIP_COSINE && flat_fixed_dim(d)) return false;      // ivfflat_pm_kernel's shapes stay where they are
+  if (d == 0 || d % 4 != 0 || d > 4096) return false;
+  return (uint64_t)nq * nprobes >= (uint64_t)g * nlist;
+}
+
+// LANCE_HIP_FLAT_MC_G=<g>, read once per process: the route from g pairs per partition on (the sweep that chose the default)
+static uint32_t ivfflat_mc_g() {
+  static const int g = getenv("LANCE_HIP_FLAT_MC_G") ? std::max(0, atoi(getenv("LANCE_HIP_FLAT_MC_G"))) : (int)IVFFLAT_MC_MIN_PAIRS_PER_LIST;
+  return (uint32_t)g;
+}
+
+// LANCE_HIP_NO_FLAT_MC, read once per process: every batch takes the route it had before flat_ivf_mc.hip (A/B runs)
+static bool ivfflat_mc_switched_off() {
+  static const bool off = getenv("LANCE_HIP_NO_FLAT_MC") != nullptr;
+  return off;
+}
+
+extern "C" int lance_hip_ivfflat_plan(uint32_t nq, uint32_t nprobes, uint32_t nlist, uint32_t d, int dtype, int metric, int has_range, int switched_off) {
+  return plan_ivfflat_mc(nq, nprobes, nlist, d, dtype, metric, has_range != 0, switched_off != 0) ? 1 : 0;
+}
+
 static int ivfflat_search_impl(lance_hip_ctx *ctx, const lance_hip_index *idx, const void *q, uint32_t nq, uint32_t k, uint32_t nprobes,
                                const uint32_t *allow, bool has_range, float lower, float upper, uint64_t *ids, float *dists) {
   LH_REQUIRE(ctx && idx && (nq == 0 || (q && ids && dists)), "ivfflat_search: NULL argument");
@@ -1136,16 +1156,21 @@ static int ivfflat_search_impl(lance_hip_ctx *ctx, const lance_hip_index *idx, c
   const size_t sel_lds = (size_t)IVFFLAT_CAP * 16;
   const size_t ex_lds = (size_t)(((d + 3) & ~3) + 2) * 4 + (size_t)k * 12 + (size_t)(k + 1) * 8 + 64 * 4 + 64;
   LH_REQUIRE(ex_lds <= 160 * 1024, "ivfflat_search: k=%u with %d-dimensional vectors does not fit the exact kernel's LDS", k, d);
+  const bool pm = fixed && idx->n_flat_items > 0 &&     // partition-major for the fixed dimensions, query-major kernel otherwise
+                  ((reinterpret_cast<uintptr_t>(qf) & 15) == 0);
+  // ... and for the other f32 shapes, batch permitting, on the matrix cores (main pass only: the bound pass visits one partition per query)
+  const bool mc = !pm && !big_k && idx->n_flat_items > 0 && ((reinterpret_cast<uintptr_t>(qf) | reinterpret_cast<uintptr_t>(idx->vectors)) & 15) == 0 &&
+                  plan_ivfflat_mc(nq, nprobes, idx->nlist, idx->d, idx->dtype, idx->metric, has_range, ivfflat_mc_switched_off(), ivfflat_mc_g());
+  IvfFlatMcArgs m{};
   auto finish = [&](int nqc, uint64_t *oid, float *od, bool select = true) {
     if (select) hipLaunchKernelGGL(ivfflat_select_kernel, dim3(nqc), dim3(256), sel_lds, ctx->stream, a, oid, od);
+    if (select && mc) launch_ivfflat_mc_flags(ctx, m, nqc, a.flags);      // a queue that overflowed: the exact kernel answers the query
     ScopedTimer t(ctx, "ivfflat_exact");
     if (has_range) launch_ivfflat_exact<true>(ctx, a, idx->metric, h32, nqc, ex_lds, oid, od);
     else launch_ivfflat_exact<false>(ctx, a, idx->metric, h32, nqc, ex_lds, oid, od);
   };
-  const bool pm = fixed && idx->n_flat_items > 0 &&     // partition-major for the fixed dimensions, query-major kernel otherwise
-                  ((reinterpret_cast<uintptr_t>(qf) & 15) == 0);
   uint32_t *pair_starts = nullptr, *pair_idx = nullptr;
-  if (pm) {
+  if (pm || mc) {
     pair_starts = ctx->scratch_t<uint32_t>("ivfflat.pair_starts", (size_t)idx->nlist + 1);
     pair_idx = ctx->scratch_t<uint32_t>("ivfflat.pair_idx", (size_t)qch * nprobes);
     if (!pair_starts || !pair_idx) return LANCE_HIP_ENOMEM;
@@ -1159,6 +1184,12 @@ static int ivfflat_search_impl(lance_hip_ctx *ctx, const lance_hip_index *idx, c
     if (!pair_starts0 || !pair_idx0 || !keys0 || !lanemin) return LANCE_HIP_ENOMEM;
   }
   a.items = idx->flat_items; a.pair_starts = pair_starts; a.pair_idx = pair_idx; a.pdiv = (int)nprobes; a.lanemin = lanemin;
+  if (mc) {
+    LH_TRY(ivfflat_mc_scratch(ctx, qch, d, &m));
+    m.vec = idx->vectors; m.row_ids = idx->row_ids; m.part_offsets = idx->part_offsets; m.nlist = (int)idx->nlist;
+    m.items = reinterpret_cast<const int *>(idx->flat_items); m.pair_starts = pair_starts; m.pair_idx = pair_idx;
+    m.nprobes = (int)nprobes; m.d = d; m.allow = allow; m.ppart = a.ppart;
+  }
   bool grouped = false;
   auto scan = [&](int bound, int nqc) {
     a.bound = bound;
@@ -1184,6 +1215,17 @@ static int ivfflat_search_impl(lance_hip_ctx *ctx, const lance_hip_index *idx, c
       }
       if (idx->metric == LANCE_HIP_DOT) launch_ivfflat_pm<METRIC_DOT, false>(ctx, a, idx->n_flat_items);
       else launch_ivfflat_pm<METRIC_L2, false>(ctx, a, idx->n_flat_items);
+      return;
+    }
+    if (!bound && mc) {
+      m.q = a.q; m.pool = pl;
+      if (!grouped) {      // once per chunk: the pairs by partition, the queries' bf16 plane and norms
+        (void)stable_group(ctx, a.probes, (int64_t)nqc * nprobes, (int64_t)nqc * nprobes, (int)idx->nlist, 1, pair_starts, pair_idx,
+                           (int64_t)nqc * nprobes, nullptr);
+        ivfflat_mc_prepare_queries(ctx, m, nqc, cosine);
+        grouped = true;
+      }
+      (void)launch_ivfflat_mc(ctx, m, idx->metric, idx->n_flat_items, nqc);
       return;
     }
     if (idx->metric == LANCE_HIP_DOT) launch_ivfflat<METRIC_DOT>(ctx, a, grid, fixed, h32);

@@ -137,6 +137,32 @@ int flat_mfma_wide_prepare_queries(lance_hip_ctx *ctx, const float *q, int nq, i
 int launch_flat_filter_mfma_wide(lance_hip_ctx *ctx, const FlatPool &e, int d, int metric, const uint16_t *xb, const float *xn2, const uint16_t *qb,
                                  const float *qn2);
 
+// IVF_FLAT batched search: partition-major main pass on the bf16 matrix cores, any d % 4 == 0 up to 4096, L2 / dot / cosine (flat_ivf_mc.hip).
+// The gate is flat.hip's plan_ivfflat_mc; the pool, the thresholds and the grouped pairs are ivfflat_search_impl's.
+struct IvfFlatMcArgs {
+  const float *vec;              // [n][d] partition-ordered rows of the index
+  const uint64_t *row_ids;       // [n]
+  const uint32_t *part_offsets;  // [nlist+1]
+  int nlist;
+  const int *items;              // the index's flat_items: (partition, first row) per 256-row block -- two workgroups each
+  const uint32_t *pair_starts;   // [nlist+1] (query, probe) pairs grouped by partition
+  const uint32_t *pair_idx;      // [nq*nprobes] pair index (query = idx / nprobes), grouped
+  const float *q;                // [nq][d] queries of this chunk (cosine: the normalised key)
+  int nprobes, d, dp;            // dp = d rounded up to the filter's stage
+  const uint32_t *allow;         // prefilter bits by storage position, or NULL
+  uint16_t *qb;                  // [nq][dp] bf16 plane of the chunk's queries, zero padded
+  float *qn;                     // [nq] |q|^2 (cosine: |q|)
+  uint32_t *scnt;                // [nq] queued rows
+  uint32_t *squeue;              // [nq][FLAT_MC_QUEUE_CAP] row numbers whose surrogate distance passed
+  uint32_t *qflag;               // [nq] 1 = the queue overflowed: the exact kernel answers the query
+  uint32_t *ppart;               // [nq][cap] partition of every pool entry
+  FlatPool pool;
+};
+int ivfflat_mc_scratch(lance_hip_ctx *ctx, int qch, int d, IvfFlatMcArgs *a);      // the ivfflat.mc.* slots and dp
+void ivfflat_mc_prepare_queries(lance_hip_ctx *ctx, const IvfFlatMcArgs &a, int nqc, bool cosine);
+int launch_ivfflat_mc(lance_hip_ctx *ctx, const IvfFlatMcArgs &a, int metric, unsigned n_items, int nqc);
+void launch_ivfflat_mc_flags(lance_hip_ctx *ctx, const IvfFlatMcArgs &a, int nqc, uint32_t *flags);
+
 int launch_assign(lance_hip_ctx *ctx, const PairwiseArgs &p, int d, int metric, int batches);
 bool assign_reads_native(PairwiseArgs p, int d, int batches);
 // residual + PQ encode in one kernel, rows read in the column's own element type (encode_fused.hip)

@@ -684,6 +684,12 @@ class Engine:
         check(self.lib.lance_hip_search_stats(self.h, C.byref(n)))
         return n.value
 
+    def ivfflat_plan(self, nq, nprobes, nlist, d, dtype="float32", metric="l2", has_range=False, switched_off=False):
+        """1 when an IVF_FLAT search of this shape runs its main pass partition-major on the matrix cores, 0 when it keeps the
+        route it had (lance_hip_ivfflat_plan: a pure function, no device)"""
+        return self.lib.lance_hip_ivfflat_plan(int(nq), int(nprobes), int(nlist), int(d), _DT[dtype][1], METRICS[metric],
+                                               int(bool(has_range)), int(bool(switched_off)))
+
     # ---- timing hooks --------------------------------------------------------------
     def timing(self, on=True):
         check(self.lib.lance_hip_timing_enable(self.h, int(on)))
