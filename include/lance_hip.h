@@ -605,8 +605,10 @@ int lance_hip_ivfrq_plan(uint32_t nq, uint32_t nprobes, uint32_t nlist, uint32_t
  * pass runs partition-major on the bf16 matrix cores -- an f32 column whose shape the fixed-dimension partition-major kernel does not
  * serve (cosine, or a dimension other than 8, 16, 32, 64, 96, 128), d a multiple of 4 up to 4096, no distance range (pass it as has_range),
  * and nq * nprobes >= 16 * nlist, unless LANCE_HIP_NO_FLAT_MC is set: pass it as switched_off --, 0 = the route the search had before.
- * The search itself also asks for k <= 128, 16-byte aligned queries and a non-empty index.  The answer does not depend on it.  A pure
- * function: no context, no device.                                                                                              */
+ * The search itself also asks for k <= 128, 16-byte aligned queries and a non-empty index.  A batch on that route runs its bound pass on
+ * the matrix cores too once nq >= 1.6 * nlist, unless LANCE_HIP_NO_FLAT_MC_BOUND is set (then, and below, the bound pass stays
+ * query-major); this function does not report that second choice.  The answer does not depend on either.  A pure function: no context,
+ * no device.                                                                                                                    */
 int lance_hip_ivfflat_plan(uint32_t nq, uint32_t nprobes, uint32_t nlist, uint32_t d, int dtype, int metric, int has_range, int switched_off);
 
 /* ---- N5: 8-bit scalar quantisation and IVF_SQ (lance-index/src/vector/sq.rs, sq/storage.rs, sq/builder.rs) ------------ */

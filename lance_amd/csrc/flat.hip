@@ -1093,6 +1093,20 @@ static bool ivfflat_mc_switched_off() {
   return off;
 }
 
+// The bound pass of a batch on the matrix-core route runs there too (ivfflat_mc_bound_kernel) once the batch brings this many queries per
+// partition: a bound tile's 128 query slots hold the queries whose NEAREST partition this is.  DESIGN.md 4f.1.
+constexpr double IVFFLAT_MC_BOUND_MIN_QUERIES_PER_LIST = 1.6;      // the smallest point of the sweep (1.6, 3.2, 6.4)
+// LANCE_HIP_FLAT_MC_BOUND_G=<g>, read once per process: the matrix-core bound pass from g queries per partition on (the sweep)
+static double ivfflat_mc_bound_g() {
+  static const double g = getenv("LANCE_HIP_FLAT_MC_BOUND_G") ? std::max(0.0, atof(getenv("LANCE_HIP_FLAT_MC_BOUND_G"))) : IVFFLAT_MC_BOUND_MIN_QUERIES_PER_LIST;
+  return g;
+}
+// LANCE_HIP_NO_FLAT_MC_BOUND, read once per process: the bound pass of every batch stays query-major (A/B runs)
+static bool ivfflat_mc_bound_switched_off() {
+  static const bool off = getenv("LANCE_HIP_NO_FLAT_MC_BOUND") != nullptr;
+  return off;
+}
+
 extern "C" int lance_hip_ivfflat_plan(uint32_t nq, uint32_t nprobes, uint32_t nlist, uint32_t d, int dtype, int metric, int has_range, int switched_off) {
   return plan_ivfflat_mc(nq, nprobes, nlist, d, dtype, metric, has_range != 0, switched_off != 0) ? 1 : 0;
 }
@@ -1158,9 +1172,11 @@ static int ivfflat_search_impl(lance_hip_ctx *ctx, const lance_hip_index *idx, c
   LH_REQUIRE(ex_lds <= 160 * 1024, "ivfflat_search: k=%u with %d-dimensional vectors does not fit the exact kernel's LDS", k, d);
   const bool pm = fixed && idx->n_flat_items > 0 &&     // partition-major for the fixed dimensions, query-major kernel otherwise
                   ((reinterpret_cast<uintptr_t>(qf) & 15) == 0);
-  // ... and for the other f32 shapes, batch permitting, on the matrix cores (main pass only: the bound pass visits one partition per query)
+  // ... and for the other f32 shapes, batch permitting, on the matrix cores
   const bool mc = !pm && !big_k && idx->n_flat_items > 0 && ((reinterpret_cast<uintptr_t>(qf) | reinterpret_cast<uintptr_t>(idx->vectors)) & 15) == 0 &&
                   plan_ivfflat_mc(nq, nprobes, idx->nlist, idx->d, idx->dtype, idx->metric, has_range, ivfflat_mc_switched_off(), ivfflat_mc_g());
+  // ... whose bound pass visits one partition per query: on the matrix cores from enough queries per partition on, query-major below
+  const bool mcb = mc && !ivfflat_mc_bound_switched_off() && (double)nq >= ivfflat_mc_bound_g() * (double)idx->nlist;
   IvfFlatMcArgs m{};
   auto finish = [&](int nqc, uint64_t *oid, float *od, bool select = true) {
     if (select) hipLaunchKernelGGL(ivfflat_select_kernel, dim3(nqc), dim3(256), sel_lds, ctx->stream, a, oid, od);
@@ -1176,7 +1192,7 @@ static int ivfflat_search_impl(lance_hip_ctx *ctx, const lance_hip_index *idx, c
     if (!pair_starts || !pair_idx) return LANCE_HIP_ENOMEM;
   }
   uint32_t *pair_starts0 = nullptr, *pair_idx0 = nullptr, *keys0 = nullptr, *lanemin = nullptr;
-  if (pm) {
+  if (pm || mcb) {      // the first-probe grouping of the partition-major bound passes (lanemin: pm's minima; ivfflat_first_probe_kernel fills it)
     pair_starts0 = ctx->scratch_t<uint32_t>("ivfflat.pair_starts0", (size_t)idx->nlist + 1);
     pair_idx0 = ctx->scratch_t<uint32_t>("ivfflat.pair_idx0", (size_t)qch);
     keys0 = ctx->scratch_t<uint32_t>("ivfflat.keys0", (size_t)qch);
@@ -1195,11 +1211,18 @@ static int ivfflat_search_impl(lance_hip_ctx *ctx, const lance_hip_index *idx, c
     a.bound = bound;
     const unsigned grid = (unsigned)(bound ? nqc : nqc * (int)nprobes);
     ScopedTimer t(ctx, bound ? "ivfflat_bound" : "ivfflat_scan");
-    if (bound && pm) {
-      // bound pass, partition-major: group the queries by their nearest partition, fold every row of that partition
-      // into 256 per-query lane minima, take the k-th smallest
+    if (bound && (pm || mcb)) {
+      // bound pass, partition-major: group the queries by their nearest partition, ...
       hipLaunchKernelGGL(ivfflat_first_probe_kernel, dim3(cdiv(nqc, 256)), dim3(256), 0, ctx->stream, a.probes, nqc, (int)nprobes, keys0, lanemin);
       (void)stable_group(ctx, keys0, (int64_t)nqc, (int64_t)nqc, (int)idx->nlist, 1, pair_starts0, pair_idx0, (int64_t)nqc, nullptr);
+      if (mcb) {
+        // ... matrix cores: the k rows of lowest bf16 surrogate among 256 per-query class minima, scored exactly; the largest is the bound
+        IvfFlatMcArgs b = m;
+        b.pair_starts = pair_starts0; b.pair_idx = pair_idx0;
+        (void)launch_ivfflat_mc_bound(ctx, b, idx->metric, idx->n_flat_items, nqc);
+        return;
+      }
+      // ... fixed dimensions: fold every row of that partition into 256 per-query lane minima, take the k-th smallest
       IvfFlatArgs b = a;
       b.pair_starts = pair_starts0; b.pair_idx = pair_idx0; b.pdiv = 1;
       if (idx->metric == LANCE_HIP_DOT) launch_ivfflat_pm<METRIC_DOT, true>(ctx, b, idx->n_flat_items);
@@ -1218,11 +1241,9 @@ static int ivfflat_search_impl(lance_hip_ctx *ctx, const lance_hip_index *idx, c
       return;
     }
     if (!bound && mc) {
-      m.q = a.q; m.pool = pl;
-      if (!grouped) {      // once per chunk: the pairs by partition, the queries' bf16 plane and norms
+      if (!grouped) {      // once per chunk: the pairs by partition
         (void)stable_group(ctx, a.probes, (int64_t)nqc * nprobes, (int64_t)nqc * nprobes, (int)idx->nlist, 1, pair_starts, pair_idx,
                            (int64_t)nqc * nprobes, nullptr);
-        ivfflat_mc_prepare_queries(ctx, m, nqc, cosine);
         grouped = true;
       }
       (void)launch_ivfflat_mc(ctx, m, idx->metric, idx->n_flat_items, nqc);
@@ -1245,6 +1266,10 @@ static int ivfflat_search_impl(lance_hip_ctx *ctx, const lance_hip_index *idx, c
       hipLaunchKernelGGL(ivfflat_flag_all_kernel, dim3(cdiv(nqc, 256)), dim3(256), 0, ctx->stream, nqc, a.flags);
       finish(nqc, oid, od, false);
       continue;
+    }
+    if (mc) {      // once per chunk, ahead of both passes: the queries' bf16 plane and norms
+      m.q = a.q; m.probes = a.probes; m.pool = pl;
+      ivfflat_mc_prepare_queries(ctx, m, nqc, cosine);
     }
     scan(1, nqc);
     scan(0, nqc);

@@ -25,7 +25,13 @@
 // what they saw.  A queue that overflowed loses rows: the query is flagged (IvfFlatMcArgs::qflag, OR-ed into the replay flags after the
 // select kernel) and the heap-emulating exact kernel answers it.
 //
-// Margin: ONE bf16 product, fixed at compile time (flat_mfma.hip's two-term split was the alternative; the queues are short: DESIGN.md 4f.1).
+// ivfflat_mc_bound_kernel / ivfflat_mc_bound_eval_kernel.  The bound pass of such a batch: a query's bound only has to be at or above the
+// exact key of its true k-th neighbour, so the largest EXACT key of any k distinct allowed rows of its nearest partition is one.  The
+// tile machinery above (the queries grouped by their FIRST probe) only chooses the rows: per query 256 class minima of (surrogate order
+// key, row in partition), class = row in partition % 256; the eval kernel scores the k lowest with ivfflat_dist_rt and writes the largest
+// key to tkey.  A bad surrogate loosens the bound and cannot make it wrong: no margin, no guard, no permissive branch on this path.
+//
+// Margin (the main pass's filter): ONE bf16 product, fixed at compile time (flat_mfma.hip's two-term split was the alternative; the queues are short: DESIGN.md 4f.1).
 // flat_mfma_wide.hip derives |x~.q~ - x.q| <= (2^-7 + 2^-16 + d 2^-23) |x| |q| <= 0.00832 |x| |q| for d <= 4096.  Two things differ here: |x|^2
 // is summed by two threads in stage order, not in the reference's order, and |q| under cosine is this file's own sqrt of such a sum -- each
 // within (d / 2 + 2) 2^-24 <= 1.3e-4 relative of the real value -- so the margins are restated with that room: EW = 0.0088 (L2, dot) and
@@ -54,6 +60,7 @@ typedef float im_f32x16 __attribute__((ext_vector_type(16)));
 constexpr int IM_KT = 64, IM_LS = IM_KT + 8;      // elements of d per stage; LDS row stride in bf16 elements
 constexpr int IM_TM = 128, IM_TN = 128;           // rows and query slots per tile
 constexpr int IM_CAP = FLAT_MC_QUEUE_CAP;
+constexpr int IM_CLASSES = 256;                   // bound pass: entries per query, a row's class is its number in the partition % 256
 constexpr float IM_EW = 0.0088f;
 constexpr float IM_EWC = 0.0092f;
 constexpr float IM_E_TINY = 7.888609052210118e-31f;      // 2^-100
@@ -96,8 +103,11 @@ __device__ __forceinline__ float im_side(float dot, float xk, float t) {
   else return __builtin_fmaf(-2.0f, dot, xk - t);
 }
 
-template <int METRIC>
-__global__ __launch_bounds__(256, 2) void ivfflat_mc_filter_kernel(IvfFlatMcArgs a) {
+// the tile walk of both passes.  BOUND = false: the main pass's filter (a.pair_* = the (query, probe) pairs by partition).  BOUND = true:
+// the bound pass (a.pair_* = the queries grouped by their NEAREST partition, one pair per query); staging and products are the same
+// instructions, the epilogue publishes instead of testing.
+template <int METRIC, bool BOUND>
+__device__ __forceinline__ void im_scan_tiles(const IvfFlatMcArgs &a) {
   constexpr int HK = IM_KT / 2;      // a staging thread moves half a stage of one row and of one query
   __shared__ __attribute__((aligned(16))) uint16_t Xs[IM_TM * IM_LS];
   __shared__ __attribute__((aligned(16))) uint16_t Qs[IM_TN * IM_LS];
@@ -110,6 +120,7 @@ __global__ __launch_bounds__(256, 2) void ivfflat_mc_filter_kernel(IvfFlatMcArgs
   const uint32_t r1 = a.part_offsets[part + 1];
   const uint32_t qs = a.pair_starts[part], qe = a.pair_starts[part + 1];
   if (row0 >= r1 || qs == qe) return;      // (uniform: an item's second half past the partition's end, or a partition nobody probes)
+  const uint32_t pdiv = BOUND ? 1u : (uint32_t)a.nprobes;      // entries of pair_idx are query * pdiv + probe
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int j = lane & 31, g = lane >> 5;
   const int wr = wave >> 1, wq = wave & 1;
@@ -152,8 +163,8 @@ __global__ __launch_bounds__(256, 2) void ivfflat_mc_filter_kernel(IvfFlatMcArgs
     if (threadIdx.x < IM_TN) {
       float t = METRIC == METRIC_COSINE ? INFINITY : -INFINITY;      // padding slot: nothing passes
       int qi = -1;
-      if (j0 + threadIdx.x < qe) {
-        qi = (int)(a.pair_idx[j0 + threadIdx.x] / (uint32_t)a.nprobes);
+      if (j0 + threadIdx.x < qe) qi = (int)(a.pair_idx[j0 + threadIdx.x] / pdiv);
+      if (!BOUND && qi >= 0) {      // (the bound pass has no thresholds yet and reads no tqs)
         const uint32_t tk = a.pool.tkey[qi];
         const float T = tk >= 0xFF800000u ? INFINITY : key_to_float(tk);      // no bound (fewer than k rows in the nearest partition) / NaN bound: every row is a candidate
         const float qn = a.qn[qi];
@@ -165,7 +176,7 @@ __global__ __launch_bounds__(256, 2) void ivfflat_mc_filter_kernel(IvfFlatMcArgs
       tqs[threadIdx.x] = t;
       tqi[threadIdx.x] = qi;
     }
-    qsrc = j0 + (uint32_t)sr < qe ? a.qb + (int64_t)(a.pair_idx[j0 + sr] / (uint32_t)a.nprobes) * a.dp + sh * HK : nullptr;
+    qsrc = j0 + (uint32_t)sr < qe ? a.qb + (int64_t)(a.pair_idx[j0 + sr] / pdiv) * a.dp + sh * HK : nullptr;
 
     im_f32x16 acc[2][2];
 #pragma unroll
@@ -211,6 +222,28 @@ __global__ __launch_bounds__(256, 2) void ivfflat_mc_filter_kernel(IvfFlatMcArgs
       const uint32_t row = row0 + (uint32_t)tr;
       const bool rvalid = row < r1 && row_allowed(a.allow, row);
       const float n2 = xn2s[tr];
+      if constexpr (BOUND) {
+        // the accumulator only ORDERS the rows of a query (its own constant dropped): L2 |x|^2 - 2 x~.q~, dot -x~.q~, cosine -x~.q~ / |x|.
+        // Every allowed row offers (order key of that value, row in partition) to class `row in partition % 256` of its query; a class
+        // keeps its minimum, different classes are different rows.  A NaN value offers nothing.  No margin: the eval kernel scores the rows.
+        if (rvalid) {
+          const uint32_t rp = row - a.part_offsets[part];
+          const float xs = METRIC == METRIC_COSINE ? sqrtf(n2) : n2;
+#pragma unroll
+          for (int bj = 0; bj < 2; ++bj) {
+#pragma unroll
+            for (int v = 0; v < 16; ++v) {
+              const int qi = tqi[wq * 64 + bj * 32 + 8 * (v >> 2) + 4 * g + (v & 3)];
+              if (qi < 0) continue;
+              const float dot = acc[bi][bj][v];
+              const float val = METRIC == METRIC_COSINE ? -dot / xs : METRIC == METRIC_DOT ? -dot : __builtin_fmaf(-2.0f, dot, xs);
+              // (no load ahead of the atomic: a class sees partition size / 256 offers, most pass; with one the pass took 3 to 10 % longer)
+              if (val == val) atomicMin(&a.bcls[(int64_t)qi * IM_CLASSES + (rp % IM_CLASSES)], ((unsigned long long)order_key(val) << 32) | rp);
+            }
+          }
+        }
+        continue;
+      }
       float xk;
       bool odd, tiny = false;      // odd: every query takes the row; tiny: the queries that are tiny too take it
       if constexpr (METRIC == METRIC_COSINE) {
@@ -256,6 +289,46 @@ __global__ __launch_bounds__(256, 2) void ivfflat_mc_filter_kernel(IvfFlatMcArgs
   }
 }
 
+template <int METRIC>
+__global__ __launch_bounds__(256, 2) void ivfflat_mc_filter_kernel(IvfFlatMcArgs a) { im_scan_tiles<METRIC, false>(a); }
+
+template <int METRIC>
+__global__ __launch_bounds__(256, 2) void ivfflat_mc_bound_kernel(IvfFlatMcArgs a) { im_scan_tiles<METRIC, true>(a); }
+
+// the bound of one query from its classes: one workgroup per query, one thread per class.  The k entries of lowest surrogate value are k
+// DISTINCT allowed rows of the query's nearest partition; the largest of their EXACT keys (ivfflat_dist_rt, the reference's arithmetic)
+// is at or above the exact key of the query's true k-th neighbour, whichever k rows the surrogate chose.  Fewer than k classes filled
+// (fewer than k allowed rows, or rows that met in one class): no bound, 0xFFFFFFFF, which the main pass reads as "every row".
+template <int METRIC>
+__global__ __launch_bounds__(256) void ivfflat_mc_bound_eval_kernel(IvfFlatMcArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float qt[];   // [d]
+  __shared__ unsigned long long ent[IM_CLASSES];
+  __shared__ uint32_t kmax;
+  static_assert(IM_CLASSES == 256, "one thread per class");
+  const FlatPool &p = a.pool;
+  const int qi = blockIdx.x, d = a.d;
+  const unsigned long long e = a.bcls[(int64_t)qi * IM_CLASSES + threadIdx.x];
+  const bool valid = e != ~0ull;
+  ent[threadIdx.x] = e;
+  if (threadIdx.x == 0) kmax = 0u;
+  for (int i = threadIdx.x; i < d; i += 256) qt[i] = a.q[(int64_t)qi * d + i];
+  const int nvalid = __syncthreads_count(valid);
+  if (nvalid < p.k) {      // (uniform)
+    if (threadIdx.x == 0) { p.tkey[qi] = 0xFFFFFFFFu; p.trid[qi] = ~0ull; }
+    return;
+  }
+  float qnorm = 0.0f;
+  if constexpr (METRIC == METRIC_COSINE) qnorm = norm_l2_rt(qt, d);
+  int rank = 0;      // entries are distinct (their low words are different rows); an empty class is above every entry
+  for (int c = 0; c < IM_CLASSES; ++c) rank += ent[c] < e ? 1 : 0;
+  if (valid && rank < p.k) {
+    const uint32_t row = a.part_offsets[a.probes[(int64_t)qi * a.nprobes]] + (uint32_t)e;
+    atomicMax(&kmax, order_key(ivfflat_dist_rt<METRIC, false>(qt, qnorm, a.vec + (int64_t)row * d, d)));
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) { p.tkey[qi] = kmax; p.trid[qi] = ~0ull; }
+}
+
 // exact evaluation of the queued rows: one workgroup per query, one lane per queued row; the query sits in LDS as in ivfflat_kernel<0, ..>
 template <int METRIC>
 __global__ __launch_bounds__(256) void ivfflat_mc_eval_kernel(IvfFlatMcArgs a) {
@@ -296,12 +369,33 @@ int ivfflat_mc_scratch(lance_hip_ctx *ctx, int qch, int d, IvfFlatMcArgs *a) {
   a->scnt = ctx->scratch_t<uint32_t>("ivfflat.mc.scnt", (size_t)qch);
   a->qflag = ctx->scratch_t<uint32_t>("ivfflat.mc.qflag", (size_t)qch);
   a->squeue = ctx->scratch_t<uint32_t>("ivfflat.mc.squeue", (size_t)qch * IM_CAP);
-  return a->qb && a->qn && a->scnt && a->qflag && a->squeue ? LANCE_HIP_OK : LANCE_HIP_ENOMEM;
+  a->bcls = ctx->scratch_t<unsigned long long>("ivfflat.mc.bcls", (size_t)qch * IM_CLASSES);
+  return a->qb && a->qn && a->scnt && a->qflag && a->squeue && a->bcls ? LANCE_HIP_OK : LANCE_HIP_ENOMEM;
 }
 
 // once per query chunk: the bf16 plane and the norms of a.q's nqc queries
 void ivfflat_mc_prepare_queries(lance_hip_ctx *ctx, const IvfFlatMcArgs &a, int nqc, bool cosine) {
   hipLaunchKernelGGL(ivfflat_mc_query_prep_kernel, dim3(nqc), dim3(64), 0, ctx->stream, a.q, a.d, a.dp, cosine ? 1 : 0, a.qb, a.qn);
+}
+
+// the bound pass of one chunk.  a.pair_starts / a.pair_idx: the chunk's queries grouped by their nearest partition; a.probes, a.q, a.qb set.
+int launch_ivfflat_mc_bound(lance_hip_ctx *ctx, const IvfFlatMcArgs &a, int metric, unsigned n_items, int nqc) {
+  ScopedTimer t(ctx, "ivfflat_mc_bound");
+  LH_CHECK_HIP(lh::memset_async(a.bcls, 0xFF, (size_t)nqc * IM_CLASSES * 8, ctx->stream));
+  const dim3 grid(2 * n_items);
+  const size_t lds = (size_t)((a.d + 3) & ~3) * 4;
+  if (metric == LANCE_HIP_COSINE) {
+    hipLaunchKernelGGL(ivfflat_mc_bound_kernel<METRIC_COSINE>, grid, dim3(256), 0, ctx->stream, a);
+    hipLaunchKernelGGL(ivfflat_mc_bound_eval_kernel<METRIC_COSINE>, dim3(nqc), dim3(256), lds, ctx->stream, a);
+  } else if (metric == LANCE_HIP_DOT) {
+    hipLaunchKernelGGL(ivfflat_mc_bound_kernel<METRIC_DOT>, grid, dim3(256), 0, ctx->stream, a);
+    hipLaunchKernelGGL(ivfflat_mc_bound_eval_kernel<METRIC_DOT>, dim3(nqc), dim3(256), lds, ctx->stream, a);
+  } else {
+    hipLaunchKernelGGL(ivfflat_mc_bound_kernel<METRIC_L2>, grid, dim3(256), 0, ctx->stream, a);
+    hipLaunchKernelGGL(ivfflat_mc_bound_eval_kernel<METRIC_L2>, dim3(nqc), dim3(256), lds, ctx->stream, a);
+  }
+  LH_CHECK_HIP(hipGetLastError());
+  return LANCE_HIP_OK;
 }
 
 // the main pass of one chunk: filter, then evaluate the queues into the pools.  Every threshold (a.pool.tkey) is set, the pairs are grouped.

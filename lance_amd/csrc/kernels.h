@@ -156,10 +156,14 @@ struct IvfFlatMcArgs {
   uint32_t *squeue;              // [nq][FLAT_MC_QUEUE_CAP] row numbers whose surrogate distance passed
   uint32_t *qflag;               // [nq] 1 = the queue overflowed: the exact kernel answers the query
   uint32_t *ppart;               // [nq][cap] partition of every pool entry
+  const uint32_t *probes;        // [nq][nprobes] bound pass: a query's nearest partition is its first probe
+  unsigned long long *bcls;      // [nq][256] bound pass: per class (row in partition % 256) the least (surrogate order key << 32 | row in partition)
   FlatPool pool;
 };
 int ivfflat_mc_scratch(lance_hip_ctx *ctx, int qch, int d, IvfFlatMcArgs *a);      // the ivfflat.mc.* slots and dp
 void ivfflat_mc_prepare_queries(lance_hip_ctx *ctx, const IvfFlatMcArgs &a, int nqc, bool cosine);
+// the bound pass on the matrix cores: a.pair_starts / a.pair_idx are the queries grouped by nearest partition; writes a.pool.tkey / trid
+int launch_ivfflat_mc_bound(lance_hip_ctx *ctx, const IvfFlatMcArgs &a, int metric, unsigned n_items, int nqc);
 int launch_ivfflat_mc(lance_hip_ctx *ctx, const IvfFlatMcArgs &a, int metric, unsigned n_items, int nqc);
 void launch_ivfflat_mc_flags(lance_hip_ctx *ctx, const IvfFlatMcArgs &a, int nqc, uint32_t *flags);
 

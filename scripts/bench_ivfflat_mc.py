@@ -9,7 +9,12 @@ Every child builds the same indices from the same seeds and records per (shape, 
   * the library's stage timers (ivfflat_bound, ivfflat_scan, ivfflat_mc, ivfflat_mc_eval, ivfflat_exact) and the rows the filter queued
     per query (count:ivfflat_mc_queued) over one more call with the timers on;
   * the same time for batches of G * nlist / nprobes queries, G = 16, 32, 64 pairs per partition;
-  * the ids and distances of the whole batch, compared between the routes by the parent: they must be equal."""
+  * the ids and distances of the whole batch, compared between the routes by the parent: they must be equal.
+
+--bound compares the BOUND pass instead (the bound pass) -> profiles/ivfflat_mc_bound.json: "mc_bound" with
+LANCE_HIP_FLAT_MC_BOUND_G=0 (the matrix-core bound pass at any batch size) against "query_major_bound" with LANCE_HIP_NO_FLAT_MC_BOUND=1
+(the parent's route: query-major bound pass, matrix-core main pass); same shapes, same protocol, same sweep, and per point whether the
+new route's slowest call beat the other's fastest."""
 import argparse
 import json
 import os
@@ -22,8 +27,9 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-ROUTES = {"mc": {"LANCE_HIP_FLAT_MC_G": "0"}, "query_major": {"LANCE_HIP_NO_FLAT_MC": "1"}}
-TIMERS = ("ivfflat_bound", "ivfflat_scan", "ivfflat_mc", "ivfflat_mc_eval", "ivfflat_exact")
+ROUTES = {"mc": {"LANCE_HIP_FLAT_MC_G": "0"}, "query_major": {"LANCE_HIP_NO_FLAT_MC": "1"}}      # (new, old)
+BOUND_ROUTES = {"mc_bound": {"LANCE_HIP_FLAT_MC_BOUND_G": "0"}, "query_major_bound": {"LANCE_HIP_NO_FLAT_MC_BOUND": "1"}}
+TIMERS = ("ivfflat_bound", "ivfflat_mc_bound", "ivfflat_scan", "ivfflat_mc", "ivfflat_mc_eval", "ivfflat_exact")
 SHAPES = ((200_000, 768), (100_000, 1536))
 METRICS = ("l2", "cosine")
 SWEEP = (16, 32, 64)
@@ -74,6 +80,7 @@ def child(a):
             name = f"{n}x{d}_{metric}"
             ix = lance_amd.create_index(x, "IVF_FLAT", metric=metric, num_partitions=a.nlist, max_iters=10, engine=eng)
             rec[name] = {"main": timed(ix, q), "sweep": {str(g): timed(ix, q[:-(-g * a.nlist // a.nprobes)].contiguous()) for g in SWEEP}}
+            print(name, rec[name]["main"]["ms"], file=sys.stderr, flush=True)
             ids, dists = ix.search_device(q, a.k, a.nprobes)
             answers[name + "_ids"], answers[name + "_dists"] = ids.cpu().numpy(), dists.cpu().numpy()
             del ix
@@ -89,35 +96,43 @@ def main():
     ap.add_argument("--queries", type=int, default=10_000)
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--nprobes", type=int, default=10)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ivfflat_mc.json"))
+    ap.add_argument("--bound", action="store_true", help="compare the bound pass's routes instead of the main pass's")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--child-out", default=None)
     a = ap.parse_args()
     if a.child_out:
         return child(a)
 
+    routes = BOUND_ROUTES if a.bound else ROUTES
+    new, old = routes
+    a.out = a.out or os.path.join(ROOT, "profiles", "ivfflat_mc_bound.json" if a.bound else "ivfflat_mc.json")
     tmp = tempfile.mkdtemp()
     runs, answers = {}, {}
-    for name, env in ROUTES.items():
+    for name, env in routes.items():
         path = os.path.join(tmp, f"{name}.json")
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child-out", path] + sys.argv[1:], env=dict(os.environ, **env), timeout=1100)
         if r.returncode != 0:
             raise SystemExit(f"the {name} child failed with status {r.returncode}")      # nothing more is started on the device
         runs[name] = json.load(open(path))
         answers[name] = np.load(path + ".npz")
-    cases = [k for k in runs["mc"] if k != "device"]
+    cases = [k for k in runs[new] if k != "device"]
     rec = {"workload": {"shapes": SHAPES, "metrics": METRICS, "nlist": a.nlist, "queries": a.queries, "k": a.k, "nprobes": a.nprobes, "dtype": "float32"},
-           "device": runs["mc"]["device"], "runs": runs,
-           "same_ids": {c: bool((answers["mc"][c + "_ids"] == answers["query_major"][c + "_ids"]).all()) for c in cases},
-           "same_distance_bits": {c: bool((answers["mc"][c + "_dists"].view(np.uint32) == answers["query_major"][c + "_dists"].view(np.uint32)).all())
+           "device": runs[new]["device"], "runs": runs,
+           "same_ids": {c: bool((answers[new][c + "_ids"] == answers[old][c + "_ids"]).all()) for c in cases},
+           "same_distance_bits": {c: bool((answers[new][c + "_dists"].view(np.uint32) == answers[old][c + "_dists"].view(np.uint32)).all())
                                   for c in cases}}
-    rec["ms_per_batch"] = {c: {name: runs[name][c]["main"]["ms"] for name in ROUTES} for c in cases}
-    rec["sweep_ms_per_batch"] = {c: {str(g): {name: runs[name][c]["sweep"][str(g)]["ms"] for name in ROUTES} for g in SWEEP} for c in cases}
-    rec["queued_rows_per_query"] = {c: runs["mc"][c]["main"]["queued_rows_per_query"] for c in cases}
+    rec["ms_per_batch"] = {c: {name: runs[name][c]["main"]["ms"] for name in routes} for c in cases}
+    rec["sweep_ms_per_batch"] = {c: {str(g): {name: runs[name][c]["sweep"][str(g)]["ms"] for name in routes} for g in SWEEP} for c in cases}
+    rec["queued_rows_per_query"] = {c: {name: runs[name][c]["main"]["queued_rows_per_query"] for name in routes} for c in cases}
+    # the acceptance rule of DESIGN.md 4f.1: the new route's slowest call against the other route's fastest
+    wins = lambda r: r[new]["max"] < r[old]["min"]
+    rec["new_slowest_beats_old_fastest"] = {c: dict({"main": wins(rec["ms_per_batch"][c])}, **{g: wins(r) for g, r in rec["sweep_ms_per_batch"][c].items()})
+                                            for c in cases}
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as fh:
         json.dump(rec, fh, indent=1)
     print(json.dumps({k: v for k, v in rec.items() if k != "runs"}))
-    print(json.dumps({name: {c: runs[name][c]["main"]["stages"] for c in cases} for name in ROUTES}))
+    print(json.dumps({name: {c: runs[name][c]["main"]["stages"] for c in cases} for name in routes}))
 
 
 if __name__ == "__main__":
