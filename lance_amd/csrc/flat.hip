@@ -552,6 +552,72 @@ static int flat_topk_v2(lance_hip_ctx *ctx, int metric, const float *x, const vo
   return LANCE_HIP_OK;      // (plane_guard gives a > 4 GiB plane back after waiting for the stream)
 }
 
+// f16 columns on the f16 matrix cores (flat_mfma_f16.hip): flat_topk_v2's epoch loop -- pool reset, a first exact epoch of FLAT_CAP / 2
+// rows, growing epochs, flat_select_kernel, the overflow repair -- with that file's kernels, which read the column (xh) and the queries
+// (qh) as the caller stored them; qf is the queries' widened copy, the operand of the exact functions.  A loop of its own: the f32
+// callers' flat_topk_v2 is untouched.  Every chunk of the call passes flat_mfma_f16_supported (flat_topk_impl splits a short last chunk off).
+static int flat_topk_f16(lance_hip_ctx *ctx, int metric, const void *xh, const uint64_t *row_ids, int64_t n, int d, const void *qh,
+                         const float *qf, int nq, int k, const FlatRange &rg, uint64_t *ids, float *dists) {
+  const int qch = std::min(nq, FLAT_QCHUNK);
+  FlatPool a;
+  a.x = nullptr; a.x_native = xh; a.x_dtype = LANCE_HIP_F16;
+  a.row_ids = row_ids; a.k = k; a.cap = FLAT_CAP;
+  a.tkey = ctx->scratch_t<uint32_t>("flat2.tkey", qch);
+  a.trid = ctx->scratch_t<uint64_t>("flat2.trid", qch);
+  a.cnt = ctx->scratch_t<uint32_t>("flat2.cnt", qch);
+  a.pkeys = ctx->scratch_t<uint32_t>("flat2.pkeys", (size_t)qch * FLAT_CAP);
+  a.prids = ctx->scratch_t<uint64_t>("flat2.prids", (size_t)qch * FLAT_CAP);
+  a.overflow = ctx->scratch_t<uint32_t>("flat2.ovf", 1);
+  if (!a.tkey || !a.trid || !a.cnt || !a.pkeys || !a.prids || !a.overflow) return LANCE_HIP_ENOMEM;
+  const int64_t growth = std::max<int64_t>(2, FLAT_CAP / (16 * (int64_t)k));
+  const float *xn2 = nullptr;
+  LH_TRY(flat_mfma_f16_prepare_rows(ctx, xh, n, d, metric, &xn2));
+  const size_t sel_lds = (size_t)FLAT_CAP * 12;
+  for (int qc0 = 0; qc0 < nq; qc0 += qch) {
+    a.q = qf + (int64_t)qc0 * d;
+    a.nq = std::min(qch, nq - qc0);
+    const void *qhc = static_cast<const char *>(qh) + (size_t)qc0 * d * 2;
+    uint64_t *oid = ids + (int64_t)qc0 * k;
+    float *od = dists + (int64_t)qc0 * k;
+    const float *qn2 = nullptr;
+    LH_TRY(flat_mfma_f16_prepare_queries(ctx, qhc, a.q, a.nq, d, metric, &qn2, &a.q_norm));
+    hipLaunchKernelGGL(flat_pool_reset_kernel, dim3(cdiv(a.nq, 256)), dim3(256), 0, ctx->stream, a, 1, rg.start_key());
+    int64_t seen = 0;
+    if (n == 0) {
+      a.r0 = a.r1 = 0;
+      hipLaunchKernelGGL(flat_select_kernel, dim3(a.nq), dim3(256), sel_lds, ctx->stream, a, 1, oid, od);
+    }
+    while (seen < n) {
+      const int64_t want = seen == 0 ? FLAT_CAP / 2 : seen * (growth - 1);
+      a.r0 = seen;
+      a.r1 = std::min<int64_t>(n, seen + std::max<int64_t>(want, 1));
+      if (n - a.r1 < (a.r1 - a.r0) / 4) a.r1 = n;            // do not leave a small tail epoch
+      {
+        ScopedTimer t(ctx, "flat_scan");
+        if (seen > 0 && seen >= k) LH_TRY(launch_flat_filter_mfma_f16(ctx, a, d, metric, qhc, xn2, qn2));
+        else LH_TRY(launch_flat_f16_exact(ctx, a, d, metric));
+      }
+      seen = a.r1;
+      hipLaunchKernelGGL(flat_select_kernel, dim3(a.nq), dim3(256), sel_lds, ctx->stream, a, seen == n ? 1 : 0, oid, od);
+    }
+    // overflow repair: rows <= T (T only ever tightens) are re-collected from scratch until every pool fits
+    for (int round = 0; round < 64; ++round) {
+      uint32_t ovf = 0;
+      LH_CHECK_HIP(hipMemcpyAsync(&ovf, a.overflow, 4, hipMemcpyDeviceToHost, ctx->stream));
+      LH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+      if (!ovf) break;
+      LH_REQUIRE(round < 63, "flat_topk: candidate pool did not converge");
+      ctx->count_stage("flat_repair");
+      hipLaunchKernelGGL(flat_pool_reset_kernel, dim3(cdiv(a.nq, 256)), dim3(256), 0, ctx->stream, a, 0, 0xFFFFFFFFu);
+      a.r0 = 0; a.r1 = n;
+      LH_TRY(launch_flat_f16_exact(ctx, a, d, metric));
+      hipLaunchKernelGGL(flat_select_kernel, dim3(a.nq), dim3(256), sel_lds, ctx->stream, a, 1, oid, od);
+    }
+  }
+  LH_CHECK_HIP(hipGetLastError());
+  return LANCE_HIP_OK;
+}
+
 template <int D>
 static void launch_flat_fixed(lance_hip_ctx *ctx, const FlatArgs &a, int metric, dim3 grid, bool ranged) {
   constexpr int TR = (8192 / D) > 256 ? 256 : (8192 / D);
@@ -1359,6 +1425,18 @@ static int flat_topk_impl(const char *what, lance_hip_ctx *ctx, int dtype, int m
     bool done = false;
     LH_TRY(flat_topk_small(ctx, metric, dtype, x, row_ids, n, d, qs2, nq, k, rg, ids, dists, &done));
     if (done) return LANCE_HIP_OK;
+  }
+  // f16 columns, query batches: the f16 matrix cores read the column and the queries as they are (flat_mfma_f16.hip).  A last chunk
+  // under the gate's batch size takes the routes below, as a call of its own.
+  if (d <= 4096 && flat_mfma_f16_supported(dtype, metric, (int)d, (int)k, (int)std::min<uint32_t>(nq, FLAT_QCHUNK), (int64_t)n, x, q, rg)) {
+    const uint32_t tail = nq % FLAT_QCHUNK;
+    const uint32_t main_nq = (tail != 0 && tail < 128) ? nq - tail : nq;      // (nq >= 128 here, so a short tail follows a whole chunk)
+    const float *qf3;
+    LH_TRY(as_f32(ctx, dtype, q, (size_t)main_nq * d, "f16.q", &qf3));
+    LH_TRY(flat_topk_f16(ctx, metric, x, row_ids, (int64_t)n, (int)d, q, qf3, (int)main_nq, (int)k, rg, ids, dists));
+    if (main_nq == nq) return LANCE_HIP_OK;
+    return flat_topk_impl(what, ctx, dtype, metric, x, row_ids, n, d, static_cast<const char *>(q) + (size_t)main_nq * d * 2, tail, k, rg,
+                          ids + (size_t)main_nq * k, dists + (size_t)main_nq * k);
   }
   if (!h32 && flat_v2_supported(metric, d, k) && !getenv("LANCE_HIP_FLAT_V1")) {
     const float *xf2 = nullptr, *qf2;

@@ -136,6 +136,13 @@ int flat_mfma_wide_prepare_rows(lance_hip_ctx *ctx, const float *x, int64_t n, i
 int flat_mfma_wide_prepare_queries(lance_hip_ctx *ctx, const float *q, int nq, int d, const uint16_t **qb, const float **qn2);
 int launch_flat_filter_mfma_wide(lance_hip_ctx *ctx, const FlatPool &e, int d, int metric, const uint16_t *xb, const float *xn2, const uint16_t *qb,
                                  const float *qn2);
+// native f16 MFMA surrogate + exact re-check for query batches against an f16 column, any d % 8 == 0 up to 4096 (flat_mfma_f16.hip)
+bool flat_mfma_f16_supported(int dtype, int metric, int d, int k, int nq, int64_t n, const void *x, const void *q, const FlatRange &rg);
+int flat_mfma_f16_prepare_rows(lance_hip_ctx *ctx, const void *x, int64_t n, int d, int metric, const float **xn2);
+int flat_mfma_f16_prepare_queries(lance_hip_ctx *ctx, const void *qh, const float *qf, int nq, int d, int metric, const float **qn2,
+                                  const float **qnorm);
+int launch_flat_f16_exact(lance_hip_ctx *ctx, const FlatPool &e, int d, int metric);
+int launch_flat_filter_mfma_f16(lance_hip_ctx *ctx, const FlatPool &e, int d, int metric, const void *qh, const float *xn2, const float *qn2);
 
 // IVF_FLAT batched search: partition-major main pass on the bf16 matrix cores, any d % 4 == 0 up to 4096, L2 / dot / cosine (flat_ivf_mc.hip).
 // The gate is flat.hip's plan_ivfflat_mc; the pool, the thresholds and the grouped pairs are ivfflat_search_impl's.
